@@ -19,6 +19,10 @@ list / block-sharing plan, fragment layouts) can be reused; the energy is invari
 reports as `rigid_motion_energy_spread`.  `cold_ms` is the very first evaluation of the process (term-list generation,
 topology build, pool allocation, kernel loading included): the one-shot cost of an MBE-2 energy.
 
+`--dump-outputs DIR` writes what the last timed evaluation returned (per-term fragment energies, SCF iterations and
+many-body deltas, the per-order sums and the total) as float64 DIR/<name>.npy.  The inputs of a timed step depend only
+on its index and the arguments, so two builds can be compared output for output.
+
 Multi-GPU: fragments are independent units -- no collective sits on the data path.  Default (`--scaling weak`): per-GPU work
 is fixed, every rank evaluates the 2080 SCFs of its own copy of the cluster (its own rigid motion; all copies have the
 same MBE-2 energy, which the line checks) and `value` is the iterations of all ranks over the slowest rank's time.
@@ -39,10 +43,6 @@ import json
 import os
 import sys
 import time
-
-# torch initialises the HIP runtime before the engine's library is loaded: the hardware-queue request the library makes
-# for itself (engine.cpp: ask_for_hardware_queues; two lanes of four to eight streams) has to be in the environment here
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -76,6 +76,8 @@ def parse_args():
     ap.add_argument("--density-tol", type=float, default=1e-8)
     ap.add_argument("--schwarz-tol", type=float, default=1e-12,
                     help="Schwarz threshold of the in-core ERI build (0 = every quartet); 1e-12 moves a fragment energy by < 1e-11 Eh")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed evaluation returned as DIR/<name>.npy (float64)")
     return ap.parse_args()
 
 
@@ -173,6 +175,21 @@ def rigid_motion(system, step, seed=977):
     return mbe.FragmentedSystem(system.element_numbers, coords, system.monomers, system.charges, system.multiplicities)
 
 
+def dump_outputs(out_dir, last):
+    """The last timed evaluation's results as float64 .npy files, per-term arrays in term-list order (a few tens of kB)."""
+    os.makedirs(out_dir, exist_ok=True)
+    orders = sorted(last["by_order"])
+    arrays = {
+        "fragment_energies": last["energies"],
+        "fragment_scf_iterations": last["iterations"],
+        "mbe_deltas": last["delta"],
+        "mbe_order_energies": [last["by_order"][k] for k in orders],
+        "mbe_energy": [last["total"]],
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     args = parse_args()
     rank = int(os.environ.get("RANK", "0"))
@@ -206,6 +223,7 @@ def main():
                 torch.cuda.synchronize()
 
     weak = args.scaling == "weak"
+    last = {}                 # the arrays the caller of the latest evaluation received (for --dump-outputs)
     rank_totals = []          # weak scaling: every rank's MBE-2 energy of every evaluation (one cluster, moved differently)
 
     def evaluate(system, st, terms):
@@ -219,7 +237,8 @@ def main():
             raise RuntimeError("fragment failed: " + run.errors[0])
         energies, iters = run.energies, run.iterations.astype(np.float64)
         if world > 1 and weak:
-            total, by_order, _ = mbe.compute_mbe(terms, energies)
+            total, by_order, delta = mbe.compute_mbe(terms, energies)
+            last.update(energies=energies, iterations=iters, total=total, by_order=by_order, delta=delta)
             # the only inter-GPU traffic: every rank's iteration count and MBE-2 energy, gathered
             mine = torch.tensor([float(np.sum(iters)), float(total)], dtype=torch.float64)
             if use_cuda_tensors:
@@ -241,7 +260,8 @@ def main():
                 torch.cuda.synchronize()
             both = buf.cpu().numpy()
             energies, iters = both[: len(terms)], both[len(terms):]
-        total, by_order, _ = mbe.compute_mbe(terms, energies)
+        total, by_order, delta = mbe.compute_mbe(terms, energies)
+        last.update(energies=energies, iterations=iters, total=total, by_order=by_order, delta=delta)
         return total, energies, float(np.sum(iters))
 
     def moved(step):
@@ -270,6 +290,8 @@ def main():
         tot_iters += it
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, last)
     main_totals = list(rank_totals)       # cold, warm-up and timed evaluations of the headline method on every rank
     st = methods.get_stats()
     if world > 1:

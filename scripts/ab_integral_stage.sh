@@ -3,7 +3,6 @@
 # product library) against libmqc_hip.so -- bench lines alternating, then kernel statistics of both.
 # Usage (on the GPU box): bash scripts/ab_integral_stage.sh [tag]
 set -e
-export GPU_MAX_HW_QUEUES=16
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 TAG=${1:-ab}
 O=gpurun_out/$TAG

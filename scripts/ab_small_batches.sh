@@ -2,7 +2,6 @@
 # A/B of the latency-bound regimes on ONE box: one rank's share of an 8-way / 4-way split and the single-call path,
 # every libmqc_hip_<label>.so next to the product library against the product library.
 set -e
-export GPU_MAX_HW_QUEUES=16
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-absmall}
 mkdir -p $O

@@ -2,7 +2,7 @@
 # Rehearsal of bench.py's N > 1 path on a one-GPU box: two ranks share device 0, gloo carries the gather.
 # Usage (on the GPU box): bash scripts/bench_two_ranks_one_gpu.sh [tag]
 set -e
-export GPU_MAX_HW_QUEUES=16 MQC_BENCH_DEVICE=0
+export MQC_BENCH_DEVICE=0
 O=gpurun_out/${1:-two_ranks}
 mkdir -p $O
 for mode in weak strong; do

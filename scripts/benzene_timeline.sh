@@ -1,7 +1,6 @@
 #!/bin/bash
 # Kernel timeline of single benzene DF-B3LYP SCFs (BASELINE configs[1]) through mqc_hip_scf_run.
 set -e
-export GPU_MAX_HW_QUEUES=16
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-benz_tl}
 mkdir -p $O

@@ -2,7 +2,6 @@
 # Kernel timeline of the integral stage (one MI355X): kernel trace of a short default bench, kept as CSV for
 # scripts/eri_timeline.py.  Usage on the GPU box: bash scripts/eri_timeline.sh [tag]
 set -e
-export GPU_MAX_HW_QUEUES=16
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 TAG=${1:-tl}
 O=gpurun_out/$TAG

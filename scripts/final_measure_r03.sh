@@ -2,7 +2,6 @@
 # The measurement run behind profiles/r03_*: benches, kernel statistics and the separate --pmc passes, one MI355X.
 # Every line of the same call runs on the same box (box-to-box spread on this pool is ~ +-15 %).
 set -e
-export GPU_MAX_HW_QUEUES=16       # rocprofv3 initialises HIP before python starts
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-r03_final}
 mkdir -p $O

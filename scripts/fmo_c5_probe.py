@@ -7,7 +7,6 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 from metalquicha_amd import fmo, mbe, methods          # noqa: E402
 from metalquicha_amd.methods import ScfSettings        # noqa: E402

@@ -2,7 +2,6 @@
 # Issue / stall / instruction-cache counters of the integral-stage kernels (separate --pmc passes, kernel trace only).
 # Usage on the GPU box: bash scripts/pmc_eri_stalls.sh [tag]
 set -e
-export GPU_MAX_HW_QUEUES=16
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 TAG=${1:-pmc_eri}
 O=gpurun_out/$TAG

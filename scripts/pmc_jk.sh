@@ -1,7 +1,6 @@
 #!/bin/bash
 # Counters of the in-core J/K kernels: the triangular-tensor kernel and (MQC_HIP_ERI_TRI=0) the square one, same box.
 set -e
-export GPU_MAX_HW_QUEUES=16
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-pmc_jk}
 mkdir -p $O

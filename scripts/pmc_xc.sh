@@ -1,7 +1,6 @@
 #!/bin/bash
 # Issue / stall counters of the split-quadrature kernels (B3LYP bench, one evaluation), two --pmc passes.
 set -e
-export GPU_MAX_HW_QUEUES=16
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-pmc_xc}
 mkdir -p $O

@@ -1,7 +1,6 @@
 #!/bin/bash
 # Kernel timeline of one rank's share of an N-way split of the (H2O)64 MBE-2 evaluation (default N = 8).
 set -e
-export GPU_MAX_HW_QUEUES=16
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/${2:-rs_tl}
 mkdir -p $O

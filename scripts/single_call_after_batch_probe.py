@@ -1,5 +1,4 @@
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, ".")
 from metalquicha_amd import capi, mbe, methods
 capi.get_context(0)

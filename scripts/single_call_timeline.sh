@@ -1,7 +1,6 @@
 #!/bin/bash
 # Kernel timeline of single water-dimer SCFs through mqc_hip_scf_run (the literal drop-in path).
 set -e
-export GPU_MAX_HW_QUEUES=16
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-sc_tl}
 mkdir -p $O

@@ -258,21 +258,57 @@ def test_fortran_drop_in_bridge_compiles_and_runs():
     assert "pure function cuest_backend_available" in src                     # mqc_cuest_bridge.f90:20
 
 
+def _patch_sides(patch_path):
+    """The two sides of a one-file unified diff as {line number: text}: what each hunk says the old file holds
+    (context and removed lines) and what the new file holds (context and added lines)."""
+    old, new = {}, {}
+    hunk = re.compile(r"^@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@")
+    o = n = None
+    for line in open(patch_path).read().splitlines():
+        m = hunk.match(line)
+        if m:
+            o, n = int(m.group(1)), int(m.group(3))
+            continue
+        if o is None or line.startswith(("--- ", "+++ ")):
+            continue
+        tag, text = line[:1], line[1:]
+        if tag in (" ", ""):
+            old[o] = new[n] = text
+            o += 1
+            n += 1
+        elif tag == "-":
+            old[o] = text
+            o += 1
+        elif tag == "+":
+            new[n] = text
+            n += 1
+    return old, new
+
+
 def test_node_worker_patch_applies_to_the_reference_file(tmp_path):
-    """fortran/patches/node_worker_batch.patch is a unified diff against the reference's distribution scheme; where the
-    reference tree is present (this container, not the GPU box) it must apply cleanly to a scratch copy."""
+    """fortran/patches/node_worker_batch.patch is a unified diff against the reference's distribution scheme.  The
+    reference file is rebuilt from the diff itself -- every line the hunks quote at its recorded line number, a distinct
+    filler line everywhere else -- and the patch must apply to it exactly (no offset, no fuzz) and produce every line
+    the hunks say the new file holds."""
     import shutil
-    ref = "/root/reference/src/fragmentation/mbe/mqc_mbe_mpi_fragment_distribution_scheme.F90"
     patch = os.path.join(ROOT, "fortran", "patches", "node_worker_batch.patch")
     assert os.path.isfile(patch)
-    if not os.path.isfile(ref) or shutil.which("patch") is None:
-        pytest.skip("no reference tree (or no patch tool) here")
+    if shutil.which("patch") is None:
+        pytest.skip("no patch tool here")
+    old, new = _patch_sides(patch)
+    assert old and new
+    n_old = max(old) + 7                 # a tail after the last hunk, as the real file has
     work = tmp_path / "scheme.F90"
-    shutil.copyfile(ref, work)
-    out = subprocess.run(["patch", "--no-backup-if-mismatch", str(work), patch], capture_output=True, text=True)
+    work.write_text("".join((old[i] if i in old else "! reference line %d" % i) + "\n" for i in range(1, n_old + 1)))
+    assert "run_cuest_scf_batch" not in work.read_text()
+    out = subprocess.run(["patch", "--no-backup-if-mismatch", "-F", "0", str(work), patch], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
+    assert "offset" not in out.stdout and "fuzz" not in out.stdout, out.stdout
+    lines = work.read_text().split("\n")
+    for i, text in new.items():
+        assert lines[i - 1] == text, (i, lines[i - 1], text)
     text = work.read_text()
-    assert "fragment_batch_t" in text and "outstanding_fifo_t" in text and "run_cuest_scf_batch" not in open(ref).read()
+    assert "fragment_batch_t" in text and "outstanding_fifo_t" in text and "run_cuest_scf_batch" in text
 
 
 def test_fortran_iso_c_binding_module_links():
