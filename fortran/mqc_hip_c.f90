@@ -163,5 +163,17 @@ module mqc_hip_c
          real(c_double), intent(inout) :: j(*)
          integer(c_int) :: r
       end function
+      !! packed in-core ERI matrix of erf(omega r12)/r12, m(npair*npair) with pair(i,j) = i(i+1)/2 + j (0-based, i >= j)
+      function mqc_hip_eri_packed_attenuated(ctx, mol, orbital, omega, schwarz_tol, m) &
+         bind(C, name="mqc_hip_eri_packed_attenuated") result(r)
+         import :: c_int, c_ptr, c_double, mqc_hip_molecule_t, mqc_hip_basis_t
+         type(c_ptr), value :: ctx
+         type(mqc_hip_molecule_t), intent(in) :: mol
+         type(mqc_hip_basis_t), intent(in) :: orbital
+         real(c_double), value :: omega
+         real(c_double), value :: schwarz_tol
+         real(c_double), intent(inout) :: m(*)
+         integer(c_int) :: r
+      end function
    end interface
 end module mqc_hip_c

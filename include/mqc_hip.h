@@ -197,6 +197,10 @@ int mqc_hip_int1e(mqc_hip_context *ctx, const mqc_hip_molecule_t *mol, const mqc
  * (molecule_eris, mqc_libcint_integrals.F90:1449) */
 int mqc_hip_eri_packed(mqc_hip_context *ctx, const mqc_hip_molecule_t *mol, const mqc_hip_basis_t *orbital,
                        double schwarz_tol, double *M /* [npair*npair] */);
+/* the same packed matrix for the long-range operator erf(omega r12)/r12, omega > 0 (the K_lr integrals of
+ * range-separated hybrids, mqc_libcint_rhf.f90:1045-1065); screened with the Coulomb Schwarz bounds, which bound it */
+int mqc_hip_eri_packed_attenuated(mqc_hip_context *ctx, const mqc_hip_molecule_t *mol, const mqc_hip_basis_t *orbital,
+                                  double omega, double schwarz_tol, double *M /* [npair*npair] */);
 /* J[D], K[D] from the in-core tensor (build_fock, mqc_libcint_rhf.f90:1491-1574) */
 int mqc_hip_jk_incore(mqc_hip_context *ctx, const mqc_hip_molecule_t *mol, const mqc_hip_basis_t *orbital,
                       const double *D, double *J, double *K);

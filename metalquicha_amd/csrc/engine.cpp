@@ -181,7 +181,7 @@ struct Slot {
 
 // carve one chunk's arrays out of the slot's pools
 static int carve_batch(mqc_hip_context* ctx, Slot& sl, const Topology& topo, const TopologyDev& td, int nfrag, bool with_eri, BatchView& bv,
-                       bool uhf = false, int npc = 0, bool hx = false)
+                       bool uhf = false, int npc = 0, bool hx = false, bool rsh = false)
 {
     const int n = topo.nao;
     const size_t nn = (size_t)n * n, nf = (size_t)nfrag;
@@ -240,8 +240,18 @@ static int carve_batch(mqc_hip_context* ctx, Slot& sl, const Topology& topo, con
             bv.eri_tri_sb = d_sb;
             bv.jk_loaded = d_sb + 2 * (size_t)topo.npair + 8;
         }
-        bv.eri = (double*)sl.eri->ensure(sizeof(double) * nf * bv.eri_stride);
+        // range-separated hybrids: the tensor of erf(omega r12)/r12 right behind it (same layout), then J scratch and K_lr
+        // of each spin for its J/K stream -- all of it counted in the footprint that sizes the chunks (rsh_doubles)
+        const size_t lr = rsh ? nf * bv.eri_stride + nf * nn * (uhf ? 3 : 2) : 0;
+        bv.eri = (double*)sl.eri->ensure(sizeof(double) * (nf * bv.eri_stride + lr));
         if (!bv.eri) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (ERI tensor)");
+        bv.eri_lr = nullptr; bv.Jlr = bv.Klr = bv.Klrb = nullptr;
+        if (rsh) {
+            bv.eri_lr = bv.eri + nf * bv.eri_stride;
+            bv.Jlr = bv.eri_lr + nf * bv.eri_stride;
+            bv.Klr = bv.Jlr + nf * nn;
+            if (uhf) bv.Klrb = bv.Klr + nf * nn;
+        }
     }
     return MQC_HIP_OK;
 }
@@ -260,6 +270,13 @@ static int validate_options(const mqc_hip_scf_options_t& o, const Topology& topo
         if (!parse_functional(o.functional, tmp, e)) { msg = e; return MQC_HIP_ERR_UNSUPPORTED; }
         if (tmp.gga == 2 && topo.nao > 140) { msg = "meta-GGA functionals are available up to n_ao = 140"; return MQC_HIP_ERR_UNSUPPORTED; }
         if (tmp.ncomp > 0 && topo.natoms > 64) { msg = "XC grid: fragments above 64 atoms are not supported yet"; return MQC_HIP_ERR_UNSUPPORTED; }
+        if (tmp.omega > 0.0) {
+            // range-separated hybrids need K_lr from a second in-core tensor of erf(omega r12)/r12: nothing else forms it
+            if (o.density_fitting) { msg = "range-separated functionals (wb97x) need exact long-range exchange K_lr: density fitting with erf-attenuated fits is not built; use exact in-core ERIs"; return MQC_HIP_ERR_UNSUPPORTED; }
+            if (o.eri_mode == MQC_HIP_ERI_DIRECT) { msg = "range-separated functionals (wb97x) run on the in-core exact-ERI path only: the direct path forms no long-range exchange K_lr"; return MQC_HIP_ERR_UNSUPPORTED; }
+            if (!incore_supported(topo.nao) || topo.nao > 116) { msg = "range-separated functionals (wb97x) run on the in-core exact-ERI path only (n_ao <= 116); larger fragments would need a direct K_lr, which is not built"; return MQC_HIP_ERR_UNSUPPORTED; }
+            if (o.want_gradient) { msg = "analytic gradients of range-separated functionals (wb97x) are not built (energies only)"; return MQC_HIP_ERR_UNSUPPORTED; }
+        }
     }
     if (o.want_gradient) {
         XcSpec tg; std::string eg;
@@ -430,7 +447,10 @@ int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology* aux, c
     const bool uhf_mem = opts.unrestricted || topo.multiplicity != 1 || (topo.nelec % 2) != 0;
     // in-core tensor: the square, or -- where the batch takes the triangular block layout (kern_fock.hip) -- 0.53 of it
     const size_t tensor = jk_tri_layout(n, topo.npair, ntot, uhf_mem) ? (size_t)((topo.npair + 1) / 2) * (size_t)jk_tri_block(topo.npair) : np * np;
-    const size_t two_e = use_df ? (2 * (size_t)naux * np + 3 * (size_t)naux * naux) : (use_direct ? 2 * (size_t)n * n : tensor);
+    // range-separated hybrids carry a second tensor (erf(omega r12)/r12) plus J scratch and K_lr per spin (carve_batch)
+    const bool rsh = xc.omega > 0.0;
+    const size_t rsh_doubles = rsh ? tensor + (size_t)n * n * (uhf_mem ? 3 : 2) : 0;
+    const size_t two_e = use_df ? (2 * (size_t)naux * np + 3 * (size_t)naux * naux) : (use_direct ? 2 * (size_t)n * n : tensor + rsh_doubles);
     // radial cache of the quadrature (MQC_HIP_XC_RADIAL_CACHE=0 turns it off): 2 doubles per shell and (padded) grid point
     static const bool rad_cache_on = [] { const char* e = std::getenv("MQC_HIP_XC_RADIAL_CACHE"); return !(e && e[0] == '0'); }();
     const int rad_pt = xc_tile_points(n);
@@ -506,7 +526,7 @@ int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology* aux, c
         hipStream_t s = sl.s;
         const double t0 = now_s();
         BatchView& bv = job.bv;
-        int rc = carve_batch(ctx, sl, topo, td, nf, !use_df && !use_direct, bv, uhf, npc, hx);
+        int rc = carve_batch(ctx, sl, topo, td, nf, !use_df && !use_direct, bv, uhf, npc, hx, rsh && !use_df && !use_direct);
         if (rc != MQC_HIP_OK) return rc;
         bv.nalpha = nalpha; bv.nbeta = nbeta;
         bv.naux = naux; bv.aux = tdx; bv.unit = ctx->d_unit;
@@ -518,7 +538,8 @@ int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology* aux, c
             bv.df_work = base + 2 * a3 + 2 * mm;
             HIP_CHECK_RET(hipMemsetAsync(bv.scal, 0, sizeof(double) * (size_t)nf * 8, s));
         }
-        bv.nocc = nocc; bv.exx = xc.exx; bv.e_tol = opts.energy_tol; bv.d_tol = opts.density_tol;
+        // range-separated hybrids: K is folded to exx K + exx_lr K_lr before the step, which then takes all of it
+        bv.nocc = nocc; bv.exx = rsh ? 1.0 : xc.exx; bv.e_tol = opts.energy_tol; bv.d_tol = opts.density_tol;
         bv.xc = xc; bv.grid = grid; bv.Vxc = nullptr;
         if (xc.ncomp > 0) {
             char* gw = (char*)sl.gridw->ensure(sizeof(double) * (size_t)nf * ((size_t)grid.npts + (size_t)n * n * (uhf ? 2 : 1) + rad_doubles + pt4_doubles) + 2048);
@@ -584,6 +605,12 @@ int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology* aux, c
         else if (use_direct) launch_direct_setup(bv, topo, s);
         else {
             launch_eri(bv, topo, stol, s, job.hx.data());
+            if (rsh) {
+                // the long-range tensor: same lists, screening (the Coulomb bounds bound it) and block sharing
+                BatchView vl = bv;
+                vl.eri = bv.eri_lr;
+                launch_eri(vl, topo, stol, s, job.hx.data(), xc.omega);
+            }
             // the bounds of a screened build tell the J/K kernel which pair rows are all zeros (triangular tensor only)
             if (stol > 0.0 && bv.eri_tri) eri_schwarz_view(bv.slot, &bv.jk_q, &bv.jk_qthresh);
         }
@@ -697,6 +724,18 @@ int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology* aux, c
                     BatchView vb = bv;
                     vb.D = bv.Db; vb.J = bv.Jb; vb.K = bv.Kb;
                     launch_jk_incore(vb, true, s);
+                }
+                if (rsh) {
+                    // K_lr of each spin density from the long-range tensor (its J is not used), folded into K
+                    BatchView vl = bv;
+                    vl.eri = bv.eri_lr; vl.J = bv.Jlr; vl.K = bv.Klr; vl.jk_loaded = nullptr;
+                    launch_jk_incore(vl, true, s);
+                    launch_exchange_fold(bv, bv.K, bv.Klr, xc.exx, xc.exx_lr, s);
+                    if (uhf) {
+                        vl.D = bv.Db; vl.K = bv.Klrb;
+                        launch_jk_incore(vl, true, s);
+                        launch_exchange_fold(bv, bv.Kb, bv.Klrb, xc.exx, xc.exx_lr, s);
+                    }
                 }
             }
             HIP_CHECK_RET(hipEventRecord(sl.e1, s));
@@ -1449,19 +1488,33 @@ int mqc_hip_int1e(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc
     return MQC_HIP_OK;
 }
 
-int mqc_hip_eri_packed(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, double schwarz_tol, double* M)
+// the packed tensor of one fragment: 1/r12 (omega = 0) or erf(omega r12)/r12
+static int stage_eri_packed(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, double omega,
+                            double schwarz_tol, double* M)
 {
     StageBatch sb;
     int rc = stage_setup(ctx, mol, bas, true, sb);
     if (rc != MQC_HIP_OK) return rc;
     // stage-level check of the tensor: poison it first, so that an element no class list covers shows up as NaN
     HIP_CHECK_RET(hipMemsetAsync(sb.bv.eri, 0xFF, sizeof(double) * (size_t)sb.topo.npair * sb.topo.npair, ctx->stream));
-    launch_eri(sb.bv, sb.topo, schwarz_tol, ctx->stream);
+    launch_eri(sb.bv, sb.topo, schwarz_tol, ctx->stream, nullptr, omega);
     HIP_CHECK_RET(hipStreamSynchronize(ctx->stream));
     HIP_CHECK_RET(hipGetLastError());
     const size_t np = (size_t)sb.topo.npair;
     HIP_CHECK_RET(hipMemcpy(M, sb.bv.eri, sizeof(double) * np * np, hipMemcpyDeviceToHost));
     return MQC_HIP_OK;
+}
+
+int mqc_hip_eri_packed(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, double schwarz_tol, double* M)
+{
+    return stage_eri_packed(ctx, mol, bas, 0.0, schwarz_tol, M);
+}
+
+int mqc_hip_eri_packed_attenuated(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, double omega,
+                                  double schwarz_tol, double* M)
+{
+    if (!(omega > 0.0) || !std::isfinite(omega)) return fail(MQC_HIP_ERR_VALIDATION, "attenuated ERIs: omega must be positive and finite");
+    return stage_eri_packed(ctx, mol, bas, omega, schwarz_tol, M);
 }
 
 int mqc_hip_jk_incore(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, const double* D, double* J, double* K)

@@ -81,13 +81,18 @@ private:
 };
 
 // exchange-correlation components (libxc-equivalent ids, unpolarised)
-enum : int { XC_LDA_X = 1, XC_LDA_C_VWN, XC_LDA_C_VWN_RPA, XC_GGA_X_B88, XC_GGA_C_LYP, XC_GGA_X_PBE, XC_GGA_C_PBE, XC_MGGA_X_TPSS, XC_MGGA_C_TPSS };
+// XC_HYB_GGA_XC_WB97X: the whole semi-local part of wB97X as one component (kern_xc.hip, wb97x_point)
+enum : int { XC_LDA_X = 1, XC_LDA_C_VWN, XC_LDA_C_VWN_RPA, XC_GGA_X_B88, XC_GGA_C_LYP, XC_GGA_X_PBE, XC_GGA_C_PBE, XC_MGGA_X_TPSS, XC_MGGA_C_TPSS,
+             XC_HYB_GGA_XC_WB97X };
 struct XcSpec {
     int ncomp = 0;
     int id[6] = {0, 0, 0, 0, 0, 0};
     double w[6] = {0, 0, 0, 0, 0, 0};
     double exx = 1.0;     // exact-exchange fraction
     int gga = 0;          // 1: needs grad rho; 2: meta-GGA, needs grad rho and tau
+    // range-separated hybrids: K_eff = exx K + exx_lr K_lr(omega), K_lr from erf(omega r12)/r12 (omega = 0: none)
+    double omega = 0.0;
+    double exx_lr = 0.0;
 };
 
 // quadrature grid of a batch: per-topology point list (atom, template point) + per-fragment weights
@@ -183,6 +188,13 @@ struct BatchView {      // plain pointers handed to kernels
     // these are the BETA spin's; densities are D_s = C_s,occ C_s,occ^T (no factor 2)
     int uhf, nalpha, nbeta;
     double *Db, *Cb, *Fb, *Jb, *Kb, *Vprevb, *epsb, *diis_fb, *diis_eb;
+    // two-electron operator of the ERI class kernels' ATT variants: erf(omega r12)/r12, omega2 = omega^2 (set by
+    // launch_eri on its own copy of the view; the Coulomb kernels never read it)
+    double omega2 = 0.0;
+    // range-separated hybrids (xc.omega > 0): the second in-core tensor, of erf(omega r12)/r12, in the layout of eri
+    // (same eri_stride), J scratch of its J/K stream and K_lr of each spin; nullptr otherwise
+    double* eri_lr = nullptr;
+    double *Jlr = nullptr, *Klr = nullptr, *Klrb = nullptr;
 };
 
 // Where an integral goes in the pair matrix of one fragment: both mirror elements of the square, or the one stored
@@ -295,16 +307,20 @@ int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology* aux, c
 void launch_int1e(const BatchView& bv, const Topology& topo, hipStream_t s);
 void launch_dipole(const BatchView& bv, const Topology& topo, hipStream_t s, bool accumulate = false);
 // host_xyz (optional, [nfrag][natoms][3] as uploaded): enables block sharing between fragments with identical atoms
-void launch_eri(const BatchView& bv, const Topology& topo, double schwarz_tol, hipStream_t s, const double* host_xyz = nullptr);
+// omega > 0: the tensor of erf(omega r12)/r12 instead of 1/r12, same layout, lists, screening and block sharing
+void launch_eri(const BatchView& bv, const Topology& topo, double schwarz_tol, hipStream_t s, const double* host_xyz = nullptr,
+                double omega = 0.0);
 // optional head start of the screened build (bounds + zero fill on side streams); launch_eri joins it
 void launch_eri_bounds(const BatchView& bv, const Topology& topo, double schwarz_tol, hipStream_t s);
 // wave-cooperative kernel for classes with an f (or g) shell (kern_eri_general.hip); false: class too large for LDS
 bool launch_eri_general(const BatchView& bv, int la, int lb, int lc, int ld, const int* d_list, int nq, const int* d_tasks, int ntasks,
-                        const double* Q, double thresh, hipStream_t s);
+                        const double* Q, double thresh, hipStream_t s, bool attenuated = false);
 bool launch_df3c_general(const BatchView& bv, int la, int lb, int lp, const int* d_list, int nq, hipStream_t s);
 bool launch_schwarz_general(const BatchView& bv, int la, int lb, const int* d_pairs, int npairs, double* Qout, hipStream_t s);
 void eri_set_side_streams(int slot, const hipStream_t* streams, int count);
 void launch_jk_incore(const BatchView& bv, bool only_active, hipStream_t s);
+// K <- exx K + exx_lr K_lr for every fragment not yet done (range-separated hybrids, before the SCF step)
+void launch_exchange_fold(const BatchView& bv, double* K, const double* Klr, double exx, double exx_lr, hipStream_t s);
 void launch_direct_setup(const BatchView& bv, const Topology& topo, hipStream_t s);
 void launch_jk_direct(const BatchView& bv, const Topology& topo, double thresh, bool only_active, hipStream_t s);
 void launch_orthogonalizer(const BatchView& bv, hipStream_t s);

@@ -20,6 +20,7 @@
 #pragma once
 #include "engine.hpp"
 #include "md_integrals.hpp"
+#include <type_traits>
 
 namespace mqc {
 
@@ -52,6 +53,16 @@ __device__ __forceinline__ void count_formed_sum(unsigned long long* ctr, int mi
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     if (ctr && (threadIdx.x & 63) == 0) atomicAdd(ctr, (unsigned long long)v);
+}
+
+// ATT: the erf(omega r12)/r12 variant of a class kernel (md_integrals.hpp, ErfOp), omega^2 from the batch view
+template <bool ATT>
+using EriOp = typename std::conditional<ATT, ErfOp, CoulombOp>::type;
+template <bool ATT>
+__device__ __forceinline__ EriOp<ATT> eri_op(const BatchView& bv)
+{
+    if constexpr (ATT) return ErfOp{bv.omega2};
+    else return CoulombOp{};
 }
 
 __device__ __forceinline__ size_t pair_index(int i, int j)
@@ -147,7 +158,7 @@ __global__ void __launch_bounds__(64) schwarz_kernel(BatchView bv, const int* __
 }
 
 // ---------------------------------------------------------------------------------------
-template <int LA, int LB, int LC, int LD>
+template <int LA, int LB, int LC, int LD, bool ATT = false>
 __global__ void __launch_bounds__(64) eri_kernel(BatchView bv, const int* __restrict__ quartets, int nquart,
                                                  const int* __restrict__ tasks, int ntasks,
                                                  const double* __restrict__ Q, double thresh)
@@ -178,7 +189,7 @@ __global__ void __launch_bounds__(64) eri_kernel(BatchView bv, const int* __rest
     constexpr int NC = ncart(LA) * ncart(LB) * ncart(LC) * ncart(LD);
     constexpr int NSA = nsph(LA), NSB = nsph(LB), NSC = nsph(LC), NSD = nsph(LD);
     double cart[NC], sph[NC];
-    eri_cart_block_src<LA, LB, LC, LD>(bra, ket, bv.boys, cart);
+    eri_cart_block_src<LA, LB, LC, LD>(bra, ket, bv.boys, cart, NoTwin(), 0, 0, eri_op<ATT>(bv));
     block_to_spherical<LA, LB, LC, LD>(bv.c2s, cart, sph);
 
     const int oa = tp.sh_aoff[A], ob = tp.sh_aoff[B], oc = tp.sh_aoff[C], od = tp.sh_aoff[D];
@@ -227,7 +238,7 @@ __global__ void __launch_bounds__(64) eri_kernel(BatchView bv, const int* __rest
 // once and stores one spherical block per member combination.  Same thread mapping as eri_kernel.
 constexpr int TWIN_FLAG = 1 << 16;
 
-template <int LA, int LB, int LC, int LD>
+template <int LA, int LB, int LC, int LD, bool ATT = false>
 __global__ void __launch_bounds__(64) eri_twin_kernel(BatchView bv, const int* __restrict__ quartets, int nquart,
                                                       const int* __restrict__ tasks, int ntasks,
                                                       const double* __restrict__ Q, double thresh)
@@ -268,7 +279,7 @@ __global__ void __launch_bounds__(64) eri_twin_kernel(BatchView bv, const int* _
     constexpr int NSA = nsph(LA), NSB = nsph(LB), NSC = nsph(LC), NSD = nsph(LD);
     constexpr int MA = twin_mult(true, LA), MB = twin_mult(true, LB), MC = twin_mult(true, LC), MD = twin_mult(true, LD);
     double acc[MA * MB * MC * MD * NC];
-    eri_cart_block_twin<LA, LB, LC, LD>(sa, sb, sc, sd, tw, bv.boys, acc);
+    eri_cart_block_twin<LA, LB, LC, LD>(sa, sb, sc, sd, tw, bv.boys, acc, 0, 0, eri_op<ATT>(bv));
 
     const size_t np = (size_t)bv.npair;
     const PairStore M = make_pair_store(bv, f);
@@ -315,7 +326,7 @@ __global__ void __launch_bounds__(64) eri_twin_kernel(BatchView bv, const int* _
 // 3.3 ms integral stage waited for that thread.  Here ONE wave takes an (entry, fragment): its 64 lanes share the
 // entry's bra primitive pairs (lane, lane + 64, ...; eri_cart_block_twin's partial form), the partial blocks are summed
 // across the wave, lane 0 transforms and stores.
-template <int LA, int LB, int LC, int LD>
+template <int LA, int LB, int LC, int LD, bool ATT = false>
 __global__ void __launch_bounds__(64) eri_twin_wave_kernel(BatchView bv, const int* __restrict__ quartets, int nquart,
                                                            const double* __restrict__ Q, double thresh)
 {
@@ -348,7 +359,7 @@ __global__ void __launch_bounds__(64) eri_twin_wave_kernel(BatchView bv, const i
     constexpr int NSA = nsph(LA), NSB = nsph(LB), NSC = nsph(LC), NSD = nsph(LD);
     constexpr int MA = twin_mult(true, LA), MB = twin_mult(true, LB), MC = twin_mult(true, LC), MD = twin_mult(true, LD);
     double acc[MA * MB * MC * MD * NC];
-    eri_cart_block_twin<LA, LB, LC, LD>(sa, sb, sc, sd, tw, bv.boys, acc, lane, 64);
+    eri_cart_block_twin<LA, LB, LC, LD>(sa, sb, sc, sd, tw, bv.boys, acc, lane, 64, eri_op<ATT>(bv));
 #pragma unroll
     for (int i = 0; i < MA * MB * MC * MD * NC; ++i) {
         double v = acc[i];
@@ -410,7 +421,7 @@ struct TensorSink {
     }
 };
 
-template <int LA, int LB, int LC, int LD>
+template <int LA, int LB, int LC, int LD, bool ATT = false>
 __global__ void __launch_bounds__(64) eri_pass_kernel(BatchView bv, const int* __restrict__ quartets, int nquart,
                                                       const int* __restrict__ tasks, int ntasks,
                                                       const double* __restrict__ Q, double thresh)
@@ -438,7 +449,7 @@ __global__ void __launch_bounds__(64) eri_pass_kernel(BatchView bv, const int* _
     const size_t np = (size_t)bv.npair;
     TensorSink sink{make_pair_store(bv, f), tp.sh_aoff[A], tp.sh_aoff[B], tp.sh_aoff[C], tp.sh_aoff[D], A == B, C == D};
     constexpr int CH = eri_pass_chunk(LA, LB, LC, LD);
-    eri_passes_src<LA, LB, LC, LD, CH, 0>(bra, ket, bv.boys, bv.c2s, lds + threadIdx.x, 64, sink);
+    eri_passes_src<LA, LB, LC, LD, CH, 0>(bra, ket, bv.boys, bv.c2s, lds + threadIdx.x, 64, sink, eri_op<ATT>(bv));
 }
 
 struct MaxSink {
@@ -602,7 +613,7 @@ void launch_eri_digest_class(const BatchView& bv, const int* d_list, int nq, con
 // Launchers: one explicit instantiation per class, spread over several translation units
 // (kern_eri_inst.hip compiled with -DERI_GROUP=k) so that the classes compile in parallel.
 // d_list: entries already on the device; d_tasks (optional): (entry, fragment) pairs replacing the dense product
-template <int LA, int LB, int LC, int LD>
+template <int LA, int LB, int LC, int LD, bool ATT = false>
 void launch_eri_class(const BatchView& bv, const int* d_list, int nq, const int* d_tasks, int ntasks,
                       const double* Q, double thresh, hipStream_t s)
 {
@@ -612,30 +623,30 @@ void launch_eri_class(const BatchView& bv, const int* d_list, int nq, const int*
     if constexpr (eri_uses_passes(LA, LB, LC, LD)) {
         constexpr int CH = eri_pass_chunk(LA, LB, LC, LD);
         const size_t lds = sizeof(double) * 64 * ncart(LA) * ncart(LB) * CH;
-        auto kern = eri_pass_kernel<LA, LB, LC, LD>;
+        auto kern = eri_pass_kernel<LA, LB, LC, LD, ATT>;
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, s, bv, d_list, nq, d_tasks, ntasks, Q, thresh);
     } else {
-        hipLaunchKernelGGL((eri_kernel<LA, LB, LC, LD>), dim3(blocks), dim3(64), 0, s, bv, d_list, nq, d_tasks, ntasks, Q, thresh);
+        hipLaunchKernelGGL((eri_kernel<LA, LB, LC, LD, ATT>), dim3(blocks), dim3(64), 0, s, bv, d_list, nq, d_tasks, ntasks, Q, thresh);
     }
 }
 
-template <int LA, int LB, int LC, int LD>
+template <int LA, int LB, int LC, int LD, bool ATT = false>
 void launch_eri_twin_class(const BatchView& bv, const int* d_list, int nq, const int* d_tasks, int ntasks,
                            const double* Q, double thresh, hipStream_t s)
 {
     const long total = d_tasks ? (long)ntasks : (long)nq * bv.nfrag;
     if (nq == 0 || total == 0) return;
-    hipLaunchKernelGGL((eri_twin_kernel<LA, LB, LC, LD>), dim3((int)((total + 63) / 64)), dim3(64), 0, s, bv, d_list, nq, d_tasks, ntasks, Q, thresh);
+    hipLaunchKernelGGL((eri_twin_kernel<LA, LB, LC, LD, ATT>), dim3((int)((total + 63) / 64)), dim3(64), 0, s, bv, d_list, nq, d_tasks, ntasks, Q, thresh);
 }
 
 // batches of at most this many fragments form their twin entries one WAVE per (entry, fragment)
 constexpr int ERI_TWIN_WAVE_MAX_FRAGMENTS = 16;
-template <int LA, int LB, int LC, int LD>
+template <int LA, int LB, int LC, int LD, bool ATT = false>
 void launch_eri_twin_wave_class(const BatchView& bv, const int* d_list, int nq, const double* Q, double thresh, hipStream_t s)
 {
     if (nq == 0 || bv.nfrag == 0) return;
-    hipLaunchKernelGGL((eri_twin_wave_kernel<LA, LB, LC, LD>), dim3((unsigned)nq * (unsigned)bv.nfrag), dim3(64), 0, s, bv, d_list, nq, Q, thresh);
+    hipLaunchKernelGGL((eri_twin_wave_kernel<LA, LB, LC, LD, ATT>), dim3((unsigned)nq * (unsigned)bv.nfrag), dim3(64), 0, s, bv, d_list, nq, Q, thresh);
 }
 
 template <int LA, int LB>

@@ -119,7 +119,11 @@ bool parse_functional(const char* name_in, XcSpec& spec, std::string& err)
     }
     else if (n == "pbe0") { add(XC_GGA_X_PBE, 0.75); add(XC_GGA_C_PBE, 1.0); spec.exx = 0.25; spec.gga = 1; }
     else if (n == "tpss") { add(XC_MGGA_X_TPSS, 1.0); add(XC_MGGA_C_TPSS, 1.0); spec.exx = 0.0; spec.gga = 2; }     // mqc_xc_spec.f90:142-166
-    else { err = "functional '" + n + "' is not available on the HIP backend (svwn, pbe, blyp, b3lyp, pbe0, tpss)"; return false; }
+    else if (n == "wb97x") {   // libxc hyb_gga_xc_wb97x: cam_alpha = 1, cam_beta = -0.842294, omega = 0.3 (mqc_xc_spec.f90:186-191)
+        add(XC_HYB_GGA_XC_WB97X, 1.0);
+        spec.exx = 0.157706; spec.exx_lr = 0.842294; spec.omega = 0.3; spec.gga = 1;
+    }
+    else { err = "functional '" + n + "' is not available on the HIP backend (svwn, pbe, blyp, b3lyp, pbe0, tpss, wb97x)"; return false; }
     return true;
 }
 

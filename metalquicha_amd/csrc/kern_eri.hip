@@ -27,7 +27,8 @@ static bool class_is_general(int la, int lb, int lc, int ld, int gen_from)
 }
 
 #define ERI_DECL(a, b, c, d) \
-    extern template void launch_eri_class<a, b, c, d>(const BatchView&, const int*, int, const int*, int, const double*, double, hipStream_t);
+    extern template void launch_eri_class<a, b, c, d>(const BatchView&, const int*, int, const int*, int, const double*, double, hipStream_t); \
+    extern template void launch_eri_class<a, b, c, d, true>(const BatchView&, const int*, int, const int*, int, const double*, double, hipStream_t);
 #define SCHWARZ_DECL(a, b) \
     extern template void launch_schwarz_class<a, b>(const BatchView&, const int*, int, int*, double*, hipStream_t);
 ERI_DECL(0, 0, 0, 0) ERI_DECL(1, 0, 0, 0) ERI_DECL(1, 0, 1, 0) ERI_DECL(1, 1, 0, 0) ERI_DECL(1, 1, 1, 0) ERI_DECL(1, 1, 1, 1)
@@ -35,11 +36,13 @@ ERI_DECL(2, 0, 0, 0) ERI_DECL(2, 0, 1, 0) ERI_DECL(2, 0, 1, 1) ERI_DECL(2, 0, 2,
 ERI_DECL(2, 1, 0, 0) ERI_DECL(2, 1, 1, 0) ERI_DECL(2, 1, 1, 1) ERI_DECL(2, 1, 2, 0) ERI_DECL(2, 1, 2, 1)
 ERI_DECL(2, 2, 0, 0) ERI_DECL(2, 2, 1, 0) ERI_DECL(2, 2, 1, 1) ERI_DECL(2, 2, 2, 0) ERI_DECL(2, 2, 2, 1) ERI_DECL(2, 2, 2, 2)
 #define TWIN_DECL(a, b, c, d) \
-    extern template void launch_eri_twin_class<a, b, c, d>(const BatchView&, const int*, int, const int*, int, const double*, double, hipStream_t);
+    extern template void launch_eri_twin_class<a, b, c, d>(const BatchView&, const int*, int, const int*, int, const double*, double, hipStream_t); \
+    extern template void launch_eri_twin_class<a, b, c, d, true>(const BatchView&, const int*, int, const int*, int, const double*, double, hipStream_t);
 TWIN_DECL(0, 0, 0, 0) TWIN_DECL(1, 0, 0, 0) TWIN_DECL(1, 0, 1, 0) TWIN_DECL(1, 1, 0, 0)
 TWIN_DECL(1, 1, 1, 0) TWIN_DECL(2, 0, 0, 0) TWIN_DECL(2, 0, 1, 0) TWIN_DECL(2, 1, 0, 0)
 #define TWINW_DECL(a, b, c, d) \
-    extern template void launch_eri_twin_wave_class<a, b, c, d>(const BatchView&, const int*, int, const double*, double, hipStream_t);
+    extern template void launch_eri_twin_wave_class<a, b, c, d>(const BatchView&, const int*, int, const double*, double, hipStream_t); \
+    extern template void launch_eri_twin_wave_class<a, b, c, d, true>(const BatchView&, const int*, int, const double*, double, hipStream_t);
 TWINW_DECL(0, 0, 0, 0) TWINW_DECL(1, 0, 0, 0)
 SCHWARZ_DECL(0, 0) SCHWARZ_DECL(1, 0) SCHWARZ_DECL(1, 1) SCHWARZ_DECL(2, 0) SCHWARZ_DECL(2, 1) SCHWARZ_DECL(2, 2)
 
@@ -535,8 +538,16 @@ __global__ void schwarz_save_kernel(const double* __restrict__ Q, double* __rest
     dst[B * ns + A] = Q[A * ns + B];
 }
 
-void launch_eri(const BatchView& bv, const Topology& topo, double schwarz_tol, hipStream_t s, const double* host_xyz)
+void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol, hipStream_t s, const double* host_xyz, double omega)
 {
+    // erf(omega r)/r: the ATT instantiations of every route below, omega^2 carried in this call's copy of the view.
+    // Screening reuses the Coulomb Schwarz bounds unchanged: erf(w r)/r is positive definite and its Fourier transform
+    // 4 pi exp(-k^2/4w^2)/k^2 lies below 4 pi/k^2, the transform of 1/r, at every k.  A diagonal integral (ab|ab) is the
+    // integral of |rho_ab(k)|^2 against that transform, so (ab|ab)_w <= (ab|ab) and Q_ab bounds both operators:
+    // |(ab|cd)_w| <= sqrt((ab|ab)_w (cd|cd)_w) <= Q_ab Q_cd.
+    const bool att = omega > 0.0;
+    BatchView bv = bv_in;
+    bv.omega2 = att ? omega * omega : 0.0;
     EriSlotState& st = eri_slot_state(bv.slot);
     const size_t np = (size_t)bv.npair;
     // The class lists cover every element of the pair matrix, so the unscreened build overwrites the whole
@@ -632,22 +643,34 @@ void launch_eri(const BatchView& bv, const Topology& topo, double schwarz_tol, h
     auto to_general = [&](const Topology::ClassList& c) { return class_is_general(c.la, c.lb, c.lc, c.ld, gen_from); };
 #define ERI_CASE(a, b, c, d_)                                                                                         \
     if (!general && cl.la == a && cl.lb == b && cl.lc == c && cl.ld == d_) {                                          \
+        if (att) {                                                                                                    \
+            launch_eri_class<a, b, c, d_, true>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream()); \
+            launch_eri_class<a, b, c, d_, true>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, st.side[rr++ % ERI_SIDE_STREAMS]); \
+        } else {                                                                                                      \
         launch_eri_class<a, b, c, d_>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream());         \
         launch_eri_class<a, b, c, d_>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, st.side[rr++ % ERI_SIDE_STREAMS]); \
+        }                                                                                                             \
     }
 #define TWIN_CASE(a, b, c, d_)                                                                                        \
     if (cl.la == a && cl.lb == b && cl.lc == c && cl.ld == d_) {                                                      \
         if (twin_wave && (a) <= 1 && (b) == 0 && (c) == 0 && (d_) == 0)                                               \
             launch_twin_wave(a, d + L.dense_off, L.dense_n, dense_stream());                                          \
+        else if (att)                                                                                                 \
+            launch_eri_twin_class<a, b, c, d_, true>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream()); \
         else                                                                                                          \
         launch_eri_twin_class<a, b, c, d_>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream());    \
+        if (att)                                                                                                      \
+            launch_eri_twin_class<a, b, c, d_, true>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, st.side[rr++ % ERI_SIDE_STREAMS]); \
+        else                                                                                                          \
         launch_eri_twin_class<a, b, c, d_>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, st.side[rr++ % ERI_SIDE_STREAMS]); \
     }
     // small batches: the twin (ss|ss) and (ps|ss) entries one wave per (entry, fragment) (eri_twin_wave_kernel)
     static const int twin_wave_max = [] { const char* e = std::getenv("MQC_HIP_TWIN_WAVE_MAX"); return e ? std::atoi(e) : ERI_TWIN_WAVE_MAX_FRAGMENTS; }();
     const bool twin_wave = bv.nfrag <= twin_wave_max;
     auto launch_twin_wave = [&](int la, const int* list, int nq, hipStream_t st_) {
-        if (la == 0) launch_eri_twin_wave_class<0, 0, 0, 0>(bv, list, nq, Q, thresh, st_);
+        if (att && la == 0) launch_eri_twin_wave_class<0, 0, 0, 0, true>(bv, list, nq, Q, thresh, st_);
+        else if (att) launch_eri_twin_wave_class<1, 0, 0, 0, true>(bv, list, nq, Q, thresh, st_);
+        else if (la == 0) launch_eri_twin_wave_class<0, 0, 0, 0>(bv, list, nq, Q, thresh, st_);
         else launch_eri_twin_wave_class<1, 0, 0, 0>(bv, list, nq, Q, thresh, st_);
     };
     // in spread mode the launches are issued heaviest first (stream order = issue order)
@@ -673,8 +696,8 @@ void launch_eri(const BatchView& bv, const Topology& topo, double schwarz_tol, h
         ERI_CASE(2, 2, 2, 2)
         if (general) {
             // a class with an f shell (or a d-heavy class routed here): the wave-cooperative LDS kernel
-            launch_eri_general(bv, cl.la, cl.lb, cl.lc, cl.ld, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream());
-            launch_eri_general(bv, cl.la, cl.lb, cl.lc, cl.ld, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, st.side[rr++ % ERI_SIDE_STREAMS]);
+            launch_eri_general(bv, cl.la, cl.lb, cl.lc, cl.ld, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream(), att);
+            launch_eri_general(bv, cl.la, cl.lb, cl.lc, cl.ld, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, st.side[rr++ % ERI_SIDE_STREAMS], att);
         }
     }
 #undef ERI_CASE

@@ -86,7 +86,8 @@ struct GenLayout {      // LDS offsets in doubles, computed by the host for the 
 
 }  // namespace
 
-enum { GEN_MODE_STORE = 0, GEN_MODE_SCHWARZ = 1, GEN_MODE_DIGEST = 2, GEN_MODE_DF3C = 3 };
+// GEN_MODE_STORE_ERF: GEN_MODE_STORE with erf(omega r12)/r12 (omega^2 = bv.omega2; md_integrals.hpp, ErfOp)
+enum { GEN_MODE_STORE = 0, GEN_MODE_SCHWARZ = 1, GEN_MODE_DIGEST = 2, GEN_MODE_DF3C = 3, GEN_MODE_STORE_ERF = 4 };
 
 // GEN_MODE_DF3C: the three-centre integrals of density fitting for orbital classes the register kernels of kern_df.hip
 // do not cover (an f shell in the bra): (ab|P) = (ab|P 1) with the "function" 1 as a one-primitive s shell of exponent 0
@@ -117,7 +118,7 @@ __global__ void __launch_bounds__(64) eri_general_kernel(BatchView bv, int la, i
     else { A = list[4 * iq]; B = list[4 * iq + 1]; C = list[4 * iq + 2]; D = list[4 * iq + 3]; }
     const TopologyDev& tp = bv.topo;
     const int ns = tp.nshell;
-    if (MODE == GEN_MODE_STORE && Q != nullptr) {
+    if ((MODE == GEN_MODE_STORE || MODE == GEN_MODE_STORE_ERF) && Q != nullptr) {
         const double* q = Q + (size_t)f * ns * ns;
         if (!(q[A * ns + B] * q[C * ns + D] >= thresh)) return;        // wave-uniform: the whole wave leaves
     }
@@ -201,8 +202,13 @@ __global__ void __launch_bounds__(64) eri_general_kernel(BatchView bv, int la, i
                         g_build_e(lc, ld, qc, qd, 0.5 * rq, Ecd + ax * ne_cd);
                     }
                     const double rs = 1.0 / sqrt(p + q);
-                    const double alpha = p * q * rs * rs;
-                    const double pref = TWO_PI_25 * rs * kab * kcd;
+                    double alpha = p * q * rs * rs;
+                    double pref = TWO_PI_25 * rs * kab * kcd;
+                    if constexpr (MODE == GEN_MODE_STORE_ERF) {
+                        const double r = 1.0 / (alpha + bv.omega2);
+                        pref *= sqrt(bv.omega2 * r);
+                        alpha *= bv.omega2 * r;
+                    }
                     const double X = px - qx, Y = py - qy, Z = pz - qz;
                     // Boys values F_n(T) (-2 alpha)^n into LDS: lane n takes order n (Taylor table), the asymptotic
                     // branch runs its upward recurrence on lane 0
@@ -449,14 +455,14 @@ static GenLayout gen_layout(int la, int lb, int lc, int ld)
 
 // Same contract as launch_eri_class<>: dense (entry x fragment) product or an explicit task list.
 bool launch_eri_general(const BatchView& bv, int la, int lb, int lc, int ld, const int* d_list, int nq,
-                        const int* d_tasks, int ntasks, const double* Q, double thresh, hipStream_t s)
+                        const int* d_tasks, int ntasks, const double* Q, double thresh, hipStream_t s, bool attenuated)
 {
     const long total = d_tasks ? (long)ntasks : (long)nq * bv.nfrag;
     if (nq == 0 || total == 0) return true;
     const GenLayout lay = gen_layout(la, lb, lc, ld);
     const size_t lds = sizeof(double) * (size_t)lay.total;
     if (lds > 160 * 1024 || total > 0x7fffffffL) return false;
-    auto kern = eri_general_kernel<GEN_MODE_STORE>;
+    auto kern = attenuated ? eri_general_kernel<GEN_MODE_STORE_ERF> : eri_general_kernel<GEN_MODE_STORE>;
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(64), lds, s, bv, la, lb, lc, ld, lay, d_list, nq, d_tasks, ntasks, Q, thresh,
                        (double*)nullptr, GenDigest{});

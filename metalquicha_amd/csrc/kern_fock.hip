@@ -798,6 +798,24 @@ static bool jk_rowcoop_on()
     return on;
 }
 
+// range-separated hybrids: K_eff = exx K + exx_lr K_lr, elementwise, fragments still iterating only
+__global__ void exchange_fold_kernel(BatchView bv, double* __restrict__ K, const double* __restrict__ Klr, double exx, double exx_lr)
+{
+    const int f = blockIdx.y;
+    if (bv.istate[4 * f] == ST_DONE) return;
+    const size_t nn = (size_t)bv.n * bv.n;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nn) return;
+    const size_t o = (size_t)f * nn + i;
+    K[o] = exx * K[o] + exx_lr * Klr[o];
+}
+
+void launch_exchange_fold(const BatchView& bv, double* K, const double* Klr, double exx, double exx_lr, hipStream_t s)
+{
+    const size_t nn = (size_t)bv.n * bv.n;
+    hipLaunchKernelGGL(exchange_fold_kernel, dim3((unsigned)((nn + 255) / 256), (unsigned)bv.nfrag), dim3(256), 0, s, bv, K, Klr, exx, exx_lr);
+}
+
 void launch_jk_incore(const BatchView& bv, bool only_active, hipStream_t s)
 {
     const int n = bv.n, np = bv.npair;

@@ -156,13 +156,29 @@ __device__ __forceinline__ Dual f_pbe_c(Dual rho, Dual r13, Dual sigma)
     return rho * (ec + H);
 }
 
+// wB97X's semi-local part at one point (defined with the spin-polarised forms below)
+__device__ __forceinline__ void wb97x_point(double ra, double rb, double saa, double sbb, double& f, double* dv);
+
 // f = rho * eps_xc per volume and its derivatives, zero below the density threshold; components k0, k0 + kstep, ...
 // (the tiled kernel deals the components of a functional to its waves: B3LYP's four run side by side)
+// RSH: the instantiation of the kernels that run wB97X (xc.omega > 0); the existing functionals' kernels are built with
+// RSH = false and never see its branch
+template <bool RSH = false>
 __device__ __forceinline__ void eval_functional(const XcSpec& xc, double rho, double sigma, double& f, double& vr, double& vs,
                                                 int k0 = 0, int kstep = 1)
 {
     f = 0.0; vr = 0.0; vs = 0.0;
     if (!(rho > XC_DENS_THRESHOLD) || k0 >= xc.ncomp) return;
+    if constexpr (RSH) {
+        // one component: the spin-polarised form at rho_s = rho/2, sigma_ss = sigma/4 (d/drho = mean of the two spin
+        // derivatives, d/dsigma = a quarter of the three sigma derivatives)
+        double d[5];
+        const double sq = 0.25 * fmax(sigma, 1.0e-40);
+        wb97x_point(0.5 * rho, 0.5 * rho, sq, sq, f, d);
+        vr = 0.5 * (d[0] + d[1]);
+        vs = 0.25 * (d[2] + d[3] + d[4]);
+        return;
+    }
     const Dual R = {rho, 1.0, 0.0};
     const Dual S_all = {fmax(sigma, 1.0e-40), 0.0, 1.0};
     const Dual R13_all = dcbrt(R);          // every component needs rho^(1/3): formed once
@@ -263,13 +279,79 @@ __device__ __forceinline__ D5 pw_mod_g5(D5 rs, D5 srs, double A, double a1, doub
 
 constexpr double XC_SPIN_FLOOR = 1.0e-30;        // a spin density below this is held there: zeta stays inside (-1, 1)
 
+// ------------------------------------------------------------------ wB97X (libxc gga_xc_wb97 with the wb97x parameters)
+// Chai & Head-Gordon 2008, per spin s with x_s^2 = sigma_ss / rho_s^(8/3) and g(x^2) = sum_i c_i u^i, u = gamma x^2/(1 + gamma x^2):
+//   e_x^LSDA(rho_s) F(a_s) g_x(x_s^2), a_s = omega / (2 k_Fs), k_Fs = (6 pi^2 rho_s)^(1/3)    short-range exchange
+//   rho_s eps_c^PW(rho_s, 0) g_ss(x_s^2)                                                    same-spin correlation
+//   [rho eps_c^PW(rho_a, rho_b) - (the two same-spin terms' local parts)] g_ab((x_a^2 + x_b^2)/2)
+// with PW92 in its ORIGINAL parameters (libxc lda_c_pw, not the pw_mod of PBE) and
+//   F(a) = 1 - 8/3 a [sqrt(pi) erf(1/(2a)) + (2a - 4a^3) exp(-1/(4a^2)) - 3a + 4a^3],
+// which cancels to O(1/a^2) for large a (low density): there, a >= 1, its series in b = 1/(2a), ten terms (the first
+// omitted one is below 1e-16 of the sum; tests/range_separated_reference.py checks both sides of the switch).
+constexpr double WB97X_OMEGA = 0.3;
+__device__ __forceinline__ D5 b97_g5(D5 x2, double gamma, double c0, double c1, double c2, double c3, double c4)
+{
+    const D5 u = gamma * x2 / (1.0 + gamma * x2);
+    return c0 + u * (c1 + u * (c2 + u * (c3 + u * c4)));
+}
+__device__ __forceinline__ D5 att_erf5(D5 a)
+{
+    if (a.v >= 1.0) {
+        const D5 b = 0.5 / a;
+        const D5 b2 = b * b;
+        const double dn[10] = {9.0, 60.0, 420.0, 3240.0, 27720.0, 262080.0, 2721600.0, 30844800.0, 379209600.0, 5029516800.0};
+        D5 acc = mk5(0.0);
+#pragma unroll
+        for (int k = 9; k >= 0; --k) acc = (((k & 1) ? -1.0 : 1.0) / dn[k]) * b2 + acc * b2;
+        return acc;
+    }
+    const D5 b = 0.5 / a;
+    const D5 erfb = chain5(b, erf(b.v), 1.1283791670955126 * exp(-b.v * b.v));
+    const D5 a3 = a * a * a;
+    return 1.0 - (8.0 / 3.0) * a * (1.7724538509055159 * erfb + (2.0 * a - 4.0 * a3) * exp5(-1.0 * (b * b)) - 3.0 * a + 4.0 * a3);
+}
+__device__ __forceinline__ void wb97x_point(double ra_in, double rb_in, double saa, double sbb, double& f, double* dv)
+{
+    const D5 r[2] = {var5(ra_in, 0), var5(rb_in, 1)};
+    const D5 sg[2] = {var5(saa, 2), var5(sbb, 4)};
+    D5 e = mk5(0.0), x2[2], ecs[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const D5 r13 = cbrt5(r[s]);
+        x2[s] = sg[s] / (r13 * r13 * r[s] * r[s]);
+        const D5 kf = 3.8977770897207535 * r13;                       // (6 pi^2)^(1/3) rho_s^(1/3)
+        const D5 ex = (-0.75 * 1.2407009817988) * (r13 * r[s]);      // -(3/4)(6/pi)^(1/3) rho_s^(4/3)
+        e = e + ex * att_erf5(WB97X_OMEGA / (2.0 * kf)) * b97_g5(x2[s], 0.004, 0.842294, 0.726479, 1.04760, -5.70635, 13.2794);
+        const D5 rs = 0.6203504908994001 / r13;
+        ecs[s] = r[s] * pw_mod_g5(rs, sqrt5(rs), 0.015545, 0.20548, 14.1189, 6.1977, 3.3662, 0.62517);   // fully polarised
+        e = e + ecs[s] * b97_g5(x2[s], 0.2, 1.0, -4.33879, 18.2308, -31.7430, 17.2901);
+    }
+    const D5 rho = r[0] + r[1];
+    const D5 z = (r[0] - r[1]) / rho;
+    const D5 rs = 0.6203504908994001 / cbrt5(rho), srs = sqrt5(rs);
+    const D5 g0 = pw_mod_g5(rs, srs, 0.031091, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294);
+    const D5 g1 = pw_mod_g5(rs, srs, 0.015545, 0.20548, 14.1189, 6.1977, 3.3662, 0.62517);
+    const D5 g2 = pw_mod_g5(rs, srs, 0.016887, 0.11125, 10.357, 3.6231, 0.88026, 0.49671);
+    const D5 fz = zeta_f5(cbrt5(1.0 + z), cbrt5(1.0 - z), z);
+    const D5 z4 = (z * z) * (z * z);
+    const D5 ec = g0 - g2 * fz * (1.0 - z4) * (1.0 / 1.709921) + (g1 - g0) * fz * z4;
+    e = e + (rho * ec - ecs[0] - ecs[1]) * b97_g5(0.5 * (x2[0] + x2[1]), 0.006, 1.0, 2.37031, -11.3995, 6.58405, -3.78132);
+    f = e.v;
+    for (int i = 0; i < 5; ++i) dv[i] = e.d[i];
+}
+
 // f per volume and its five derivatives; zero where the TOTAL density is below the threshold
+template <bool RSH = false>
 __device__ __forceinline__ void eval_functional_pol(const XcSpec& xc, double ra_in, double rb_in, double saa, double sab, double sbb,
                                                     double& f, double* dv)
 {
     f = 0.0;
     for (int i = 0; i < 5; ++i) dv[i] = 0.0;
     if (!(ra_in + rb_in > XC_DENS_THRESHOLD)) return;
+    if constexpr (RSH) {
+        wb97x_point(fmax(ra_in, XC_SPIN_FLOOR), fmax(rb_in, XC_SPIN_FLOOR), fmax(saa, 1.0e-40), fmax(sbb, 1.0e-40), f, dv);
+        return;
+    }
     const D5 ra_all = var5(fmax(ra_in, XC_SPIN_FLOOR), 0), rb_all = var5(fmax(rb_in, XC_SPIN_FLOOR), 1);
     const D5 Saa = var5(fmax(saa, 1.0e-40), 2), Sab = var5(sab, 3), Sbb = var5(fmax(sbb, 1.0e-40), 4);
     const D5 rho_all = ra_all + rb_all;
@@ -885,7 +967,7 @@ __device__ unsigned long long g_xc_stamps[16];
 #define XC_ST(k)
 #endif
 
-template <bool GGA, int PT, int JMAX, int OCC, bool DREG, int NTC, bool FAST = false, int NWV = XV_NW>
+template <bool GGA, int PT, int JMAX, int OCC, bool DREG, int NTC, bool FAST = false, int NWV = XV_NW, bool RSH = false>
 __global__ void __launch_bounds__(64 * NWV, OCC) xc_tile_kernel(BatchView bv, int only_active)
 {
     // One tile = PT points: AO slab -> X = D chi, rho / grad rho -> functional (one lane per point) -> a -> A += a chi^T.
@@ -1125,7 +1207,7 @@ __global__ void __launch_bounds__(64 * NWV, OCC) xc_tile_kernel(BatchView bv, in
                 const double sigma = GGA ? rx * rx + ry * ry + rz * rz : 0.0;
                 double fx, vr, vs;
                 if (probe & 4) { fx = -rho; vr = -1.0; vs = 0.0; }
-                else eval_functional(bv.xc, rho, sigma, fx, vr, vs);
+                else eval_functional<RSH>(bv.xc, rho, sigma, fx, vr, vs);
                 const double w = (s0 + p < gd.npts) ? wts[s0 + p] : 0.0;
                 e_acc += w * fx;
                 n_acc += w * rho;
@@ -1206,7 +1288,7 @@ __global__ void __launch_bounds__(64 * NWV, OCC) xc_tile_kernel(BatchView bv, in
     }
 }
 
-template <bool GGA, int PT, int JMAX, int OCC, bool DREG, int NTC, int NWV = XV_NW>
+template <bool GGA, int PT, int JMAX, int OCC, bool DREG, int NTC, int NWV = XV_NW, bool RSH = false>
 static void xc_tile_launch(const BatchView& bv, int oa, hipStream_t s)
 {
     const int np = ((bv.n + 15) / 16) * 16;
@@ -1222,10 +1304,10 @@ static void xc_tile_launch(const BatchView& bv, int oa, hipStream_t s)
         lds += rad_lds;
         oa |= 2;
     }
-    auto kern = xc_tile_kernel<GGA, PT, JMAX, OCC, DREG, NTC, false, NWV>;
+    auto kern = xc_tile_kernel<GGA, PT, JMAX, OCC, DREG, NTC, false, NWV, RSH>;
     if constexpr (DREG) {
         static const bool fast_on = [] { const char* e = std::getenv("MQC_HIP_XC_FAST_SLAB"); return !(e && e[0] == '0'); }();
-        if (fast_on && (oa & 2) && bv.topo.lmax <= 2) kern = xc_tile_kernel<GGA, PT, JMAX, OCC, DREG, NTC, true, NWV>;
+        if (fast_on && (oa & 2) && bv.topo.lmax <= 2) kern = xc_tile_kernel<GGA, PT, JMAX, OCC, DREG, NTC, true, NWV, RSH>;
     }
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const int tile_pts = PT;
@@ -1244,6 +1326,16 @@ static bool xc_tile_dispatch(const BatchView& bv, int oa, hipStream_t s)
     // 32-point tiles at two workgroups (eight waves) per CU: 256 registers, no scratch.  (A 168-register build for
     // three waves per SIMD spilled ~300 B per lane in the functional and measured slower; removed.)
     const int nt = (bv.n + 15) / 16, jobs = (nt * nt + XV_NW - 1) / XV_NW;
+    if constexpr (GGA) {
+        if (bv.xc.omega > 0.0) {
+            // wB97X (restricted fragments the split quadrature does not take): the 16-point tile family only
+            if (jobs <= 9) xc_tile_launch<GGA, 16, 9, 1, false, 0, XV_NW, true>(bv, oa, s);
+            else if (jobs <= 16) xc_tile_launch<GGA, 16, 16, 1, false, 0, XV_NW, true>(bv, oa, s);
+            else if (jobs <= 21) xc_tile_launch<GGA, 16, 21, 1, false, 0, XV_NW, true>(bv, oa, s);
+            else return false;
+            return true;
+        }
+    }
     if (nt <= 4) {                       // n <= 64
         if (nt == 1) xc_tile_launch<GGA, 32, 1, 2, true, 1>(bv, oa, s);
         else if (nt == 2) xc_tile_launch<GGA, 32, 1, 2, true, 2>(bv, oa, s);
@@ -1886,7 +1978,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (NTC >= 4 ? 2 : 3)) xc_
     }
 }
 
-template <bool GGA>
+template <bool GGA, bool RSH = false>
 __global__ void __launch_bounds__(256) xc_functional_kernel(BatchView bv, int only_active)
 {
     const int f = blockIdx.y;
@@ -1902,7 +1994,7 @@ __global__ void __launch_bounds__(256) xc_functional_kernel(BatchView bv, int on
         const double w = p < gd.npts ? wts[p] : 0.0;
         const double sigma = GGA ? rx * rx + ry * ry + rz * rz : 0.0;
         double fx, vr, vs;
-        eval_functional(bv.xc, rho, sigma, fx, vr, vs);
+        eval_functional<RSH>(bv.xc, rho, sigma, fx, vr, vs);
         e_acc += w * fx; n_acc += w * rho;
         const double t2 = 2.0 * w * vs;
         *(double2*)(v4 + 4 * (size_t)p) = make_double2(0.5 * w * vr, t2 * rx);
@@ -2080,7 +2172,9 @@ static bool xc_split_launch(const BatchView& bv, int oa, hipStream_t s)
     int g2 = (npad + 255) / 256;
     if (g2 > 64) g2 = 64;
     hipLaunchKernelGGL(k1, dim3(g1, bv.nfrag), dim3(NTHR), lds1, s, bv, oa);
-    hipLaunchKernelGGL(xc_functional_kernel<GGA>, dim3(g2, bv.nfrag), dim3(256), 0, s, bv, oa);
+    auto kf = xc_functional_kernel<GGA>;
+    if constexpr (GGA) { if (bv.xc.omega > 0.0) kf = xc_functional_kernel<GGA, true>; }
+    hipLaunchKernelGGL(kf, dim3(g2, bv.nfrag), dim3(256), 0, s, bv, oa);
     hipLaunchKernelGGL(k3, dim3(g3, bv.nfrag), dim3(NTHR), lds3, s, bv, oa);
     return true;
 }
@@ -2111,7 +2205,7 @@ __global__ void xc_reset_kernel(BatchView bv)
     if (f < bv.nfrag) { bv.scal[(size_t)f * 8 + 5] = 0.0; bv.scal[(size_t)f * 8 + 6] = 0.0; }
 }
 
-template <bool GGA, int PT, int NV>
+template <bool GGA, int PT, int NV, bool RSH = false>
 __global__ void __launch_bounds__(XC_NT) xc_uks_kernel(BatchView bv, int flags)
 {
     extern __shared__ double lds[];
@@ -2184,7 +2278,7 @@ __global__ void __launch_bounds__(XC_NT) xc_uks_kernel(BatchView bv, int flags)
             const double sab = ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2];
             const double sbb = gb[0] * gb[0] + gb[1] * gb[1] + gb[2] * gb[2];
             double fx, dv[5];
-            eval_functional_pol(bv.xc, ra, rb, saa, sab, sbb, fx, dv);
+            eval_functional_pol<RSH>(bv.xc, ra, rb, saa, sab, sbb, fx, dv);
             const double w = pw[p];
             e_acc += w * fx;
             n_acc += w * (ra + rb);
@@ -2239,6 +2333,7 @@ static void xc_uks_launch(const BatchView& bv, int oa, hipStream_t s)
     const int n = bv.n;
     const size_t lds = sizeof(double) * ((size_t)(GGA ? 7 : 4) * n * (PT + 1) + 5 * PT + 16);
     auto kern = xc_uks_kernel<GGA, PT, NV>;
+    if constexpr (GGA) { if (bv.xc.omega > 0.0) kern = xc_uks_kernel<GGA, PT, NV, true>; }
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const int ntiles = (bv.grid.npts + PT - 1) / PT;
     int gx = (8192 + bv.nfrag - 1) / bv.nfrag;

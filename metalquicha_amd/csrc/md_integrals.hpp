@@ -178,6 +178,30 @@ MQC_HD void hermite_r(double alpha, double X, double Y, double Z, const double* 
 }
 
 // ---------------------------------------------------------------------------------------
+// Two-electron operator of an ERI block: 1/r12 (CoulombOp, every existing instantiation) or erf(omega r12)/r12 (ErfOp,
+// the long-range exchange of range-separated hybrids).  The Hermite expansion of a primitive quartet is the same for
+// both; only R_tuv changes: alpha = pq/(p+q) becomes alpha_w = alpha w^2/(alpha + w^2) (Boys argument and the
+// (-2 alpha)^n factors) and the prefactor gains sqrt(alpha_w/alpha) = w/sqrt(alpha + w^2).
+struct CoulombOp {
+    static constexpr bool attenuated = false;
+};
+struct ErfOp {
+    static constexpr bool attenuated = true;
+    double omega2;
+};
+template <int L, class Op>
+MQC_HD void hermite_r_op(const Op& op, double alpha, double X, double Y, double Z, const double* __restrict__ table, double* R,
+                         double scale = 1.0)
+{
+    if constexpr (Op::attenuated) {
+        const double r = 1.0 / (alpha + op.omega2);
+        hermite_r<L>(alpha * op.omega2 * r, X, Y, Z, table, R, scale * sqrt(op.omega2 * r));
+    } else {
+        hermite_r<L>(alpha, X, Y, Z, table, R, scale);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // 1-D Hermite expansion coefficients with E^{00}_0 = 1 (the Gaussian product factor is kept
 // as a scalar by the caller).  E[(i*(LB+1)+j)*(LA+LB+1)+t]
 template <int LA, int LB>
@@ -466,9 +490,9 @@ MQC_HD void bra_from_hermite(const E1D<LA, LB>& ex, const E1D<LA, LB>& ey, const
 // ---------------------------------------------------------------------------------------
 // Contracted Cartesian ERI block (ab|cd), out[((ia*NCB+ib)*NCC+ic)*NCD+id] (accumulated
 // into a zeroed buffer by this routine).
-template <int LA, int LB, int LC, int LD, class Bra, class Ket, class Twin = NoTwin>
+template <int LA, int LB, int LC, int LD, class Bra, class Ket, class Twin = NoTwin, class Op = CoulombOp>
 MQC_HD void eri_cart_block_src(const Bra& bra, const Ket& ket, const double* __restrict__ boys_table, double* out,
-                               const Twin& tw = Twin(), int bra_first = 0, int bra_step = 0)
+                               const Twin& tw = Twin(), int bra_first = 0, int bra_step = 0, const Op& op = Op())
 {
     constexpr int NCA = ncart(LA), NCB = ncart(LB), NCC = ncart(LC), NCD = ncart(LD);
     constexpr int LAB = LA + LB, LCD = LC + LD, L = LAB + LCD;
@@ -501,7 +525,7 @@ MQC_HD void eri_cart_block_src(const Bra& bra, const Ket& ket, const double* __r
             const double alpha = p * q * rpq;
             const double pref = TWO_PI_25 * rs * P.kp * Qp.kp;
             double R[nherm(L)];
-            hermite_r<L>(alpha, px - qx, py - qy, pz - qz, boys_table, R);
+            hermite_r_op<L>(op, alpha, px - qx, py - qy, pz - qz, boys_table, R);
 
             if constexpr (UNROLLED) {
                 // loop over ket components; for each, G[h] over bra Hermite indices
@@ -672,7 +696,7 @@ MQC_HD void eri_cart_block_src(const Bra& bra, const Ket& ket, const double* __r
                     const double rs = fast_rsqrt(Pb[t].p + Qp.p);
                     const double alpha = Pb[t].p * Qp.p * rs * rs;
                     double R[nherm(L)];
-                    hermite_r<L>(alpha, Pb[t].px - Qp.px, Pb[t].py - Qp.py, Pb[t].pz - Qp.pz, boys_table, R, kq * rs);
+                    hermite_r_op<L>(op, alpha, Pb[t].px - Qp.px, Pb[t].py - Qp.py, Pb[t].pz - Qp.pz, boys_table, R, kq * rs);
                     ket_into_hermite<LAB, LC, LD>(fx, fy, fz, R, H[t]);
                 }
             }
@@ -721,7 +745,7 @@ MQC_HD void eri_cart_block_src(const Bra& bra, const Ket& ket, const double* __r
                 const double rs = fast_rsqrt(P.p + Qp.p);
                 const double alpha = P.p * Qp.p * rs * rs;
                 double R[nherm(L)];
-                hermite_r<L>(alpha, P.px - Qp.px, P.py - Qp.py, P.pz - Qp.pz, boys_table, R, TWO_PI_25 * Qp.kp * rs);
+                hermite_r_op<L>(op, alpha, P.px - Qp.px, P.py - Qp.py, P.pz - Qp.pz, boys_table, R, TWO_PI_25 * Qp.kp * rs);
                 double G[NK * NHAB];
 #pragma unroll
                 for (int h = 0; h < NK * NHAB; ++h) G[h] = 0.0;
@@ -876,12 +900,13 @@ constexpr int eri_twin_combos(int la, int lb, int lc, int ld)
 {
     return twin_mult(true, la) * twin_mult(true, lb) * twin_mult(true, lc) * twin_mult(true, ld);
 }
-template <int LA, int LB, int LC, int LD>
+template <int LA, int LB, int LC, int LD, class Op = CoulombOp>
 MQC_HD void eri_cart_block_twin(const ShellRef& A, const ShellRef& B, const ShellRef& C, const ShellRef& D, const TwinCoefs& tw,
-                                const double* __restrict__ boys_table, double* out, int bra_first = 0, int bra_step = 0)
+                                const double* __restrict__ boys_table, double* out, int bra_first = 0, int bra_step = 0,
+                                const Op& op = Op())
 {
     const PairFlyRaw bra(A, B), ket(C, D);
-    eri_cart_block_src<LA, LB, LC, LD, PairFlyRaw, PairFlyRaw, TwinCoefs>(bra, ket, boys_table, out, tw, bra_first, bra_step);
+    eri_cart_block_src<LA, LB, LC, LD, PairFlyRaw, PairFlyRaw, TwinCoefs, Op>(bra, ket, boys_table, out, tw, bra_first, bra_step, op);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -898,10 +923,10 @@ MQC_HD void eri_cart_block_twin(const ShellRef& A, const ShellRef& B, const Shel
 //     `sink(i, j, k, l, value)` (spherical indices inside the shell block).
 // Each pass recomputes the Hermite tables and R_tuv for its primitive quartets: more arithmetic,
 // no scratch memory -- which is what the profile said these classes were waiting on.
-template <int LA, int LB, int LC, int LD, int CH, int PASS, class Bra, class Ket, class Sink>
+template <int LA, int LB, int LC, int LD, int CH, int PASS, class Bra, class Ket, class Sink, class Op = CoulombOp>
 MQC_HD void eri_pass(const Bra& bra, const Ket& ket,
                      const double* __restrict__ boys_table, const double* __restrict__ c2s,
-                     double* __restrict__ acc, int stride, Sink& sink)
+                     double* __restrict__ acc, int stride, Sink& sink, const Op& op = Op())
 {
     constexpr int NCA = ncart(LA), NCB = ncart(LB), NCC = ncart(LC), NCD = ncart(LD);
     constexpr int NSA = nsph(LA), NSB = nsph(LB), NSC = nsph(LC), NSD = nsph(LD);
@@ -944,7 +969,7 @@ MQC_HD void eri_pass(const Bra& bra, const Ket& ket,
                     const double rs = fast_rsqrt(P.p + Qp.p);
                     const double alpha = P.p * Qp.p * rs * rs;
                     double R[nherm(L)];
-                    hermite_r<L>(alpha, P.px - Qp.px, P.py - Qp.py, P.pz - Qp.pz, boys_table, R, TWO_PI_25 * rs * Qp.kp);
+                    hermite_r_op<L>(op, alpha, P.px - Qp.px, P.py - Qp.py, P.pz - Qp.pz, boys_table, R, TWO_PI_25 * rs * Qp.kp);
 #pragma unroll
                     for (int s = S0; s < S1; ++s) {
                         const int mc = s / NSD, md = s - mc * NSD;
@@ -1017,7 +1042,7 @@ MQC_HD void eri_pass(const Bra& bra, const Ket& ket,
                     const double alpha = p * q * rpq;
                     const double pref = TWO_PI_25 * rs * P.kp * Qp.kp;
                     double R[nherm(L)];
-                    hermite_r<L>(alpha, px - qx, py - qy, pz - qz, boys_table, R);
+                    hermite_r_op<L>(op, alpha, px - qx, py - qy, pz - qz, boys_table, R);
 #pragma unroll
                     for (int s = S0; s < S1; ++s) {
                         const int mc = s / NSD, md = s - mc * NSD;
@@ -1107,23 +1132,23 @@ MQC_HD void eri_pass(const Bra& bra, const Ket& ket,
     }
 }
 
-template <int LA, int LB, int LC, int LD, int CH, int PASS, class Bra, class Ket, class Sink>
+template <int LA, int LB, int LC, int LD, int CH, int PASS, class Bra, class Ket, class Sink, class Op = CoulombOp>
 MQC_HD void eri_passes_src(const Bra& bra, const Ket& ket,
                            const double* __restrict__ boys_table, const double* __restrict__ c2s,
-                           double* __restrict__ acc, int stride, Sink& sink)
+                           double* __restrict__ acc, int stride, Sink& sink, const Op& op = Op())
 {
     constexpr int NPASS = (nsph(LC) * nsph(LD) + CH - 1) / CH;
-    eri_pass<LA, LB, LC, LD, CH, PASS>(bra, ket, boys_table, c2s, acc, stride, sink);
-    if constexpr (PASS + 1 < NPASS) eri_passes_src<LA, LB, LC, LD, CH, PASS + 1>(bra, ket, boys_table, c2s, acc, stride, sink);
+    eri_pass<LA, LB, LC, LD, CH, PASS>(bra, ket, boys_table, c2s, acc, stride, sink, op);
+    if constexpr (PASS + 1 < NPASS) eri_passes_src<LA, LB, LC, LD, CH, PASS + 1>(bra, ket, boys_table, c2s, acc, stride, sink, op);
 }
 
-template <int LA, int LB, int LC, int LD, int CH, int PASS, class Sink>
+template <int LA, int LB, int LC, int LD, int CH, int PASS, class Sink, class Op = CoulombOp>
 MQC_HD void eri_passes_from(const ShellRef& A, const ShellRef& B, const ShellRef& C, const ShellRef& D,
                             const double* __restrict__ boys_table, const double* __restrict__ c2s,
-                            double* __restrict__ acc, int stride, Sink& sink)
+                            double* __restrict__ acc, int stride, Sink& sink, const Op& op = Op())
 {
     const PairFly bra(A, B), ket(C, D);
-    eri_passes_src<LA, LB, LC, LD, CH, PASS>(bra, ket, boys_table, c2s, acc, stride, sink);
+    eri_passes_src<LA, LB, LC, LD, CH, PASS>(bra, ket, boys_table, c2s, acc, stride, sink, op);
 }
 
 // ket components per pass: as many as keep the accumulator slab at or under 64 entries per lane
