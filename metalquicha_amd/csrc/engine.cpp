@@ -272,10 +272,13 @@ static int validate_options(const mqc_hip_scf_options_t& o, const Topology& topo
         if (tmp.ncomp > 0 && topo.natoms > 64) { msg = "XC grid: fragments above 64 atoms are not supported yet"; return MQC_HIP_ERR_UNSUPPORTED; }
         if (tmp.omega > 0.0) {
             // range-separated hybrids need K_lr from a second in-core tensor of erf(omega r12)/r12: nothing else forms it
-            if (o.density_fitting) { msg = "range-separated functionals (wb97x) need exact long-range exchange K_lr: density fitting with erf-attenuated fits is not built; use exact in-core ERIs"; return MQC_HIP_ERR_UNSUPPORTED; }
-            if (o.eri_mode == MQC_HIP_ERI_DIRECT) { msg = "range-separated functionals (wb97x) run on the in-core exact-ERI path only: the direct path forms no long-range exchange K_lr"; return MQC_HIP_ERR_UNSUPPORTED; }
-            if (!incore_supported(topo.nao) || topo.nao > 116) { msg = "range-separated functionals (wb97x) run on the in-core exact-ERI path only (n_ao <= 116); larger fragments would need a direct K_lr, which is not built"; return MQC_HIP_ERR_UNSUPPORTED; }
-            if (o.want_gradient) { msg = "analytic gradients of range-separated functionals (wb97x) are not built (energies only)"; return MQC_HIP_ERR_UNSUPPORTED; }
+            std::string fn(o.functional);
+            std::transform(fn.begin(), fn.end(), fn.begin(), [](unsigned char c) { return (char)std::tolower(c); });
+            const std::string rs = "range-separated functionals (" + fn + ")";
+            if (o.density_fitting) { msg = rs + " need exact long-range exchange K_lr: density fitting with erf-attenuated fits is not built; use exact in-core ERIs"; return MQC_HIP_ERR_UNSUPPORTED; }
+            if (o.eri_mode == MQC_HIP_ERI_DIRECT) { msg = rs + " run on the in-core exact-ERI path only: the direct path forms no long-range exchange K_lr"; return MQC_HIP_ERR_UNSUPPORTED; }
+            if (!incore_supported(topo.nao) || topo.nao > 116) { msg = rs + " run on the in-core exact-ERI path only (n_ao <= 116); larger fragments would need a direct K_lr, which is not built"; return MQC_HIP_ERR_UNSUPPORTED; }
+            if (o.want_gradient) { msg = "analytic gradients of " + rs + " are not built (energies only)"; return MQC_HIP_ERR_UNSUPPORTED; }
         }
     }
     if (o.want_gradient) {

@@ -82,8 +82,10 @@ private:
 
 // exchange-correlation components (libxc-equivalent ids, unpolarised)
 // XC_HYB_GGA_XC_WB97X: the whole semi-local part of wB97X as one component (kern_xc.hip, wb97x_point)
+// XC_GGA_X_ITYH: B88 exchange attenuated by erf(omega r12) in libxc's ITYH form, omega = XcSpec.omega (CAM-B3LYP;
+// kern_xc.hip, ityh_spin)
 enum : int { XC_LDA_X = 1, XC_LDA_C_VWN, XC_LDA_C_VWN_RPA, XC_GGA_X_B88, XC_GGA_C_LYP, XC_GGA_X_PBE, XC_GGA_C_PBE, XC_MGGA_X_TPSS, XC_MGGA_C_TPSS,
-             XC_HYB_GGA_XC_WB97X };
+             XC_HYB_GGA_XC_WB97X, XC_GGA_X_ITYH };
 struct XcSpec {
     int ncomp = 0;
     int id[6] = {0, 0, 0, 0, 0, 0};

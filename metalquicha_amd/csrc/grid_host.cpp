@@ -123,7 +123,14 @@ bool parse_functional(const char* name_in, XcSpec& spec, std::string& err)
         add(XC_HYB_GGA_XC_WB97X, 1.0);
         spec.exx = 0.157706; spec.exx_lr = 0.842294; spec.omega = 0.3; spec.gga = 1;
     }
-    else { err = "functional '" + n + "' is not available on the HIP backend (svwn, pbe, blyp, b3lyp, pbe0, tpss, wb97x)"; return false; }
+    else if (n == "cam-b3lyp" || n == "camb3lyp") {
+        // libxc hyb_gga_xc_cam_b3lyp: cam_alpha = 0.65, cam_beta = -0.46, omega = 0.33, ac = 0.81, VWN5 (not B3LYP's
+        // VWN-RPA); B88 at 1 - alpha = 0.35 plus ITYH-attenuated B88 at -beta = 0.46, exact exchange alpha + beta = 0.19
+        // at all ranges plus 0.46 more at long range
+        add(XC_GGA_X_B88, 0.35); add(XC_GGA_X_ITYH, 0.46); add(XC_LDA_C_VWN, 0.19); add(XC_GGA_C_LYP, 0.81);
+        spec.exx = 0.19; spec.exx_lr = 0.46; spec.omega = 0.33; spec.gga = 1;
+    }
+    else { err = "functional '" + n + "' is not available on the HIP backend (svwn, pbe, blyp, b3lyp, pbe0, tpss, wb97x, cam-b3lyp)"; return false; }
     return true;
 }
 

@@ -156,13 +156,16 @@ __device__ __forceinline__ Dual f_pbe_c(Dual rho, Dual r13, Dual sigma)
     return rho * (ec + H);
 }
 
-// wB97X's semi-local part at one point (defined with the spin-polarised forms below)
+// wB97X's semi-local part at one point, and one spin's ITYH exchange (value, d/drho_s, d/dsigma_ss) -- both defined with
+// the spin-polarised forms below
 __device__ __forceinline__ void wb97x_point(double ra, double rb, double saa, double sbb, double& f, double* dv);
+__device__ __forceinline__ void ityh_spin(double rs, double ss, double omega, double& e, double& er, double& es);
 
 // f = rho * eps_xc per volume and its derivatives, zero below the density threshold; components k0, k0 + kstep, ...
 // (the tiled kernel deals the components of a functional to its waves: B3LYP's four run side by side)
-// RSH: the instantiation of the kernels that run wB97X (xc.omega > 0); the existing functionals' kernels are built with
-// RSH = false and never see its branch
+// RSH: the instantiation of the kernels that run range-separated hybrids (xc.omega > 0); the existing functionals'
+// kernels are built with RSH = false and never see its branches.  wB97X is one component, evaluated whole on k0 == 0;
+// any other RSH functional (CAM-B3LYP) is the weighted component sum below, in which only ITYH is new.
 template <bool RSH = false>
 __device__ __forceinline__ void eval_functional(const XcSpec& xc, double rho, double sigma, double& f, double& vr, double& vs,
                                                 int k0 = 0, int kstep = 1)
@@ -170,19 +173,31 @@ __device__ __forceinline__ void eval_functional(const XcSpec& xc, double rho, do
     f = 0.0; vr = 0.0; vs = 0.0;
     if (!(rho > XC_DENS_THRESHOLD) || k0 >= xc.ncomp) return;
     if constexpr (RSH) {
-        // one component: the spin-polarised form at rho_s = rho/2, sigma_ss = sigma/4 (d/drho = mean of the two spin
-        // derivatives, d/dsigma = a quarter of the three sigma derivatives)
-        double d[5];
-        const double sq = 0.25 * fmax(sigma, 1.0e-40);
-        wb97x_point(0.5 * rho, 0.5 * rho, sq, sq, f, d);
-        vr = 0.5 * (d[0] + d[1]);
-        vs = 0.25 * (d[2] + d[3] + d[4]);
-        return;
+        if (xc.id[0] == XC_HYB_GGA_XC_WB97X) {
+            // one component: the spin-polarised form at rho_s = rho/2, sigma_ss = sigma/4 (d/drho = mean of the two spin
+            // derivatives, d/dsigma = a quarter of the three sigma derivatives)
+            double d[5];
+            const double sq = 0.25 * fmax(sigma, 1.0e-40);
+            wb97x_point(0.5 * rho, 0.5 * rho, sq, sq, f, d);
+            vr = 0.5 * (d[0] + d[1]);
+            vs = 0.25 * (d[2] + d[3] + d[4]);
+            return;
+        }
     }
     const Dual R = {rho, 1.0, 0.0};
     const Dual S_all = {fmax(sigma, 1.0e-40), 0.0, 1.0};
     const Dual R13_all = dcbrt(R);          // every component needs rho^(1/3): formed once
     for (int k = k0; k < xc.ncomp; k += kstep) {
+        if constexpr (RSH) {
+            if (xc.id[k] == XC_GGA_X_ITYH) {
+                // the spin form at rho_s = rho/2, sigma_ss = sigma/4, both spins alike: f = 2 e, d/drho = de/drho_s,
+                // d/dsigma = de/dsigma_ss / 2
+                double e, er, es;
+                ityh_spin(0.5 * rho, 0.25 * S_all.v, xc.omega, e, er, es);
+                f += xc.w[k] * (2.0 * e); vr += xc.w[k] * er; vs += xc.w[k] * (0.5 * es);
+                continue;
+            }
+        }
         Dual d;
         // The cases are pure functions of loop invariants: left alone, the compiler hoists ALL SEVEN functionals out of the
         // loop (speculative execution) and the loop only selects among the results -- every tile paid for PBE, VWN5 and
@@ -310,6 +325,25 @@ __device__ __forceinline__ D5 att_erf5(D5 a)
     const D5 a3 = a * a * a;
     return 1.0 - (8.0 / 3.0) * a * (1.7724538509055159 * erfb + (2.0 * a - 4.0 * a3) * exp5(-1.0 * (b * b)) - 3.0 * a + 4.0 * a3);
 }
+// ------------------------------------------------------------------ ITYH (libxc gga_x_ityh with B88's enhancement factor)
+// Iikura, Tsuneda, Yanai & Hirao 2001, the short-range part of CAM-B3LYP's B88, per spin s with x_s = sqrt(sigma_ss) /
+// rho_s^(4/3):
+//   e_s = -C_x rho_s^(4/3) F(x_s) F_att(a_s),  F(x) = 1 + (beta / C_x) x^2 / (1 + 6 beta x asinh x),  beta = 0.0042,
+//   a_s = omega sqrt(F(x_s)) / (2 k_Fs),  k_Fs = (6 pi^2 rho_s)^(1/3)    (k_GGA = k_Fs / sqrt(F)),
+// C_x = (3/4)(6/pi)^(1/3), and F_att the attenuation function of wB97X (att_erf5, its series for a >= 1).
+__device__ __forceinline__ void ityh_spin(double rs_in, double ss_in, double omega, double& e, double& er, double& es)
+{
+    const double beta = 0.0042, cx = 0.9305257363491;                // (3/4)(6/pi)^(1/3)
+    const D5 r = var5(rs_in, 0), s = var5(ss_in, 2);
+    const D5 r13 = cbrt5(r);
+    const D5 r43 = r * r13;
+    const D5 x = sqrt5(s) / r43;
+    const D5 fx = 1.0 + (beta / cx) * x * x / (1.0 + 6.0 * beta * x * asinh5(x));
+    const D5 kf = 3.8977770897207535 * r13;                           // (6 pi^2)^(1/3) rho_s^(1/3)
+    const D5 v = (-cx) * r43 * fx * att_erf5(omega * sqrt5(fx) / (2.0 * kf));
+    e = v.v; er = v.d[0]; es = v.d[2];
+}
+
 __device__ __forceinline__ void wb97x_point(double ra_in, double rb_in, double saa, double sbb, double& f, double* dv)
 {
     const D5 r[2] = {var5(ra_in, 0), var5(rb_in, 1)};
@@ -349,8 +383,10 @@ __device__ __forceinline__ void eval_functional_pol(const XcSpec& xc, double ra_
     for (int i = 0; i < 5; ++i) dv[i] = 0.0;
     if (!(ra_in + rb_in > XC_DENS_THRESHOLD)) return;
     if constexpr (RSH) {
-        wb97x_point(fmax(ra_in, XC_SPIN_FLOOR), fmax(rb_in, XC_SPIN_FLOOR), fmax(saa, 1.0e-40), fmax(sbb, 1.0e-40), f, dv);
-        return;
+        if (xc.id[0] == XC_HYB_GGA_XC_WB97X) {
+            wb97x_point(fmax(ra_in, XC_SPIN_FLOOR), fmax(rb_in, XC_SPIN_FLOOR), fmax(saa, 1.0e-40), fmax(sbb, 1.0e-40), f, dv);
+            return;
+        }
     }
     const D5 ra_all = var5(fmax(ra_in, XC_SPIN_FLOOR), 0), rb_all = var5(fmax(rb_in, XC_SPIN_FLOOR), 1);
     const D5 Saa = var5(fmax(saa, 1.0e-40), 2), Sab = var5(sab, 3), Sbb = var5(fmax(sbb, 1.0e-40), 4);
@@ -361,6 +397,16 @@ __device__ __forceinline__ void eval_functional_pol(const XcSpec& xc, double ra_
     const D5 rs_all = 0.6203504908994001 / r13_all;
     const D5 sig_all = Saa + 2.0 * Sab + Sbb;
     for (int k = 0; k < xc.ncomp; ++k) {
+        if constexpr (RSH) {
+            if (xc.id[k] == XC_GGA_X_ITYH) {       // one spin each: sigma_ab does not enter
+                double ea, ea_r, ea_s, eb, eb_r, eb_s;
+                ityh_spin(ra_all.v, Saa.v, xc.omega, ea, ea_r, ea_s);
+                ityh_spin(rb_all.v, Sbb.v, xc.omega, eb, eb_r, eb_s);
+                f += xc.w[k] * (ea + eb);
+                dv[0] += xc.w[k] * ea_r; dv[1] += xc.w[k] * eb_r; dv[2] += xc.w[k] * ea_s; dv[4] += xc.w[k] * eb_s;
+                continue;
+            }
+        }
         D5 d;
         // opaque per iteration, so that the cases stay behind their branch instead of being hoisted out of the loop
         // all seven at once (see eval_functional)
@@ -1328,7 +1374,8 @@ static bool xc_tile_dispatch(const BatchView& bv, int oa, hipStream_t s)
     const int nt = (bv.n + 15) / 16, jobs = (nt * nt + XV_NW - 1) / XV_NW;
     if constexpr (GGA) {
         if (bv.xc.omega > 0.0) {
-            // wB97X (restricted fragments the split quadrature does not take): the 16-point tile family only
+            // range-separated hybrids (restricted fragments the split quadrature does not take): the 16-point tile
+            // family only
             if (jobs <= 9) xc_tile_launch<GGA, 16, 9, 1, false, 0, XV_NW, true>(bv, oa, s);
             else if (jobs <= 16) xc_tile_launch<GGA, 16, 16, 1, false, 0, XV_NW, true>(bv, oa, s);
             else if (jobs <= 21) xc_tile_launch<GGA, 16, 21, 1, false, 0, XV_NW, true>(bv, oa, s);
@@ -1720,6 +1767,8 @@ static bool xc_pipe_dispatch(const BatchView& bv, int oa, hipStream_t s)
 {
     static const bool on = [] { const char* e = std::getenv("MQC_HIP_XC_PIPE"); return e && e[0] == '1'; }();
     if (!on || bv.uhf || bv.n > 64 || bv.topo.lmax > 2 || !bv.grid.rad || bv.grid.rad_pt != XP_PT) return false;
+    // no RSH instantiation: range-separated hybrids (ITYH, wB97X) go on to the tile kernel
+    if (bv.xc.omega > 0.0) return false;
     bool has_x = false, has_c = false;
     for (int k = 0; k < bv.xc.ncomp; ++k) { if (xc_is_exchange(bv.xc.id[k])) has_x = true; else has_c = true; }
     if (!has_x) return false;             // the exchange wave also carries the gradient and the electron count
