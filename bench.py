@@ -33,10 +33,18 @@ Prints ONE JSON line on rank 0 (contract in the task statement), including
   roofline     -- the dominant kernel of THIS run (J/K stream, integral stage, XC quadrature or SCF step, whichever
                   took the most HIP-event time inside the timed region) against its bound, plus `stages` with the
                   figure of every stage
+
+A plain run does only what that line's headline needs: set-up, the cold evaluation and the warm-up, the timed steps,
+--dump-outputs, the line.  `--full` adds the measurements and checks that take runs of their own, after the timed
+steps and never part of `value`:
   cpu_baseline -- the oracle (a CPU port of the reference's libcint path) on this box's host cores the way the
                   reference runs an MBE job: one single-threaded process per core, fragments handed out one at a
                   time (mqc_many_body_expansion.f90:455-461), over a bounded sample of the same fragments; the
-                  sample's energies are compared with the GPU's (`parity_max_abs_diff`).
+                  sample's energies are compared with the GPU's (`parity_max_abs_diff`)
+  b3lyp        -- the same cluster with B3LYP, its own roofline and CPU sample
+  secondary    -- DF-RHF, DF-B3LYP, the single-call drop-in, FMO2 of the same cluster and one benzene (configs[1])
+  mfma_counters -- MFMA-utilisation counters of the committed B3LYP / DF --pmc passes
+`--no-secondary` and `--no-cpu-baseline` leave parts of that out of a --full run.
 """
 import argparse
 import json
@@ -67,10 +75,13 @@ def parse_args():
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="N > 1: weak = every rank evaluates the MBE-2 of its own copy of the cluster (per-GPU work fixed); "
                          "strong = the ONE cluster's term list round-robin over the ranks (total work fixed)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's steps, also run the CPU baselines and the B3LYP / DF / single-call / FMO2 / "
+                         "benzene measurements (off: a plain run does only what the headline needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-dimers-per-core", type=int, default=2, help="CPU-baseline sample: dimers per host core")
     ap.add_argument("--cpu-procs", type=int, default=0, help="CPU-baseline worker processes (0 = the cores this process may use, at most 32)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the extra B3LYP / DF / single-call measurements")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the extra B3LYP / DF / single-call measurements")
     ap.add_argument("--fixed-geometry", action="store_true", help="re-evaluate bit-identical coordinates (round-1 behaviour: caches hit)")
     ap.add_argument("--energy-tol", type=float, default=1e-10)
     ap.add_argument("--density-tol", type=float, default=1e-8)
@@ -305,7 +316,7 @@ def main():
     # the level-3 pruned grid, 20 % exact exchange from the same in-core tensor): one warm-up + two timed evaluations on
     # fresh geometries, its own engine statistics (-> its own roofline) -- never part of `value`
     b3 = None
-    if not args.no_secondary and not args.functional and not args.df:
+    if args.full and not args.no_secondary and not args.functional and not args.df:
         sb = methods.ScfSettings(basis_set=args.basis, functional="b3lyp", guess="gwh", energy_tol=args.energy_tol,
                                  density_tol=args.density_tol, schwarz_tol=args.schwarz_tol, device_rank=local_rank)
         _, e_b3_frag, _ = evaluate(system0, sb, terms)       # warm-up on the unmoved cluster: its fragment energies are what the CPU sample is compared with
@@ -333,7 +344,7 @@ def main():
     # the same cluster (one warm-up + one timed evaluation each, moved geometry), and the literal drop-in: ONE fragment
     # per mqc_hip_scf_run call, as an unchanged do_fragment_work would drive the engine
     secondary = None
-    if not args.no_secondary and not args.functional and not args.df and world == 1:     # single-GPU measurements: the N = 1 line carries them
+    if args.full and not args.no_secondary and not args.functional and not args.df and world == 1:     # single-GPU measurements: the N = 1 line carries them
         secondary = {}
         for label, kw in (("rhf_density_fitted", dict(density_fitting=True)),
                           ("b3lyp_density_fitted", dict(functional="b3lyp", density_fitting=True))):
@@ -504,6 +515,7 @@ def main():
             "ms_per_step": 1e3 * elapsed / n_steps,
             "higher_is_better": True,
             "scaling": args.scaling,
+            "full": args.full,
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
@@ -560,7 +572,7 @@ def main():
                 line["b3lyp"]["cpu_baseline"] = cb
                 line["b3lyp"]["parity_max_abs_diff"] = cb["parity_max_abs_diff"]
         line["secondary"] = secondary
-        pm_all = committed_pmc()
+        pm_all = committed_pmc() if args.full else None
         if pm_all and "passes" in pm_all:
             # MFMA-utilisation counters (SQ_VALU_MFMA_BUSY_CYCLES, SQ_INSTS_VALU_MFMA_MOPS_F64) of the B3LYP and DF commands,
             # collected in their own rocprofv3 --pmc passes and committed under profiles/
@@ -572,7 +584,7 @@ def main():
                 return None
             line["mfma_counters"] = {"xc": _mf("sq_b3lyp", "xc_tile_kernel"), "df_jk": _mf("sq_df", "df_jk_mfma_kernel"),
                                      "df_fit": _mf("sq_df", "df_fit_mfma_kernel"), "source": pm_all.get("_source")}
-        if not args.no_cpu_baseline and world == 1 and not args.functional and not args.df:
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.functional and not args.df:
             line["cpu_baseline"] = cpu_baseline(system0, terms, args.basis, energies0, args)
             line["parity_max_abs_diff"] = line["cpu_baseline"]["parity_max_abs_diff"]
         else:

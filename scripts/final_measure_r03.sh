@@ -5,7 +5,7 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-r03_final}
 mkdir -p $O
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python bench.py --functional b3lyp --no-secondary --no-cpu-baseline > $O/bench_b3lyp.json 2> $O/bench_b3lyp.err
 python bench.py --df --no-secondary --no-cpu-baseline > $O/bench_df.json 2> $O/bench_df.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_rhf -o rhf -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > $O/prof_rhf.log 2>&1
