@@ -797,6 +797,9 @@ void launch_direct_setup(const BatchView& bv, const Topology& topo, hipStream_t 
     (void)hipStreamSynchronize(s);
 }
 
+// the Schwarz bounds Q [nfrag][ns][ns] launch_direct_setup formed for the batch in this slot
+const double* direct_schwarz_view(int slot) { return (const double*)g_direct_q_slot[slot & 1].ensure(0); }
+
 #define DIG_CASE(a, b, c, d)                                                                          \
     if (!general && cl.la == a && cl.lb == b && cl.lc == c && cl.ld == d)                             \
         launch_eri_digest_class<a, b, c, d>(bv, d_list + off, (int)cl.quartets.size() / 4, Q, Dmax, thresh, Jt, Kt, oa, s);

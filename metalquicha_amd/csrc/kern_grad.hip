@@ -17,6 +17,8 @@
 // once per block; the derivative integrals are then contracted on the fly -- nine numbers per quartet (centres A, B, C;
 // D by translational invariance), never stored.  Shells up to f; the two largest f classes pass their ket columns in chunks.
 #include "eri_kernels.hpp"
+#include <cstdio>
+#include <cstdlib>
 
 namespace mqc {
 
@@ -178,6 +180,69 @@ __global__ void grad_total_density_kernel(BatchView bv, double* __restrict__ Dto
     const size_t total = (size_t)bv.nfrag * bv.n * bv.n;
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < total) Dtot[idx] = bv.D[idx] + bv.Db[idx];
+}
+
+// ---------------------------------------------------------------------------------------
+// Screening of the two-electron term (fragments above n_ao = 140).  Block maxima per shell pair, Pm [nfrag][3][ns][ns]:
+// |Dtot|, and for an unrestricted run |D_alpha|, |D_beta| (the exchange densities of Gamma).
+__global__ void grad_density_max_kernel(BatchView bv, const double* __restrict__ Dtot, double* __restrict__ Pm)
+{
+    const int f = blockIdx.y, ns = bv.topo.nshell, n = bv.n;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= ns * ns) return;
+    const int A = idx / ns, B = idx - A * ns;
+    const int oa = bv.topo.sh_aoff[A], ob = bv.topo.sh_aoff[B];
+    const int na = 2 * bv.topo.sh_l[A] + 1, nb = 2 * bv.topo.sh_l[B] + 1;
+    const size_t nn = (size_t)n * n;
+    const double* Dt = Dtot + f * nn;
+    const double* Da = bv.D + f * nn;
+    const double* Db = bv.uhf ? bv.Db + f * nn : nullptr;
+    double mt = 0.0, ma = 0.0, mb = 0.0;
+    for (int i = 0; i < na; ++i)
+        for (int j = 0; j < nb; ++j) {
+            const size_t o = (size_t)(oa + i) * n + ob + j;
+            mt = fmax(mt, fabs(Dt[o]));
+            if (Db) { ma = fmax(ma, fabs(Da[o])); mb = fmax(mb, fabs(Db[o])); }
+        }
+    double* p = Pm + (size_t)f * 3 * ns * ns;
+    p[idx] = mt; p[ns * ns + idx] = ma; p[2 * ns * ns + idx] = mb;
+}
+
+// The quartets of one class whose Schwarz bound Q_AB Q_CD times the density factor of Gamma (header of this file)
+//     4 |Dt_AB| |Dt_CD| + exx (|Dt_AC| |Dt_BD| + |Dt_AD| |Dt_BC|)                        restricted
+//     4 |Dt_AB| |Dt_CD| + 2 exx sum_spin (|Ds_AC| |Ds_BD| + |Ds_AD| |Ds_BC|)              unrestricted
+// reaches thresh, compacted into out (one atomic per wave); Q and Pm are the fragment's own
+__global__ void __launch_bounds__(256) grad_screen_kernel(const int* __restrict__ list, int nq, int ns, const double* __restrict__ Q,
+                                                          const double* __restrict__ Pm, int uhf, double exx, double thresh,
+                                                          int* __restrict__ out, int* __restrict__ count)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    int A = 0, B = 0, C = 0, D = 0;
+    bool keep = false;
+    if (i < nq) {
+        A = list[4 * i]; B = list[4 * i + 1]; C = list[4 * i + 2]; D = list[4 * i + 3];
+        const double* t = Pm;
+        double fac = 4.0 * t[A * ns + B] * t[C * ns + D];
+        if (exx != 0.0) {
+            if (uhf) {
+                const double* a = Pm + ns * ns; const double* b = a + ns * ns;
+                fac += 2.0 * fabs(exx) * (a[A * ns + C] * a[B * ns + D] + a[A * ns + D] * a[B * ns + C] +
+                                          b[A * ns + C] * b[B * ns + D] + b[A * ns + D] * b[B * ns + C]);
+            } else {
+                fac += fabs(exx) * (t[A * ns + C] * t[B * ns + D] + t[A * ns + D] * t[B * ns + C]);
+            }
+        }
+        keep = Q[A * ns + B] * Q[C * ns + D] * fac >= thresh;
+    }
+    const unsigned long long m = __ballot(keep);
+    const int lane = threadIdx.x & 63;
+    int base = 0;
+    if (lane == 0 && m) base = atomicAdd(count, __popcll(m));
+    base = __shfl(base, 0, 64);
+    if (keep) {
+        const int k = base + __popcll(m & ((1ull << lane) - 1ull));
+        out[4 * k] = A; out[4 * k + 1] = B; out[4 * k + 2] = C; out[4 * k + 3] = D;
+    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -877,14 +942,65 @@ static bool launch_df_gradient(const BatchView& bv, const Topology& topo, const 
     return true;
 }
 
+// The exact two-electron term of fragments above n_ao = 140 (schwarz != nullptr: the direct path's bounds [nfrag][ns][ns]):
+// per fragment, every class list is screened on the device into a compacted copy, and the survivor counts come back in
+// one read; the class launches then cover the survivors of that fragment only (a one-fragment view of the batch).
+static bool launch_eri_grad_screened(const BatchView& bv, const Topology& topo, const double* Dtot, double* d_grad, const int* d_lists,
+                                     const std::vector<size_t>& class_off, const double* schwarz, double thresh, hipStream_t s, std::string& err)
+{
+    const int n = bv.n, nf = bv.nfrag, ns = (int)topo.shells.size(), ncl = (int)topo.classes.size();
+    const size_t nn = (size_t)n * n, nss = (size_t)ns * ns;
+    size_t lint = 0;
+    for (auto& cl : topo.classes) lint += cl.quartets.size();
+    static DevicePool pool_slot[2];
+    const size_t pm_doubles = (size_t)nf * 3 * nss;
+    char* base = (char*)pool_slot[bv.slot & 1].ensure(sizeof(double) * pm_doubles + sizeof(int) * (lint + 64 + (size_t)ncl));
+    if (!base) { err = "out of device memory (gradient screening)"; return false; }
+    double* Pm = (double*)base;
+    int* counts = (int*)(Pm + pm_doubles);
+    int* out = counts + ((ncl + 63) & ~63);
+    hipLaunchKernelGGL(grad_density_max_kernel, dim3((unsigned)((nss + 255) / 256), nf), dim3(256), 0, s, bv, Dtot, Pm);
+    std::vector<int> hcount(ncl);
+    for (int f = 0; f < nf; ++f) {
+        (void)hipMemsetAsync(counts, 0, sizeof(int) * ncl, s);
+        for (int k = 0; k < ncl; ++k) {
+            const int nq = (int)(topo.classes[k].quartets.size() / 4);
+            if (nq == 0) continue;
+            hipLaunchKernelGGL(grad_screen_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, d_lists + class_off[k], nq, ns,
+                               schwarz + (size_t)f * nss, (const double*)(Pm + (size_t)f * 3 * nss), bv.uhf ? 1 : 0, bv.exx, thresh,
+                               out + class_off[k] - class_off[0], counts + k);
+        }
+        if (hipMemcpyAsync(hcount.data(), counts, sizeof(int) * ncl, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) { err = "gradient: screening failed"; return false; }
+        BatchView vf = bv;
+        vf.nfrag = 1;
+        vf.xyz = bv.xyz + (size_t)f * topo.natoms * 3;
+        const double* Dbf = bv.uhf ? bv.Db + f * nn : (const double*)nullptr;
+        for (int k = 0; k < ncl; ++k) {
+            if (hcount[k] == 0) continue;
+            const auto& cl = topo.classes[k];
+            const Grad2eLayout lay = grad2e_layout(cl.la, cl.lb, cl.lc, cl.ld);
+            if (sizeof(double) * (size_t)lay.total > 160 * 1024) { err = "gradient: class too large for LDS"; return false; }
+            hipLaunchKernelGGL(eri_grad_kernel, dim3((unsigned)hcount[k]), dim3(64), sizeof(double) * (size_t)lay.total, s, vf, cl.la, cl.lb, cl.lc, cl.ld, lay,
+                               (const int*)(out + class_off[k] - class_off[0]), hcount[k], Dtot + f * nn, Dbf, d_grad + (size_t)f * topo.natoms * 3);
+        }
+    }
+    return true;
+}
+
 bool launch_gradient(const BatchView& bv, const Topology& topo, const Topology* aux, double* d_grad, double* work, int* d_lists,
-                     size_t list_capacity_ints, hipStream_t s, std::string& err)
+                     size_t list_capacity_ints, hipStream_t s, std::string& err, const double* schwarz, double screen_tol)
 {
     const int n = bv.n, nf = bv.nfrag;
     const size_t nn = (size_t)n * n;
     if (topo.lmax > 3) { err = "analytic gradients cover s, p, d and f shells"; return false; }
     double* Wm = work;
     double* Dtot = bv.D;
+    // MQC_HIP_GRAD_TIMING=1 (measurement): the span of this stage and of its XC part on stderr, per batch
+    static const bool timing = [] { const char* e = std::getenv("MQC_HIP_GRAD_TIMING"); return e && e[0] == '1'; }();
+    hipEvent_t ev[3] = {};
+    if (timing) for (auto& e : ev) { (void)hipEventCreate(&e); }
+    if (timing) (void)hipEventRecord(ev[0], s);
     (void)hipMemsetAsync(d_grad, 0, sizeof(double) * (size_t)nf * topo.natoms * 3, s);
     hipLaunchKernelGGL(grad_weighted_density_kernel, dim3((unsigned)((nn + 255) / 256), nf), dim3(256), 0, s, bv, Wm);
     if (bv.uhf) {
@@ -923,6 +1039,15 @@ bool launch_gradient(const BatchView& bv, const Topology& topo, const Topology* 
     if (bv.naux > 0) {
         if (!aux) { err = "gradient: the auxiliary basis is missing"; return false; }
         if (!launch_df_gradient(bv, topo, *aux, Dtot, d_grad, s, err)) return false;
+    } else if (schwarz) {
+        std::vector<size_t> class_off;
+        for (auto& cl : topo.classes) {
+            class_off.push_back(off);
+            if (!cl.quartets.empty())
+                (void)hipMemcpyAsync(d_lists + off, cl.quartets.data(), cl.quartets.size() * sizeof(int), hipMemcpyHostToDevice, s);
+            off += cl.quartets.size();
+        }
+        if (!launch_eri_grad_screened(bv, topo, Dtot, d_grad, d_lists, class_off, schwarz, screen_tol, s, err)) return false;
     } else
     for (auto& cl : topo.classes) {
         if (cl.quartets.empty()) continue;
@@ -935,7 +1060,17 @@ bool launch_gradient(const BatchView& bv, const Topology& topo, const Topology* 
         off += cl.quartets.size();
     }
     // ---- exchange-correlation (Kohn-Sham): moving functions, moving points, moving partition
+    if (timing) (void)hipEventRecord(ev[1], s);
     if (bv.xc.ncomp > 0 && !launch_xc_gradient(bv, d_grad, s, err)) return false;
+    if (timing) {
+        (void)hipEventRecord(ev[2], s);
+        (void)hipEventSynchronize(ev[2]);
+        float all = 0.f, xc = 0.f;
+        (void)hipEventElapsedTime(&all, ev[0], ev[2]);
+        (void)hipEventElapsedTime(&xc, ev[1], ev[2]);
+        std::fprintf(stderr, "mqc_hip gradient: n=%d nfrag=%d screened=%d total %.3f ms, XC %.3f ms\n", n, nf, schwarz ? 1 : 0, all, xc);
+        for (auto& e : ev) (void)hipEventDestroy(e);
+    }
     return true;
 }
 

@@ -2831,6 +2831,205 @@ __global__ void __launch_bounds__(XG_NT) xc_grad_kernel(BatchView bv, double* __
         if (gacc[i] != 0.0) atomicAdd(&d_grad[(size_t)f * tp.natoms * 3 + i], gacc[i]);
 }
 
+// ---- the wide form of the moving-functions / moving-points term, for fragments whose six second derivatives per
+// function and point do not fit the LDS beside the rest (n up to 256; MQC_HIP_XC_GRAD_WIDE=1 takes it at every n).
+// The LDS holds chi, d chi (4 values) and X = D chi, Xg_j = D d_j chi (NX values) per function and point; step 4
+// forms the second derivatives again in registers, one (shell, point) item at a time, from the radial sums.
+
+// radial sums R0 = R, R1 = R'/r, R2 = (R'/r)'/r of shell sh at grid point g and the offset x from its centre
+__device__ __forceinline__ void xgw_radial(const TopologyDev& tp, const GridDev& gd, const double* __restrict__ xyz, int sh, int g,
+                                           double* x, double& R0, double& R1, double& R2)
+{
+    const int at = tp.sh_atom[sh], oa = gd.pt_atom[g], it = gd.pt_tmpl[g];
+    for (int d = 0; d < 3; ++d) x[d] = xyz[3 * oa + d] + gd.tmpl_xyz[3 * it + d] - xyz[3 * at + d];
+    const double r2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
+    const double* e = tp.exps + tp.sh_poff[sh];
+    const double* c = tp.coefs + tp.sh_poff[sh];
+    R0 = 0.0; R1 = 0.0; R2 = 0.0;
+    for (int k = 0; k < tp.sh_nprim[sh]; ++k) {
+        const double a = e[k], ar2 = a * r2;
+        if (ar2 < XC_EXP_CUTOFF) {
+            const double t = c[k] * exp(-ar2);
+            R0 += t; R1 -= 2.0 * a * t; R2 += 4.0 * a * a * t;
+        }
+    }
+}
+
+// polynomial P of real solid harmonic m of shell l at x, its gradient Pi and packed Hessian Pij (xx, xy, xz, yy, yz, zz),
+// in the order and normalisation of emit_shell_d2
+__device__ __forceinline__ void xgw_harmonic(int l, int m, const double* x, const double* __restrict__ c2s, double& P, double* Pi, double* Pij)
+{
+    P = 0.0;
+    for (int i = 0; i < 3; ++i) Pi[i] = 0.0;
+    for (int i = 0; i < 6; ++i) Pij[i] = 0.0;
+    if (l == 0) { P = 1.0; return; }
+    if (l == 1) {
+        for (int i = 0; i < 3; ++i) if (i == m) { P = x[i]; Pi[i] = 1.0; }
+        return;
+    }
+    if (l == 2) {
+        const int ca[6] = {0, 0, 0, 1, 1, 2}, cb[6] = {0, 1, 2, 1, 2, 2};
+        for (int c = 0; c < 6; ++c) {
+            const double w = c2s_coef<2>(nullptr, m, c);
+            if (w == 0.0) continue;
+            const int a = ca[c], b = cb[c];
+            P += w * x[a] * x[b];
+            Pi[a] += w * x[b]; Pi[b] += w * x[a];
+            Pij[c] += (a == b) ? 2.0 * w : w;
+        }
+        return;
+    }
+    double pw[3][LMAX_AO + 1];
+    for (int d = 0; d < 3; ++d) { pw[d][0] = 1.0; for (int k = 1; k <= l; ++k) pw[d][k] = pw[d][k - 1] * x[d]; }
+    const int nc = ncart(l);
+    for (int c = 0; c < nc; ++c) {
+        const double w = c2s[c2s_table_offset(l) + m * nc + c];
+        if (w == 0.0) continue;
+        int e[3];
+        cart_lmn(l, c, e[0], e[1], e[2]);
+        double f0[3], f1[3], f2[3];
+        for (int d = 0; d < 3; ++d) {
+            f0[d] = pw[d][e[d]];
+            f1[d] = e[d] > 0 ? e[d] * pw[d][e[d] - 1] : 0.0;
+            f2[d] = e[d] > 1 ? e[d] * (e[d] - 1) * pw[d][e[d] - 2] : 0.0;
+        }
+        P += w * f0[0] * f0[1] * f0[2];
+        Pi[0] += w * f1[0] * f0[1] * f0[2]; Pi[1] += w * f0[0] * f1[1] * f0[2]; Pi[2] += w * f0[0] * f0[1] * f1[2];
+        Pij[0] += w * f2[0] * f0[1] * f0[2]; Pij[1] += w * f1[0] * f1[1] * f0[2]; Pij[2] += w * f1[0] * f0[1] * f1[2];
+        Pij[3] += w * f0[0] * f2[1] * f0[2]; Pij[4] += w * f0[0] * f1[1] * f1[2]; Pij[5] += w * f0[0] * f0[1] * f2[2];
+    }
+}
+
+template <bool GGA, bool UKS, int PT>
+__global__ void __launch_bounds__(XG_NT) xc_grad_wide_kernel(BatchView bv, double* __restrict__ d_grad, double* __restrict__ fbuf)
+{
+    extern __shared__ double lds[];
+    const int f = blockIdx.y, tid = threadIdx.x, n = bv.n;
+    const TopologyDev& tp = bv.topo;
+    const GridDev& gd = bv.grid;
+    constexpr int PTP = PT + 1, NXS = GGA ? 4 : 1, NSP = UKS ? 2 : 1;
+    const size_t S = (size_t)n * PTP;
+    double* ao = lds;                                   // [4][n][PTP]: chi, d chi (3)
+    double* X = ao + 4 * S;                             // [NSP][NXS][n][PTP]: D chi, D d_j chi
+    double* pwv = X + (size_t)NSP * NXS * S;            // [NSP][4][PT]: w v_rho, w c_j
+    double* gacc = pwv + NSP * 4 * PT;                  // [natoms][3]
+    int* own = (int*)(gacc + 3 * tp.natoms);            // [PT]
+    const double* xyz = bv.xyz + (size_t)f * tp.natoms * 3;
+    const double* Dm[2] = {bv.D + (size_t)f * n * n, UKS ? bv.Db + (size_t)f * n * n : nullptr};
+    const double* wts = gd.weights + (size_t)f * gd.npts;
+
+    for (int i = tid; i < 3 * tp.natoms; i += XG_NT) gacc[i] = 0.0;
+    const int ntiles = (gd.npts + PT - 1) / PT;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int g0 = tile * PT;
+        // 1. functions and first derivatives: (shell, point) items
+        for (int idx = tid; idx < tp.nshell * PT; idx += XG_NT) {
+            const int sh = idx / PT, p = idx - sh * PT, g = g0 + p;
+            const int l = tp.sh_l[sh], a0 = tp.sh_aoff[sh];
+            double x[3] = {0.0, 0.0, 0.0}, R0 = 0.0, R1 = 0.0, R2 = 0.0;
+            if (g < gd.npts) xgw_radial(tp, gd, xyz, sh, g, x, R0, R1, R2);
+            for (int m = 0; m < 2 * l + 1; ++m) {
+                double P, Pi[3], Pij[6];
+                xgw_harmonic(l, m, x, bv.c2s, P, Pi, Pij);
+                const int o = (a0 + m) * PTP + p;
+                ao[o] = P * R0;
+                for (int i = 0; i < 3; ++i) ao[(1 + i) * S + o] = Pi[i] * R0 + P * R1 * x[i];
+            }
+        }
+        if (tid < PT) own[tid] = (g0 + tid < gd.npts) ? gd.pt_atom[g0 + tid] : 0;
+        __syncthreads();
+        // 2. X = D chi and, for a gradient-corrected functional, D d_j chi, per spin
+        for (int idx = tid; idx < n * PT; idx += XG_NT) {
+            const int mu = idx / PT, p = idx - mu * PT;
+            for (int sp = 0; sp < NSP; ++sp) {
+                const double* __restrict__ dr = Dm[sp] + (size_t)mu * n;
+                double acc[NXS];
+                for (int k = 0; k < NXS; ++k) acc[k] = 0.0;
+                for (int nu = 0; nu < n; ++nu) {
+                    const double d = dr[nu];
+                    for (int k = 0; k < NXS; ++k) acc[k] += d * ao[k * S + nu * PTP + p];
+                }
+                for (int k = 0; k < NXS; ++k) X[((size_t)sp * NXS + k) * S + mu * PTP + p] = acc[k];
+            }
+        }
+        __syncthreads();
+        // 3. densities, the functional, the per-point weights; the energy density goes to fbuf for the partition term
+        if (tid < PT) {
+            const int p = tid, g = g0 + p;
+            double rho[2] = {0.0, 0.0}, gr[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+            for (int sp = 0; sp < NSP; ++sp)
+                for (int mu = 0; mu < n; ++mu) {
+                    const double xc_ = X[(size_t)sp * NXS * S + mu * PTP + p];
+                    rho[sp] += xc_ * ao[mu * PTP + p];
+                    if (GGA) for (int j = 0; j < 3; ++j) gr[sp][j] += 2.0 * xc_ * ao[(1 + j) * S + mu * PTP + p];
+                }
+            const double w = (g < gd.npts) ? wts[g] : 0.0;
+            double fx = 0.0;
+            if (!UKS) {
+                const double sigma = GGA ? gr[0][0] * gr[0][0] + gr[0][1] * gr[0][1] + gr[0][2] * gr[0][2] : 0.0;
+                double vr, vs;
+                eval_functional(bv.xc, rho[0], sigma, fx, vr, vs);
+                pwv[p] = w * vr;
+                for (int j = 0; j < 3; ++j) pwv[(1 + j) * PT + p] = GGA ? w * 2.0 * vs * gr[0][j] : 0.0;
+            } else {
+                double saa = 0.0, sab = 0.0, sbb = 0.0, dv[5];
+                for (int j = 0; j < 3; ++j) { saa += gr[0][j] * gr[0][j]; sab += gr[0][j] * gr[1][j]; sbb += gr[1][j] * gr[1][j]; }
+                eval_functional_pol(bv.xc, rho[0], rho[1], saa, sab, sbb, fx, dv);
+                pwv[p] = w * dv[0]; pwv[4 * PT + p] = w * dv[1];
+                for (int j = 0; j < 3; ++j) {
+                    pwv[(1 + j) * PT + p] = GGA ? w * (2.0 * dv[2] * gr[0][j] + dv[3] * gr[1][j]) : 0.0;
+                    pwv[(5 + j) * PT + p] = GGA ? w * (2.0 * dv[4] * gr[1][j] + dv[3] * gr[0][j]) : 0.0;
+                }
+            }
+            if (g < gd.npts) fbuf[(size_t)f * gd.npts + g] = fx;
+        }
+        __syncthreads();
+        // 4. sums per (shell, point), second derivatives in registers: the functions move with the shell's atom, the
+        //    point with its owner
+        for (int idx = tid; idx < tp.nshell * PT; idx += XG_NT) {
+            const int sh = idx / PT, p = idx - sh * PT, g = g0 + p;
+            if (g >= gd.npts) continue;
+            const int l = tp.sh_l[sh], a0 = tp.sh_aoff[sh], A = tp.sh_atom[sh];
+            double x[3], R0, R1, R2;
+            xgw_radial(tp, gd, xyz, sh, g, x, R0, R1, R2);
+            double Sk[3] = {0.0, 0.0, 0.0};
+            for (int m = 0; m < 2 * l + 1; ++m) {
+                double P, Pi[3], Pij[6];
+                xgw_harmonic(l, m, x, bv.c2s, P, Pi, Pij);
+                double gk[3], h[6];
+                for (int i = 0; i < 3; ++i) gk[i] = Pi[i] * R0 + P * R1 * x[i];
+                if (GGA) {
+                    int q = 0;
+                    for (int i = 0; i < 3; ++i)
+                        for (int j = i; j < 3; ++j, ++q)
+                            h[q] = Pij[q] * R0 + (Pi[i] * x[j] + Pi[j] * x[i]) * R1 + P * (R2 * x[i] * x[j] + (i == j ? R1 : 0.0));
+                }
+                const int o = (a0 + m) * PTP + p;
+                for (int sp = 0; sp < NSP; ++sp) {
+                    const double wv = pwv[(sp * 4) * PT + p];
+                    const double* Xs = X + (size_t)sp * NXS * S;
+                    const double xc_ = Xs[o];
+                    for (int k = 0; k < 3; ++k) Sk[k] += wv * gk[k] * xc_;
+                    if (GGA) {
+                        const double c0 = pwv[(sp * 4 + 1) * PT + p], c1 = pwv[(sp * 4 + 2) * PT + p], c2 = pwv[(sp * 4 + 3) * PT + p];
+                        const double xg = c0 * Xs[S + o] + c1 * Xs[2 * S + o] + c2 * Xs[3 * S + o];        // sum_j c_j (D d_j chi)_mu
+                        Sk[0] += (c0 * h[0] + c1 * h[1] + c2 * h[2]) * xc_ + gk[0] * xg;
+                        Sk[1] += (c0 * h[1] + c1 * h[3] + c2 * h[4]) * xc_ + gk[1] * xg;
+                        Sk[2] += (c0 * h[2] + c1 * h[4] + c2 * h[5]) * xc_ + gk[2] * xg;
+                    }
+                }
+            }
+            const int ow = own[p];
+            for (int k = 0; k < 3; ++k) {
+                if (Sk[k] != 0.0) { atomicAdd(&gacc[3 * A + k], -2.0 * Sk[k]); atomicAdd(&gacc[3 * ow + k], 2.0 * Sk[k]); }
+            }
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < 3 * tp.natoms; i += XG_NT)
+        if (gacc[i] != 0.0) atomicAdd(&d_grad[(size_t)f * tp.natoms * 3 + i], gacc[i]);
+}
+
 // d(f3(f2(f1(nu))))/d nu of Becke's cell function s = (1 - f3) / 2, f(x) = x (3 - x^2) / 2
 __device__ __forceinline__ void becke_cutoff_d(double nu, double& s, double& ds)
 {
@@ -2932,7 +3131,30 @@ bool launch_xc_gradient(const BatchView& bv, double* d_grad, hipStream_t s, std:
     if (!fbuf) { err = "out of device memory (XC gradient)"; return false; }
     const int NA = gga ? 10 : 4, NX = (gga ? 4 : 1) * (uks ? 2 : 1);
     const size_t lds = sizeof(double) * ((size_t)(NA + NX) * n * (XG_PT + 1) + 8 * XG_PT + 3 * bv.topo.natoms + 8) + sizeof(int) * (bv.topo.natoms + 2 + XG_PT);
-    if (lds > 160 * 1024) { err = "XC gradient: fragment too large for the LDS slab"; return false; }
+    // MQC_HIP_XC_GRAD_WIDE=1: the wide kernel at every n (A/B switch); otherwise only where the slab above does not fit
+    static const bool wide_env = [] { const char* e = std::getenv("MQC_HIP_XC_GRAD_WIDE"); return e && e[0] == '1'; }();
+    if (wide_env || lds > 160 * 1024) {
+        auto wide_lds = [&](int pt) { return sizeof(double) * ((size_t)(4 + NX) * n * (pt + 1) + 8 * pt + 3 * bv.topo.natoms + 8) + sizeof(int) * (pt + 8); };
+        const int pt = wide_lds(8) <= 160 * 1024 ? 8 : 4;
+        const size_t wl = wide_lds(pt);
+        if (wl > 160 * 1024) { err = "XC gradient: fragment too large for the LDS slab"; return false; }
+        const int ntw = (bv.grid.npts + pt - 1) / pt;
+        int gw = (8192 + bv.nfrag - 1) / bv.nfrag;
+        if (gw > ntw) gw = ntw;
+        if (gw < 1) gw = 1;
+#define XGW_LAUNCH(G, U, P)                                                                                 \
+    do {                                                                                                    \
+        (void)hipFuncSetAttribute((const void*)xc_grad_wide_kernel<G, U, P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl); \
+        hipLaunchKernelGGL((xc_grad_wide_kernel<G, U, P>), dim3(gw, bv.nfrag), dim3(XG_NT), wl, s, bv, d_grad, fbuf); \
+    } while (0)
+#define XGW_PT(G, U) do { if (pt == 8) XGW_LAUNCH(G, U, 8); else XGW_LAUNCH(G, U, 4); } while (0)
+        if (gga) { if (uks) XGW_PT(true, true); else XGW_PT(true, false); }
+        else { if (uks) XGW_PT(false, true); else XGW_PT(false, false); }
+#undef XGW_PT
+#undef XGW_LAUNCH
+        hipLaunchKernelGGL(becke_xc_grad_kernel, dim3((bv.grid.npts + 255) / 256, bv.nfrag), dim3(256), 0, s, bv, fbuf, d_grad);
+        return true;
+    }
     const int ntiles = (bv.grid.npts + XG_PT - 1) / XG_PT;
     int gx = (8192 + bv.nfrag - 1) / bv.nfrag;
     if (gx > ntiles) gx = ntiles;
