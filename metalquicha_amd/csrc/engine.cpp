@@ -59,10 +59,6 @@ static size_t scratch_reservation_bytes(const mqc_hip_context* ctx)
     return (size_t)queues * SCRATCH_BOUND_PER_LANE * 64 * waves;
 }
 
-struct TopoDevHolder {
-    TopologyDev dev;
-};
-
 static int upload_topology(mqc_hip_context* ctx, const Topology& topo, TopologyDev& td, DevicePool* pool = nullptr, hipStream_t stream = nullptr)
 {
     if (!pool) pool = &ctx->pool_topo;
@@ -156,103 +152,44 @@ static int upload_topology(mqc_hip_context* ctx, const Topology& topo, TopologyD
     return MQC_HIP_OK;
 }
 
-static size_t per_fragment_main_doubles(int n, int natoms, bool uhf = false, int npc = 0, bool hx = false)
-{
-    const size_t nn = (size_t)n * n;
-    return ((npc > 0 || hx) ? nn + 4 * (size_t)npc + 64 : 0)   // embedding operator U and the point charges (x, y, z, q)
-           + (hx ? nn + 32 : 0)                                  // the caller's h_extra
-           + (uhf ? 6 * nn + 2 * DIIS_MAX * nn + n : 0)   // beta spin: D C F J K Vprev, DIIS histories, eps
-           + 9 * nn    // S H X F D C J K Vprev
-           + 6 * nn    // W
-           + 2 * DIIS_MAX * nn   // DIIS histories
-           + DIIS_MAX * DIIS_MAX + n + 8 + 3 * (size_t)natoms + 8 + 4;   // diis_b, eps, scal, xyz, ints (padded), dipole
-}
-
 // One pipeline slot: a stream with its own pools and events.  While the SCF loop of chunk k runs on
 // one slot, the integrals of chunk k+1 are formed on the other (compute-bound ERI kernels fill the
 // gaps the HBM-bound J/K stream and the per-iteration host round trip leave).
 struct Slot {
     int id;
     hipStream_t s;
-    DevicePool *main, *eri, *misc, *gridw, *df;
-    hipEvent_t e0, e1, e2, e3, q0, q1;
+    DevicePool* pool[NPOOL];          // indexed by POOL_*
+    hipEvent_t e0, e1, e2, e3, q0, q1, s0, s1;
     int* h_counter;
-    hipEvent_t s0 = nullptr, s1 = nullptr;
 };
 
-// carve one chunk's arrays out of the slot's pools
-static int carve_batch(mqc_hip_context* ctx, Slot& sl, const Topology& topo, const TopologyDev& td, int nfrag, bool with_eri, BatchView& bv,
-                       bool uhf = false, int npc = 0, bool hx = false, bool rsh = false)
+static Slot make_slot(mqc_hip_context* ctx, int id, int* h_counter)
 {
-    const int n = topo.nao;
-    const size_t nn = (size_t)n * n, nf = (size_t)nfrag;
-    const size_t main_bytes = sizeof(double) * nf * per_fragment_main_doubles(n, topo.natoms, uhf, npc, hx) + 16384;
-    char* base = (char*)sl.main->ensure(main_bytes);
-    if (!base) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (SCF matrices)");
-    auto take = [&base](size_t b) { char* p = base; base += (b + 255) & ~size_t(255); return p; };
-    bv.topo = td; bv.nfrag = nfrag; bv.n = n; bv.npair = topo.npair; bv.slot = sl.id;
-    bv.boys = ctx->d_boys; bv.c2s = ctx->d_c2s;
-    bv.xyz = (double*)take(sizeof(double) * nf * topo.natoms * 3);
-    bv.S = (double*)take(sizeof(double) * nf * nn); bv.H = (double*)take(sizeof(double) * nf * nn);
-    bv.X = (double*)take(sizeof(double) * nf * nn); bv.F = (double*)take(sizeof(double) * nf * nn);
-    bv.D = (double*)take(sizeof(double) * nf * nn); bv.C = (double*)take(sizeof(double) * nf * nn);
-    bv.J = (double*)take(sizeof(double) * nf * nn); bv.K = (double*)take(sizeof(double) * nf * nn);
-    bv.W = (double*)take(sizeof(double) * nf * 6 * nn);
-    bv.Vprev = (double*)take(sizeof(double) * nf * nn);
-    bv.diis_f = (double*)take(sizeof(double) * nf * DIIS_MAX * nn);
-    bv.diis_e = (double*)take(sizeof(double) * nf * DIIS_MAX * nn);
-    bv.diis_b = (double*)take(sizeof(double) * nf * DIIS_MAX * DIIS_MAX);
-    bv.eps = (double*)take(sizeof(double) * nf * n);
-    bv.scal = (double*)take(sizeof(double) * nf * 8);
-    bv.dip = (double*)take(sizeof(double) * nf * 4);
-    bv.uhf = uhf ? 1 : 0; bv.nalpha = 0; bv.nbeta = 0;
-    bv.Db = bv.Cb = bv.Fb = bv.Jb = bv.Kb = bv.Vprevb = bv.epsb = bv.diis_fb = bv.diis_eb = nullptr;
-    if (uhf) {
-        bv.Db = (double*)take(sizeof(double) * nf * nn); bv.Cb = (double*)take(sizeof(double) * nf * nn);
-        bv.Fb = (double*)take(sizeof(double) * nf * nn); bv.Jb = (double*)take(sizeof(double) * nf * nn);
-        bv.Kb = (double*)take(sizeof(double) * nf * nn); bv.Vprevb = (double*)take(sizeof(double) * nf * nn);
-        bv.diis_fb = (double*)take(sizeof(double) * nf * DIIS_MAX * nn);
-        bv.diis_eb = (double*)take(sizeof(double) * nf * DIIS_MAX * nn);
-        bv.epsb = (double*)take(sizeof(double) * nf * n);
-    }
-    bv.diis_state = (int*)take(sizeof(int) * nf * 2);
-    bv.istate = (int*)take(sizeof(int) * nf * 4);
-    bv.npc = npc; bv.pc = nullptr; bv.U = nullptr; bv.Hx = nullptr;
-    if (npc > 0) bv.pc = (double*)take(sizeof(double) * nf * npc * 4);
-    if (npc > 0 || hx) bv.U = (double*)take(sizeof(double) * nf * nn);
-    if (hx) bv.Hx = (double*)take(sizeof(double) * nf * nn);
-    bv.counters = (int*)sl.misc->ensure(256 + sizeof(int) * (2 * (size_t)topo.npair + 8 + (size_t)nfrag));      // + the block tables of a triangular tensor + its per-fragment read counters
-    if (!bv.counters) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (counters)");
-    bv.eri_count = (unsigned long long*)(bv.counters + 16);
-    bv.eri = nullptr; bv.eri_tri = 0; bv.eri_tri_pb = 0; bv.eri_tri_sb = nullptr; bv.eri_stride = 0; bv.jk_q = nullptr; bv.jk_qthresh = 0.0; bv.jk_loaded = nullptr;
-    if (with_eri) {
-        const size_t np = (size_t)topo.npair;
-        bv.eri_tri = jk_tri_layout(n, topo.npair, nfrag, uhf) ? 1 : 0;
-        bv.eri_stride = np * np;
-        if (bv.eri_tri) {
-            // triangular block layout (kern_fock.hip): block length and the start of the short row of every block
-            static std::vector<int> sb_host[2];
-            std::vector<int>& sbh = sb_host[sl.id & 1];
-            bv.eri_tri_pb = jk_tri_block(topo.npair, &sbh);
-            bv.eri_stride = (size_t)((topo.npair + 1) / 2) * (size_t)bv.eri_tri_pb;
-            int* d_sb = (int*)((char*)bv.counters + 256);
-            if (hipMemcpyAsync(d_sb, sbh.data(), sizeof(int) * sbh.size(), hipMemcpyHostToDevice, sl.s) != hipSuccess)
-                return fail(MQC_HIP_ERR_DEVICE, "upload of the tensor block table failed");
-            bv.eri_tri_sb = d_sb;
-            bv.jk_loaded = d_sb + 2 * (size_t)topo.npair + 8;
-        }
-        // range-separated hybrids: the tensor of erf(omega r12)/r12 right behind it (same layout), then J scratch and K_lr
-        // of each spin for its J/K stream -- all of it counted in the footprint that sizes the chunks (rsh_doubles)
-        const size_t lr = rsh ? nf * bv.eri_stride + nf * nn * (uhf ? 3 : 2) : 0;
-        bv.eri = (double*)sl.eri->ensure(sizeof(double) * (nf * bv.eri_stride + lr));
-        if (!bv.eri) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (ERI tensor)");
-        bv.eri_lr = nullptr; bv.Jlr = bv.Klr = bv.Klrb = nullptr;
-        if (rsh) {
-            bv.eri_lr = bv.eri + nf * bv.eri_stride;
-            bv.Jlr = bv.eri_lr + nf * bv.eri_stride;
-            bv.Klr = bv.Jlr + nf * nn;
-            if (uhf) bv.Klrb = bv.Klr + nf * nn;
-        }
+    if (id == 0)
+        return {0, ctx->stream, {&ctx->pool_main, &ctx->pool_eri, &ctx->pool_misc, &ctx->pool_gridw, &ctx->pool_df},
+                ctx->ev0, ctx->ev1, ctx->ev2, ctx->ev3, ctx->evq0, ctx->evq1, ctx->evs[0][0], ctx->evs[0][1], h_counter};
+    return {1, ctx->stream2, {&ctx->pool_main2, &ctx->pool_eri2, &ctx->pool_misc2, &ctx->pool_gridw2, &ctx->pool_df2},
+            ctx->evb0, ctx->evb1, ctx->evb2, ctx->evb3, ctx->evq2, ctx->evq3, ctx->evs[1][0], ctx->evs[1][1], h_counter};
+}
+
+// carve one chunk's arrays out of the slot's pools (carve_chunk) and upload the block table of a triangular tensor
+static int carve_slot(mqc_hip_context* ctx, const Slot& sl, const BatchPlan& plan, const TopologyDev& td, int nfrag, BatchView& bv)
+{
+    static const char* const what[NPOOL] = {"SCF matrices", "ERI tensor", "counters", "grid weights", "fitted tensor"};
+    BatchView probe{};
+    const ChunkBytes need = carve_chunk(plan, nfrag, nullptr, probe);
+    char* bases[NPOOL] = {};
+    for (int k = 0; k < NPOOL; ++k)
+        if (need.pool[k] && !(bases[k] = (char*)sl.pool[k]->ensure(need.pool[k])))
+            return fail(MQC_HIP_ERR_DEVICE, std::string("out of device memory (") + what[k] + ")");
+    carve_chunk(plan, nfrag, bases, bv);
+    bv.topo = td; bv.slot = sl.id; bv.boys = ctx->d_boys; bv.c2s = ctx->d_c2s; bv.unit = ctx->d_unit;
+    if (bv.eri_tri) {
+        static std::vector<int> sb_host[2];      // stays alive while the copy is in flight
+        std::vector<int>& sbh = sb_host[sl.id & 1];
+        jk_tri_block(plan.npair, &sbh);
+        if (hipMemcpyAsync((void*)bv.eri_tri_sb, sbh.data(), sizeof(int) * sbh.size(), hipMemcpyHostToDevice, sl.s) != hipSuccess)
+            return fail(MQC_HIP_ERR_DEVICE, "upload of the tensor block table failed");
     }
     return MQC_HIP_OK;
 }
@@ -264,55 +201,39 @@ static bool incore_supported(int n)
     return n <= 256 && (sizeof(double) * 3 * np <= 160 * 1024 - 512);
 }
 
-static int validate_options(const mqc_hip_scf_options_t& o, const Topology& topo, std::string& msg)
+static int validate_options(const mqc_hip_scf_options_t& o, const Topology& topo, const BatchPlan& p, std::string& msg)
 {
-    {
-        XcSpec tmp; std::string e;
-        if (!parse_functional(o.functional, tmp, e)) { msg = e; return MQC_HIP_ERR_UNSUPPORTED; }
-        if (tmp.gga == 2 && topo.nao > 140) { msg = "meta-GGA functionals are available up to n_ao = 140"; return MQC_HIP_ERR_UNSUPPORTED; }
-        if (tmp.ncomp > 0 && topo.natoms > 64) { msg = "XC grid: fragments above 64 atoms are not supported yet"; return MQC_HIP_ERR_UNSUPPORTED; }
-        if (tmp.omega > 0.0) {
-            // range-separated hybrids need K_lr from a second in-core tensor of erf(omega r12)/r12: nothing else forms it
-            std::string fn(o.functional);
-            std::transform(fn.begin(), fn.end(), fn.begin(), [](unsigned char c) { return (char)std::tolower(c); });
-            const std::string rs = "range-separated functionals (" + fn + ")";
-            if (o.density_fitting) { msg = rs + " need exact long-range exchange K_lr: density fitting with erf-attenuated fits is not built; use exact in-core ERIs"; return MQC_HIP_ERR_UNSUPPORTED; }
-            if (o.eri_mode == MQC_HIP_ERI_DIRECT) { msg = rs + " run on the in-core exact-ERI path only: the direct path forms no long-range exchange K_lr"; return MQC_HIP_ERR_UNSUPPORTED; }
-            if (!incore_supported(topo.nao) || topo.nao > 116) { msg = rs + " run on the in-core exact-ERI path only (n_ao <= 116); larger fragments would need a direct K_lr, which is not built"; return MQC_HIP_ERR_UNSUPPORTED; }
-            if (o.want_gradient) { msg = "analytic gradients of " + rs + " are not built (energies only)"; return MQC_HIP_ERR_UNSUPPORTED; }
-        }
+    if (p.xc.gga == 2 && topo.nao > 140) { msg = "meta-GGA functionals are available up to n_ao = 140"; return MQC_HIP_ERR_UNSUPPORTED; }
+    if (p.xc.ncomp > 0 && topo.natoms > 64) { msg = "XC grid: fragments above 64 atoms are not supported yet"; return MQC_HIP_ERR_UNSUPPORTED; }
+    if (p.rsh) {
+        // range-separated hybrids need K_lr from a second in-core tensor of erf(omega r12)/r12: nothing else forms it
+        std::string fn(o.functional);
+        std::transform(fn.begin(), fn.end(), fn.begin(), [](unsigned char c) { return (char)std::tolower(c); });
+        const std::string rs = "range-separated functionals (" + fn + ")";
+        if (o.density_fitting) { msg = rs + " need exact long-range exchange K_lr: density fitting with erf-attenuated fits is not built; use exact in-core ERIs"; return MQC_HIP_ERR_UNSUPPORTED; }
+        if (o.eri_mode == MQC_HIP_ERI_DIRECT) { msg = rs + " run on the in-core exact-ERI path only: the direct path forms no long-range exchange K_lr"; return MQC_HIP_ERR_UNSUPPORTED; }
+        if (!incore_supported(topo.nao) || topo.nao > 116) { msg = rs + " run on the in-core exact-ERI path only (n_ao <= 116); larger fragments would need a direct K_lr, which is not built"; return MQC_HIP_ERR_UNSUPPORTED; }
+        if (o.want_gradient) { msg = "analytic gradients of " + rs + " are not built (energies only)"; return MQC_HIP_ERR_UNSUPPORTED; }
     }
     if (o.want_gradient) {
-        XcSpec tg; std::string eg;
-        parse_functional(o.functional, tg, eg);
-        if (tg.gga == 2) { msg = "analytic gradients of meta-GGA functionals are not built (energies only)"; return MQC_HIP_ERR_UNSUPPORTED; }
+        if (p.xc.gga == 2) { msg = "analytic gradients of meta-GGA functionals are not built (energies only)"; return MQC_HIP_ERR_UNSUPPORTED; }
         if (topo.lmax > 3) { msg = "analytic gradients cover s, p, d and f shells"; return MQC_HIP_ERR_UNSUPPORTED; }
     }
-    // restricted iff multiplicity 1, even electron count and not forced (mqc_cuest_driver.f90:127)
-    const bool uhf = o.unrestricted || topo.multiplicity != 1 || (topo.nelec % 2) != 0;
-    if (uhf) {
+    if (p.uhf) {
         // the occupation checks of run_libcint_uhf (mqc_libcint_rhf.f90:768-793)
         if (topo.multiplicity < 1) { msg = "UHF: multiplicity must be at least 1"; return MQC_HIP_ERR_VALIDATION; }
         if ((topo.nelec + topo.multiplicity - 1) % 2 != 0) { msg = "UHF: an electron count and multiplicity that cannot be paired -- their parities disagree"; return MQC_HIP_ERR_VALIDATION; }
-        const int na = (topo.nelec + topo.multiplicity - 1) / 2, nb = topo.nelec - na;
-        if (nb < 0 || na < 0) { msg = "UHF: multiplicity asks for more unpaired electrons than the system has"; return MQC_HIP_ERR_VALIDATION; }
-        if (na < 1) { msg = "UHF: no electrons to place"; return MQC_HIP_ERR_VALIDATION; }
-        {
-            XcSpec tu; std::string eu;
-            parse_functional(o.functional, tu, eu);
-            if (tu.ncomp > 0 && topo.nao > 140) { msg = "unrestricted Kohn-Sham is available up to n_ao = 140"; return MQC_HIP_ERR_UNSUPPORTED; }
-        }
+        if (p.nbeta < 0 || p.nalpha < 0) { msg = "UHF: multiplicity asks for more unpaired electrons than the system has"; return MQC_HIP_ERR_VALIDATION; }
+        if (p.nalpha < 1) { msg = "UHF: no electrons to place"; return MQC_HIP_ERR_VALIDATION; }
+        if (p.xc.ncomp > 0 && topo.nao > 140) { msg = "unrestricted Kohn-Sham is available up to n_ao = 140"; return MQC_HIP_ERR_UNSUPPORTED; }
     } else if (topo.nelec < 2) { msg = "RHF: no electrons to place"; return MQC_HIP_ERR_VALIDATION; }
     if (o.guess < MQC_HIP_GUESS_AUTO || o.guess > MQC_HIP_GUESS_SAC) { msg = "unknown initial guess"; return MQC_HIP_ERR_VALIDATION; }
-    if (o.guess == MQC_HIP_GUESS_SAC && uhf) { msg = "the SAC guess (free atoms' own spin densities) is available for restricted runs; unrestricted runs take sad, gwh or core"; return MQC_HIP_ERR_UNSUPPORTED; }
+    if (o.guess == MQC_HIP_GUESS_SAC && p.uhf) { msg = "the SAC guess (free atoms' own spin densities) is available for restricted runs; unrestricted runs take sad, gwh or core"; return MQC_HIP_ERR_UNSUPPORTED; }
     if (o.max_iter < 1) { msg = "max_iter must be positive"; return MQC_HIP_ERR_VALIDATION; }
     if (o.use_diis && (o.diis_size < 0 || o.diis_size > DIIS_MAX)) { msg = "diis_size must be within 0..8"; return MQC_HIP_ERR_VALIDATION; }
     if (!o.density_fitting && o.eri_mode == MQC_HIP_ERI_INCORE && !incore_supported(topo.nao)) { msg = "fragment too large for the in-core exact-ERI path (n_ao <= 116); use eri_mode auto/direct or density fitting"; return MQC_HIP_ERR_UNSUPPORTED; }
-    if (topo.lmax > CLASS_LMAX) {
-        const bool direct = !o.density_fitting && (o.eri_mode == MQC_HIP_ERI_DIRECT || (o.eri_mode == MQC_HIP_ERI_AUTO && !incore_supported(topo.nao)));
-        (void)direct;       // f classes are digested by the LDS kernel: the direct build covers them
-        if (o.density_fitting && topo.lmax > 3) { msg = "density fitting covers orbital shells up to f"; return MQC_HIP_ERR_UNSUPPORTED; }
-    }
+    // f classes are digested by the LDS kernel: the exact-ERI paths cover them
+    if (o.density_fitting && topo.lmax > 3) { msg = "density fitting covers orbital shells up to f"; return MQC_HIP_ERR_UNSUPPORTED; }
     // n_ao <= 140: the Fock matrix is diagonalised in LDS; up to 256 it is rotated in global memory (L2), exact-ERI
     // direct path and the quadrature's z-split; density fitting keeps the 140 limit (its J/K kernels tile n in LDS)
     if (topo.nao > 256) { msg = "fragment too large for the eigen-solver (n_ao <= 256)"; return MQC_HIP_ERR_UNSUPPORTED; }
@@ -320,10 +241,42 @@ static int validate_options(const mqc_hip_scf_options_t& o, const Topology& topo
     return MQC_HIP_OK;
 }
 
+// The decisions of a batch call of ntot fragments that do not wait for the grid: functional, spin, two-electron path,
+// Schwarz thresholds; then the refusals of validate_options
+static int plan_batch(const mqc_hip_scf_options_t& o, const Topology& topo, int ntot, BatchPlan& p, std::string& msg)
+{
+    p.n = topo.nao; p.npair = topo.npair; p.natoms = topo.natoms;
+    if (!parse_functional(o.functional, p.xc, msg)) return MQC_HIP_ERR_UNSUPPORTED;
+    p.rsh = p.xc.omega > 0.0;
+    // restricted iff multiplicity 1, even electron count and not forced (mqc_cuest_driver.f90:127)
+    p.uhf = o.unrestricted || topo.multiplicity != 1 || (topo.nelec % 2) != 0;
+    p.nalpha = p.uhf ? (topo.nelec + topo.multiplicity - 1) / 2 : topo.nelec / 2;
+    p.nbeta = p.uhf ? topo.nelec - p.nalpha : topo.nelec / 2;
+    p.nocc = p.nalpha;
+    // exact-ERI path selection (mqc_libcint_bridge.f90:819-892 with an HBM budget instead of 2 GB of host memory)
+    p.two_e = o.density_fitting ? TWO_E_DF
+            : (o.eri_mode == MQC_HIP_ERI_DIRECT || (o.eri_mode == MQC_HIP_ERI_AUTO && !incore_supported(topo.nao))) ? TWO_E_DIRECT : TWO_E_INCORE;
+    p.direct_tol = o.schwarz_tol > 0.0 ? o.schwarz_tol : 1.0e-11;   // mqc_libcint_direct.f90:61
+    // Schwarz screening of the in-core build pays for itself through the quartets it drops; for a handful of fragments
+    // the bounds (one thread per shell pair walking its primitive quartets: 1.6 ms for one cc-pVDZ water dimer) cost
+    // more than the screened quartets save, and the unscreened tensor needs no zero fill.  Energies move by < 1e-11 Eh
+    // either way (that is what the threshold means); MQC_HIP_SCHWARZ_MIN_FRAGMENTS=0 screens always.
+    static const int schwarz_min = [] { const char* e = std::getenv("MQC_HIP_SCHWARZ_MIN_FRAGMENTS"); return e ? std::atoi(e) : 9; }();
+    p.stol = (o.schwarz_tol > 0.0 && ntot >= schwarz_min) ? o.schwarz_tol : 0.0;
+    return validate_options(o, topo, p, msg);
+}
+
 static void fill_error(mqc_hip_scf_result_t* r, const std::string& msg)
 {
     r->has_error = 1;
     std::snprintf(r->message, sizeof(r->message), "%s", msg.c_str());
+}
+
+// a batch that does not run: every fragment carries the reason
+static int refuse(const std::vector<mqc_hip_scf_result_t*>& results, int code, const std::string& msg)
+{
+    for (auto* r : results) { fill_error(r, msg); r->scf_status = MQC_HIP_SCF_NOT_RUN; }
+    return fail(code, msg);
 }
 
 // Starting density of the superposed-atom guesses (one per topology: it does not depend on the geometry) and, for
@@ -335,133 +288,596 @@ struct AtomicGuess {
 };
 static DevicePool g_guess_pool[2];
 
-int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology* aux, const std::vector<const double*>& xyz_in,
-              const mqc_hip_scf_options_t& opts, std::vector<mqc_hip_scf_result_t*>& results_in, int lane,
-              const AtomicGuess* atomic_guess = nullptr, const std::vector<const mqc_hip_molecule_t*>* mols_in = nullptr)
+// What the stages of one batch call share besides the plan: the inputs, ordered by compactness, the device topology
+// and grid, and the statistics, gathered locally (two lanes may run at once) and merged at the end
+struct Batch {
+    const Topology& topo;
+    const Topology* aux;
+    const mqc_hip_scf_options_t& opts;
+    const AtomicGuess* guess;
+    std::vector<const double*> xyz;
+    std::vector<mqc_hip_scf_result_t*> results;
+    std::vector<const mqc_hip_molecule_t*> mols;     // embedded groups only (point charges, h_extra)
+    TopologyDev td{}, tdx{};
+    GridDev grid;
+    Stats stats;
+};
+
+struct Job {
+    int start = 0, nf = 0;
+    BatchView bv{};
+    std::vector<double> hx, hpc;
+};
+
+// ---- exchange-correlation: per-element grid templates and the per-topology point list
+static int upload_grid(mqc_hip_context* ctx, Batch& b, DevicePool& pool, hipStream_t s)
 {
-    // statistics are gathered locally and merged at the end (two lanes may run at once)
-    struct StatsCtx { Stats stats; } local;
-    StatsCtx* const sx = &local;
+    const Topology& topo = b.topo;
+    std::map<int, std::pair<int, int>> tmpl_of_z;     // Z -> (offset, count) in the packed template arrays
+    std::vector<double> txyz, tw, sb(topo.natoms);
+    std::vector<int> pt_atom, pt_tmpl;
+    for (int a = 0; a < topo.natoms; ++a) {
+        // a ghost centre enters the grid builder with Z = 0 (numbers = nint(mol%charges), mqc_libcint_xc.F90:181-183):
+        // period-1 sizes, xi(0) = 1, Bragg radius(0) = 2 Angstrom -- it still owns grid points
+        const int z = (topo.zeff[a] == 0.0) ? 0 : topo.Z[a];
+        sb[a] = std::sqrt(bragg_radius_bohr(z)) + 1e-200;
+        if (!tmpl_of_z.count(z)) {
+            std::vector<double> x, w; std::string e;
+            if (!build_atom_template(z, b.opts.grid_level, b.opts.radial_points, b.opts.angular_points, x, w, e))
+                return refuse(b.results, MQC_HIP_ERR_UNSUPPORTED, e);
+            tmpl_of_z[z] = {(int)tw.size(), (int)w.size()};
+            txyz.insert(txyz.end(), x.begin(), x.end());
+            tw.insert(tw.end(), w.begin(), w.end());
+        }
+        const auto oc = tmpl_of_z[z];
+        for (int k = 0; k < oc.second; ++k) { pt_atom.push_back(a); pt_tmpl.push_back(oc.first + k); }
+    }
+    GridDev& grid = b.grid;
+    grid.npts = (int)pt_atom.size();
+    const size_t b_int = (sizeof(int) * pt_atom.size() + 255) & ~size_t(255);
+    const size_t b_xyz = (sizeof(double) * txyz.size() + 255) & ~size_t(255);
+    const size_t b_w = (sizeof(double) * tw.size() + 255) & ~size_t(255);
+    const size_t b_sb = (sizeof(double) * sb.size() + 255) & ~size_t(255);
+    char* gb = (char*)pool.ensure(2 * b_int + b_xyz + b_w + b_sb + 1024);
+    if (!gb) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (grid templates)");
+    int* d_pa = (int*)gb; int* d_pt = (int*)(gb + b_int);
+    double* d_x = (double*)(gb + 2 * b_int); double* d_w = (double*)(gb + 2 * b_int + b_xyz);
+    double* d_sb = (double*)(gb + 2 * b_int + b_xyz + b_w);
+    HIP_CHECK_RET(hipMemcpyAsync(d_pa, pt_atom.data(), sizeof(int) * pt_atom.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemcpyAsync(d_pt, pt_tmpl.data(), sizeof(int) * pt_tmpl.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemcpyAsync(d_x, txyz.data(), sizeof(double) * txyz.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemcpyAsync(d_w, tw.data(), sizeof(double) * tw.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemcpyAsync(d_sb, sb.data(), sizeof(double) * sb.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));     // the host vectors go out of scope
+    grid.pt_atom = d_pa; grid.pt_tmpl = d_pt; grid.tmpl_xyz = d_x; grid.tmpl_w = d_w; grid.sqrt_bragg = d_sb;
+    return MQC_HIP_OK;
+}
+
+// J and K of the density in bv by the batch's two-electron path.  In the SCF loop (in_loop) the fragments that are
+// done are skipped and a restricted direct build may go incrementally; an unrestricted view always builds in full.
+static void jk_one(const BatchPlan& plan, const Topology& topo, const BatchView& bv, bool in_loop, hipStream_t s)
+{
+    if (plan.two_e == TWO_E_DF) launch_df_jk(bv, in_loop, s);
+    else if (plan.two_e == TWO_E_INCORE) launch_jk_incore(bv, in_loop, s);
+    else if (in_loop) launch_jk_direct_incremental(bv, topo, plan.direct_tol, true, s);     // restricted: G_ref += G(D - D_ref)
+    else launch_jk_direct(bv, topo, plan.direct_tol, false, s);
+}
+
+// J/K of one SCF iteration: the alpha (or closed-shell) density, the beta density of an unrestricted run, then the
+// long-range exchange of a range-separated hybrid folded into K
+static int build_jk(const BatchPlan& plan, const Topology& topo, const BatchView& bv, hipStream_t s)
+{
+    jk_one(plan, topo, bv, true, s);
+    if (plan.uhf) {
+        BatchView vb = bv;
+        vb.D = bv.Db; vb.J = bv.Jb; vb.K = bv.Kb;
+        if (plan.two_e == TWO_E_DF) {
+            // unrestricted density fitting, as run_uks_scf of the cuEST path (mqc_cuest_scf.f90:637-1009): J from each
+            // spin density, K_s = sum_P (B_P C_s)(B_P C_s)^T; the kernels return the closed-shell 2 W W^T
+            const size_t tot = (size_t)bv.nfrag * plan.n * plan.n;
+            launch_scale(bv.K, tot, 0.5, s);
+            if (plan.nbeta > 0) {
+                vb.C = bv.Cb; vb.nocc = plan.nbeta;
+                launch_df_jk(vb, true, s);
+                launch_scale(bv.Kb, tot, 0.5, s);
+            } else {
+                HIP_CHECK_RET(hipMemsetAsync(bv.Jb, 0, sizeof(double) * tot, s));
+                HIP_CHECK_RET(hipMemsetAsync(bv.Kb, 0, sizeof(double) * tot, s));
+            }
+        } else jk_one(plan, topo, vb, true, s);      // the same stream over the tensor, or the direct integrals formed again
+    }
+    if (plan.rsh) {
+        // K_lr of each spin density from the long-range tensor (its J is not used), folded into K
+        BatchView vl = bv;
+        vl.eri = bv.eri_lr; vl.J = bv.Jlr; vl.K = bv.Klr; vl.jk_loaded = nullptr;
+        launch_jk_incore(vl, true, s);
+        launch_exchange_fold(bv, bv.K, bv.Klr, plan.xc.exx, plan.xc.exx_lr, s);
+        if (plan.uhf) {
+            vl.D = bv.Db; vl.K = bv.Klrb;
+            launch_jk_incore(vl, true, s);
+            launch_exchange_fold(bv, bv.Kb, bv.Klrb, plan.xc.exx, plan.xc.exx_lr, s);
+        }
+    }
+    return MQC_HIP_OK;
+}
+
+// ---- stage 1 of a chunk: everything up to (and including) the guess, enqueued on the slot's stream
+static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const Slot& sl, Job& job)
+{
+    const Topology& topo = b.topo;
+    const mqc_hip_scf_options_t& opts = b.opts;
+    const int nf = job.nf, n = plan.n;
+    hipStream_t s = sl.s;
+    const double t0 = now_s();
+    BatchView& bv = job.bv;
+    // range-separated hybrids: K is folded to exx K + exx_lr K_lr before the step, which then takes all of it
+    bv.nalpha = plan.nalpha; bv.nbeta = plan.nbeta; bv.nocc = plan.nocc; bv.aux = b.tdx;
+    bv.exx = plan.rsh ? 1.0 : plan.xc.exx; bv.e_tol = opts.energy_tol; bv.d_tol = opts.density_tol;
+    bv.max_iter = opts.max_iter; bv.diis_size = opts.use_diis ? opts.diis_size : 0;
+    bv.xc = plan.xc; bv.grid = b.grid;
+    int rc = carve_slot(ctx, sl, plan, b.td, nf, bv);
+    if (rc != MQC_HIP_OK) return rc;
+    if (plan.two_e == TWO_E_DF) HIP_CHECK_RET(hipMemsetAsync(bv.scal, 0, sizeof(double) * (size_t)nf * 8, s));
+    job.hx.resize((size_t)nf * topo.natoms * 3);
+    for (int f = 0; f < nf; ++f) std::memcpy(&job.hx[(size_t)f * topo.natoms * 3], b.xyz[job.start + f], sizeof(double) * topo.natoms * 3);
+    HIP_CHECK_RET(hipMemcpyAsync(bv.xyz, job.hx.data(), sizeof(double) * job.hx.size(), hipMemcpyHostToDevice, s));
+    if (plan.npc > 0) {
+        // layout [charge][x, y, z, q][fragment], FRAGMENT FASTEST: the lanes of a wave are consecutive fragments, so a
+        // wave reads a charge's component as one contiguous 512-byte line -- with [fragment][charge][4] every lane
+        // streamed its own 49 KB array and a wave-load touched 64 cache lines (int1e: 40 % of a 512-fragment FMO run)
+        job.hpc.resize((size_t)nf * plan.npc * 4);
+        for (int f = 0; f < nf; ++f) {
+            const mqc_hip_molecule_t* m = b.mols[job.start + f];
+            for (int g = 0; g < plan.npc; ++g) {
+                double* q = &job.hpc[(size_t)g * 4 * nf + f];
+                q[0] = m->point_charge_xyz[3 * g]; q[(size_t)nf] = m->point_charge_xyz[3 * g + 1]; q[2 * (size_t)nf] = m->point_charge_xyz[3 * g + 2];
+                q[3 * (size_t)nf] = m->point_charges[g];
+            }
+        }
+        HIP_CHECK_RET(hipMemcpyAsync((void*)bv.pc, job.hpc.data(), sizeof(double) * job.hpc.size(), hipMemcpyHostToDevice, s));
+    }
+    if (plan.hx)
+        for (int f = 0; f < nf; ++f)
+            HIP_CHECK_RET(hipMemcpyAsync((void*)(bv.Hx + (size_t)f * n * n), b.mols[job.start + f]->h_extra, sizeof(double) * n * n, hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemsetAsync(bv.istate, 0, sizeof(int) * (size_t)nf * 4, s));
+    HIP_CHECK_RET(hipMemsetAsync(bv.eri_count, 0, sizeof(unsigned long long), s));
+    const double t1 = now_s();
+    b.stats.t_setup += t1 - t0;
+
+    const bool incore = plan.two_e == TWO_E_INCORE;
+    if (incore) launch_eri_bounds(bv, topo, plan.stol, s);     // screened build: bounds run next to the 1e stage
+    // The one-electron stage, the orthogonaliser and the starting guess need the geometry (S, H) only and are
+    // latency-bound (six class launches; one workgroup per fragment, Jacobi sweeps): they run on a side stream next
+    // to the compute-bound two-electron stage, which does not wait for them (0.7 ms of a single-fragment call)
+    hipStream_t so = ctx->side[sl.id & 1][2];
+    HIP_CHECK_RET(hipEventRecord(ctx->evo[sl.id & 1][0], s));             // uploads and resets above are in
+    HIP_CHECK_RET(hipStreamWaitEvent(so, ctx->evo[sl.id & 1][0], 0));
+    launch_int1e(bv, topo, so);
+    // block-sharing plan and class lists of the integral stage: host work that depends on the geometry only, done
+    // here while the bounds and one-electron kernels run
+    if (incore) eri_plan_lists(bv, topo, s, job.hx.data());
+    if ((rc = stage_check("int1e")) != MQC_HIP_OK) return rc;
+    launch_orthogonalizer(bv, so);
+    if ((rc = stage_check("orthogonalizer")) != MQC_HIP_OK) return rc;
+    if (!b.guess) launch_guess(bv, opts.guess == MQC_HIP_GUESS_CORE ? MQC_HIP_GUESS_CORE : MQC_HIP_GUESS_GWH, so);
+    if ((rc = stage_check("guess")) != MQC_HIP_OK) return rc;
+    HIP_CHECK_RET(hipEventRecord(ctx->evo[sl.id & 1][1], so));
+    if (plan.xc.ncomp > 0) { launch_becke_weights(bv, s); if (bv.grid.rad) launch_xc_radial_cache(bv, s); }
+    if ((rc = stage_check("grid weights")) != MQC_HIP_OK) return rc;
+    const double t2 = now_s();
+    b.stats.t_int1e += t2 - t1;
+
+    HIP_CHECK_RET(hipEventRecord(sl.q0, s));
+    if (plan.two_e == TWO_E_DF) launch_df_build(bv, topo, *b.aux, s);
+    else if (plan.two_e == TWO_E_DIRECT) launch_direct_setup(bv, topo, s);
+    else {
+        launch_eri(bv, topo, plan.stol, s, job.hx.data());
+        if (plan.rsh) {
+            // the long-range tensor: same lists, screening (the Coulomb bounds bound it) and block sharing
+            BatchView vl = bv;
+            vl.eri = bv.eri_lr;
+            launch_eri(vl, topo, plan.stol, s, job.hx.data(), plan.xc.omega);
+        }
+        // the bounds of a screened build tell the J/K kernel which pair rows are all zeros (triangular tensor only)
+        if (plan.stol > 0.0 && bv.eri_tri) eri_schwarz_view(bv.slot, &bv.jk_q, &bv.jk_qthresh);
+    }
+    HIP_CHECK_RET(hipEventRecord(sl.q1, s));
+    if ((rc = stage_check("two-electron setup")) != MQC_HIP_OK) return rc;
+    b.stats.eri_quartets += topo.n_quartets * nf;
+    HIP_CHECK_RET(hipStreamWaitEvent(s, ctx->evo[sl.id & 1][1], 0));      // join: X, C, D of the guess are ready
+    if (b.guess) {
+        // superposed atoms (build_restricted_guess / atomic_guess_fock, mqc_libcint_atomic_guess.f90:168-212,
+        // mqc_libcint_rhf.f90:1382-1411): the same block-diagonal density in every fragment of the topology, its
+        // Hartree-Fock Fock matrix from the two-electron stage just built (full exchange), then the usual
+        // diagonalisation and occupation -- both spins of an unrestricted run start from it
+        const size_t nn = (size_t)n * n;
+        double* d0 = (double*)g_guess_pool[sl.id & 1].ensure(sizeof(double) * 2 * nn + 256);
+        if (!d0) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (guess density)");
+        HIP_CHECK_RET(hipMemcpyAsync(d0, b.guess->D0.data(), sizeof(double) * nn, hipMemcpyHostToDevice, s));
+        launch_broadcast(bv.D, d0, nn, nf, s);
+        BatchView vg = bv;
+        vg.exx = 1.0; vg.uhf = 0;
+        if (plan.two_e == TWO_E_DF) {
+            HIP_CHECK_RET(hipMemcpyAsync(d0 + nn, b.guess->Cp.data(), sizeof(double) * nn, hipMemcpyHostToDevice, s));
+            launch_broadcast(bv.C, d0 + nn, nn, nf, s);
+            vg.nocc = b.guess->nmodes;
+        }
+        jk_one(plan, topo, vg, false, s);
+        launch_guess(bv, MQC_HIP_GUESS_SAD, s);
+        if ((rc = stage_check("atomic guess")) != MQC_HIP_OK) return rc;
+    }
+    b.stats.t_eri += now_s() - t2;      // host time to enqueue; the kernels are timed by q0/q1
+    return MQC_HIP_OK;
+}
+
+// ---- stage 2: the SCF loop, one int back per iteration (or per block of iterations)
+static int scf_loop(const BatchPlan& plan, Batch& b, const Slot& sl, Job& job)
+{
+    const int nf = job.nf, n = plan.n;
+    const double np = (double)plan.npair;
+    hipStream_t s = sl.s;
+    BatchView& bv = job.bv;
+    Stats& st = b.stats;
+    const bool df = plan.two_e == TWO_E_DF, ks = plan.xc.ncomp > 0;
+    int rc;
+    const double t3 = now_s();
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    if ((rc = stage_check("integrals")) != MQC_HIP_OK) return rc;
+    {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, sl.q0, sl.q1);
+        st.eri_kernel_seconds += ms * 1e-3;
+    }
+    int remaining = nf;
+    int guard = 0;
+    double tri_doubles_per_fragment = -1.0;      // read back after the first J/K launch of the chunk
+    // Small batches are latency-bound: the host round trip after every iteration (one int back, ~50 us) costs as
+    // much as the kernels.  They run BLOCKS of iterations between two reads of the counter -- finished fragments
+    // drop out of every kernel by themselves (state machine), so an iteration enqueued past convergence is three
+    // empty launches.  Large batches keep one read per iteration (MQC_HIP_SCF_SYNC_BLOCK overrides: 1 = always).
+    static const int sync_block_env = [] { const char* e = std::getenv("MQC_HIP_SCF_SYNC_BLOCK"); return e ? std::atoi(e) : 0; }();
+    static const int block_max_frag = [] { const char* e = std::getenv("MQC_HIP_SCF_BLOCK_MAX_FRAGMENTS"); return e ? std::atoi(e) : 256; }();
+    const bool blocked = sync_block_env != 1 && nf <= block_max_frag;
+    const int max_guard = b.opts.max_iter + 2;
+    int blocks_done = 0;
+    while (remaining > 0 && guard < max_guard) {
+        int block_len = 1;
+        if (blocked) block_len = sync_block_env > 1 ? sync_block_env : (blocks_done == 0 ? 8 : 4);
+        if (block_len > max_guard - guard) block_len = max_guard - guard;
+        ++blocks_done;
+        for (int bi = 0; bi < block_len; ++bi) {
+            HIP_CHECK_RET(hipEventRecord(sl.e0, s));
+            if ((rc = build_jk(plan, b.topo, bv, s)) != MQC_HIP_OK) return rc;
+            HIP_CHECK_RET(hipEventRecord(sl.e1, s));
+            if (guard == 0 && (rc = stage_check("J/K build")) != MQC_HIP_OK) return rc;
+            if (ks) {
+                HIP_CHECK_RET(hipEventRecord(sl.e2, s));
+                launch_xc(bv, true, s);
+                HIP_CHECK_RET(hipEventRecord(sl.e3, s));
+            }
+            HIP_CHECK_RET(hipEventRecord(sl.s0, s));
+            launch_scf_step(bv, s);
+            HIP_CHECK_RET(hipEventRecord(sl.s1, s));
+            if (bi + 1 < block_len) { ++guard; continue; }
+            HIP_CHECK_RET(hipMemcpyAsync(sl.h_counter, bv.counters, sizeof(int), hipMemcpyDeviceToHost, s));
+            HIP_CHECK_RET(hipStreamSynchronize(s));
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, sl.s0, sl.s1);
+            st.scf_step_seconds += ms * 1e-3 * block_len;
+            (void)hipEventElapsedTime(&ms, sl.e0, sl.e1);
+            if (df) {
+                st.df_bytes += (double)remaining * 8.0 * (double)plan.naux * (double)n * (double)n * block_len;
+                st.df_flops += (double)remaining * 4.0 * (double)plan.naux * (double)n * (double)n * (1.0 + (plan.xc.exx != 0.0 ? (double)plan.nocc : 0.0)) * block_len;
+            }
+            // density fitting: the J/K kernel reads the fitted tensor once, and it is stored packed [naux][npair] -- about
+            // half of SURVEY 8d's 8 n^2 A (df_bytes keeps that figure; fock_bytes is what the kernel really streams)
+            // in-core: the tensor as stored -- the square, or its lower triangle (BatchView::eri_tri) -- once per spin density;
+            // the triangular kernel skips rows the Schwarz bounds prove zero and reports the chunks it did read
+            if (bv.eri_tri && bv.jk_loaded && tri_doubles_per_fragment < 0.0) {
+                std::vector<int> ld(nf);
+                if (hipMemcpy(ld.data(), bv.jk_loaded, sizeof(int) * (size_t)nf, hipMemcpyDeviceToHost) == hipSuccess) {
+                    double sum = 0.0;
+                    for (int v : ld) sum += v;
+                    tri_doubles_per_fragment = 128.0 * sum / (double)nf;
+                } else tri_doubles_per_fragment = (double)bv.eri_stride;
+            }
+            const double tensor_doubles = (bv.eri_tri && tri_doubles_per_fragment >= 0.0) ? tri_doubles_per_fragment
+                                                                                         : (bv.eri_stride ? (double)bv.eri_stride : np * np);
+            const double launch_bytes = df ? (double)remaining * (double)plan.naux * np * 8.0
+                                           : (double)remaining * tensor_doubles * 8.0 * (plan.uhf ? 2.0 : 1.0);
+            st.fock_kernel_seconds += ms * 1e-3 * block_len;
+            st.fock_bytes += launch_bytes * block_len;
+            st.fock_launches += block_len;
+            if (launch_bytes >= 1073741824.0) {
+                st.fock_big_launches += 1; st.fock_big_seconds += ms * 1e-3; st.fock_big_bytes += launch_bytes;
+            }
+            if (ks) {
+                float mx = 0.f;
+                (void)hipEventElapsedTime(&mx, sl.e2, sl.e3);
+                st.xc_kernel_seconds += mx * 1e-3 * block_len;
+                st.xc_points += (double)remaining * plan.npts * block_len;
+                st.xc_flops += (double)remaining * plan.npts * (plan.xc.gga ? 8.0 : 4.0) * (double)n * (double)n * block_len;
+            }
+            remaining = sl.h_counter[0];
+            ++guard;
+        }
+    }
+    if ((rc = stage_check("SCF loop")) != MQC_HIP_OK) return rc;
+    st.t_fock += now_s() - t3;
+    return MQC_HIP_OK;
+}
+
+// + nuclear repulsion: dE_nuc/dR_A = -sum_B Z_A Z_B (R_A - R_B)/|R_AB|^3 (ghosts carry no charge)
+static void nuclear_gradient(const Topology& topo, const double* x, const double* g_elec, double* g)
+{
+    for (int a = 0; a < topo.natoms; ++a) {
+        double g3[3] = {g_elec[3 * a], g_elec[3 * a + 1], g_elec[3 * a + 2]};
+        for (int b = 0; b < topo.natoms; ++b) {
+            if (b == a || topo.zeff[a] == 0.0 || topo.zeff[b] == 0.0) continue;
+            const double dx = x[3 * a] - x[3 * b], dy = x[3 * a + 1] - x[3 * b + 1], dz = x[3 * a + 2] - x[3 * b + 2];
+            const double r2 = dx * dx + dy * dy + dz * dz, r3 = r2 * std::sqrt(r2);
+            const double zz = topo.zeff[a] * topo.zeff[b] / r3;
+            g3[0] -= zz * dx; g3[1] -= zz * dy; g3[2] -= zz * dz;
+        }
+        g[3 * a] = g3[0]; g[3 * a + 1] = g3[1]; g[3 * a + 2] = g3[2];
+    }
+}
+
+// <S^2> = S_z (S_z + 1) + n_beta - sum_ij |<a_i|S|b_j>|^2  (spin_contamination, mqc_libcint_rhf.f90)
+static double s_squared(int n, int nalpha, int nbeta, const double* Ca, const double* Cb, const double* S)
+{
+    double ov2 = 0.0;
+    std::vector<double> SCb((size_t)n * std::max(nbeta, 1));
+    for (int mu = 0; mu < n; ++mu)
+        for (int j = 0; j < nbeta; ++j) {
+            double t = 0.0;
+            for (int nu = 0; nu < n; ++nu) t += S[(size_t)mu * n + nu] * Cb[(size_t)nu * n + j];
+            SCb[(size_t)mu * nbeta + j] = t;
+        }
+    for (int i = 0; i < nalpha; ++i)
+        for (int j = 0; j < nbeta; ++j) {
+            double t = 0.0;
+            for (int mu = 0; mu < n; ++mu) t += Ca[(size_t)mu * n + i] * SCb[(size_t)mu * nbeta + j];
+            ov2 += t * t;
+        }
+    const double sz = 0.5 * (nalpha - nbeta);
+    return sz * (sz + 1.0) + nbeta - ov2;
+}
+
+// mu = sum_A Z_A (R_A - O) - [tr(D r) - O tr(D S)], O = centre of nuclear charge, tr(D S) = N_electrons
+// (system_compute_dipole, mqc_cuest_integrals.f90:1443-1521); dr = tr(D x), tr(D y), tr(D z) about the origin
+static void dipole(const Topology& topo, const double* x, const double* dr, double* mu_out)
+{
+    double ztot = 0.0, o[3] = {0, 0, 0}, mu[3] = {0, 0, 0};
+    for (int a = 0; a < topo.natoms; ++a) { ztot += topo.zeff[a]; for (int c = 0; c < 3; ++c) o[c] += topo.zeff[a] * x[3 * a + c]; }
+    if (ztot > 0.0) for (int c = 0; c < 3; ++c) o[c] /= ztot; else for (int c = 0; c < 3; ++c) o[c] = 0.0;
+    for (int a = 0; a < topo.natoms; ++a) for (int c = 0; c < 3; ++c) mu[c] += topo.zeff[a] * (x[3 * a + c] - o[c]);
+    for (int c = 0; c < 3; ++c) mu_out[c] = mu[c] - (dr[c] - o[c] * (double)topo.nelec);
+}
+
+// what the embedded callers read besides the energy: tr(D u), u itself (U != nullptr), Mulliken populations
+// (inner_scf / fragment_charges, mqc_libcint_fmo.f90:1992-2021)
+static void embedding_and_mulliken(const Topology& topo, const double* D, const double* U, const double* S, mqc_hip_scf_result_t* r)
+{
+    const int n = topo.nao;
+    const size_t nn = (size_t)n * n;
+    if (U) {
+        double e = 0.0;
+        for (size_t k = 0; k < nn; ++k) e += D[k] * U[k];
+        r->e_embedding = e;
+        if (r->embedding_matrix) std::memcpy(r->embedding_matrix, U, sizeof(double) * nn);
+    }
+    if (r->mulliken_charges) {
+        for (int a = 0; a < topo.natoms; ++a) r->mulliken_charges[a] = topo.zeff[a];
+        for (size_t sh = 0; sh < topo.shells.size(); ++sh) {
+            const int a = topo.shells[sh].atom, o0 = topo.shells[sh].aoff, nf_sh = 2 * topo.shells[sh].l + 1;
+            for (int mu = o0; mu < o0 + nf_sh; ++mu) {
+                double pop = 0.0;
+                for (int nu = 0; nu < n; ++nu) pop += D[(size_t)mu * n + nu] * S[(size_t)nu * n + mu];
+                r->mulliken_charges[a] -= pop;
+            }
+        }
+    }
+}
+
+// what a chunk's results are made of, read back once after its SCF loop
+struct ChunkOut {
+    std::vector<double> scal, eps, epsb, dip, grad;
+    std::vector<double> D, U, S;      // total density, embedding operator, overlap: only where a caller reads them
+    std::vector<int> ist;
+};
+
+// the result record of fragment f of the chunk
+static int write_result(const BatchPlan& plan, Batch& b, const Job& job, const ChunkOut& o, int f, hipStream_t s)
+{
+    const Topology& topo = b.topo;
+    const int n = plan.n, nocc = plan.nocc;
+    const size_t nn = (size_t)n * n;
+    mqc_hip_scf_result_t* r = b.results[job.start + f];
+    const double* x = b.xyz[job.start + f];
+    const int nmo = o.ist[4 * f + 2];
+    r->n_ao = n; r->n_mo = nmo; r->n_occ = nocc;
+    if (nocc > nmo) {
+        // nmo check: more occupied orbitals than the basis supports after dropping near-null modes
+        fill_error(r, plan.uhf ? "UHF: more alpha electrons than the basis supports after near-null modes were dropped"
+                               : "RHF: more occupied orbitals than the basis supports after near-null modes were dropped");
+        r->scf_status = MQC_HIP_SCF_NOT_RUN;
+        return MQC_HIP_OK;
+    }
+    r->e_nuclear = nuclear_repulsion(topo, x);
+    r->e_electronic = o.scal[8 * f + 4];
+    r->e_total = r->e_electronic + r->e_nuclear;
+    r->e_xc = plan.xc.ncomp > 0 ? o.scal[8 * f + 5] : 0.0;
+    r->iterations = o.ist[4 * f + 1];
+    const bool conv = o.ist[4 * f + 3] != 0 && o.ist[4 * f] == ST_DONE;
+    r->scf_status = conv ? MQC_HIP_SCF_CONVERGED : MQC_HIP_SCF_NOT_CONVERGED;
+    r->homo = o.eps[(size_t)f * n + nocc - 1];
+    r->lumo = nocc < nmo ? o.eps[(size_t)f * n + nocc] : 0.0;
+    r->has_orbitals = 1;
+    r->n_alpha = plan.nalpha; r->n_beta = plan.nbeta; r->s_squared = 0.0;
+    if (b.opts.want_gradient && r->gradient) {
+        nuclear_gradient(topo, x, &o.grad[(size_t)f * topo.natoms * 3], r->gradient);
+        r->has_gradient = 1;
+    }
+    if (plan.uhf) {
+        std::vector<double> Ca(nn), Cb(nn), Sm(nn);
+        HIP_CHECK_RET(hipMemcpyAsync(Ca.data(), job.bv.C + (size_t)f * nn, sizeof(double) * nn, hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipMemcpyAsync(Cb.data(), job.bv.Cb + (size_t)f * nn, sizeof(double) * nn, hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipMemcpyAsync(Sm.data(), job.bv.S + (size_t)f * nn, sizeof(double) * nn, hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        r->s_squared = s_squared(n, plan.nalpha, plan.nbeta, Ca.data(), Cb.data(), Sm.data());
+        if (r->orbital_energies_beta) std::memcpy(r->orbital_energies_beta, &o.epsb[(size_t)f * n], sizeof(double) * nmo);
+    }
+    dipole(topo, x, &o.dip[4 * f], r->dipole);
+    r->has_dipole = 1;
+    if (r->orbital_energies) std::memcpy(r->orbital_energies, &o.eps[(size_t)f * n], sizeof(double) * nmo);
+    const bool embedded = plan.npc > 0 || plan.hx;
+    if (embedded || r->mulliken_charges)
+        embedding_and_mulliken(topo, o.D.data() + f * nn, embedded ? o.U.data() + f * nn : nullptr,
+                               r->mulliken_charges ? o.S.data() + f * nn : nullptr, r);
+    if (r->density) std::memcpy(r->density, o.D.data() + f * nn, sizeof(double) * nn);
+    r->has_error = 0; r->message[0] = '\0';
+    if (plan.two_e == TWO_E_DF && o.scal[8 * f + 7] == 1.0)
+        fill_error(r, "density fitting: the auxiliary metric (P|Q) could not be factorised or diagonalised");
+    else if (!std::isfinite(r->e_total)) fill_error(r, "SCF produced a non-finite energy");
+    else if (!conv && !b.opts.allow_crap_scf)
+        fill_error(r, "SCF did not converge in " + std::to_string(r->iterations) + " iterations");
+    b.stats.scf_iterations_total += r->iterations;
+    return MQC_HIP_OK;
+}
+
+// ---- stage 3: gradient, dipole integrals and the chunk's arrays back to the host, then the result records
+static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& job)
+{
+    const Topology& topo = b.topo;
+    const int nf = job.nf, n = plan.n;
+    const size_t tot = (size_t)nf * n * n;
+    hipStream_t s = sl.s;
+    const BatchView& bv = job.bv;
+    const double t4 = now_s();
+    ChunkOut o;
+    o.scal.resize((size_t)nf * 8); o.eps.resize((size_t)nf * n); o.dip.resize((size_t)nf * 4); o.ist.resize((size_t)nf * 4);
+    unsigned long long formed = 0;
+    // ---- analytic gradient (compute_scf_gradient, mqc_cuest_gradient.f90:91-175): device terms here, E_nuc' on the host
+    if (b.opts.want_gradient) {
+        size_t lint = topo.pairs.size() + 64;
+        for (auto& cl : topo.classes) lint += cl.quartets.size();
+        const size_t nnh = (size_t)n * n;
+        const size_t bytes = sizeof(double) * ((size_t)nf * topo.natoms * 3 + 2 * (size_t)nf * nnh + 8) + sizeof(int) * (lint + 64);
+        char* gb = (char*)g_grad_pool[sl.id & 1].ensure(bytes);
+        if (!gb) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (gradient)");
+        double* d_grad = (double*)gb;
+        double* gwork = d_grad + (((size_t)nf * topo.natoms * 3 + 7) & ~size_t(7));
+        int* glists = (int*)(gwork + 2 * (size_t)nf * nnh);
+        // above n_ao = 140 the two-electron term skips the (quartet, fragment) tasks the direct path's Schwarz bounds
+        // (still resident in this slot) prove below 1e-3 of its threshold: a derivative integral exceeds the bound of
+        // its undifferentiated quartet, and at the threshold itself the dropped tasks moved a (H2O)6 / cc-pVDZ
+        // gradient by 3.8e-9.  MQC_HIP_GRAD_SCREEN=0 forms them all (A/B switch)
+        static const bool grad_screen = [] { const char* e = std::getenv("MQC_HIP_GRAD_SCREEN"); return !(e && e[0] == '0'); }();
+        const double* gq = (grad_screen && plan.two_e == TWO_E_DIRECT && n > 140) ? direct_schwarz_view(bv.slot) : nullptr;
+        std::string gerr;
+        if (!launch_gradient(bv, topo, b.aux, d_grad, gwork, glists, lint, s, gerr, gq, 1.0e-3 * plan.direct_tol)) return fail(MQC_HIP_ERR_UNSUPPORTED, gerr);
+        o.grad.resize((size_t)nf * topo.natoms * 3);
+        HIP_CHECK_RET(hipMemcpyAsync(o.grad.data(), d_grad, sizeof(double) * o.grad.size(), hipMemcpyDeviceToHost, s));
+    }
+    launch_dipole(bv, topo, s);
+    if (plan.uhf) {
+        BatchView vb = bv;
+        vb.D = bv.Db;
+        launch_dipole(vb, topo, s, true);      // total density = D_a + D_b
+        o.epsb.resize((size_t)nf * n);
+        HIP_CHECK_RET(hipMemcpyAsync(o.epsb.data(), bv.epsb, sizeof(double) * o.epsb.size(), hipMemcpyDeviceToHost, s));
+    }
+    HIP_CHECK_RET(hipMemcpyAsync(o.dip.data(), bv.dip, sizeof(double) * o.dip.size(), hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipMemcpyAsync(&formed, bv.eri_count, sizeof(formed), hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipMemcpyAsync(o.scal.data(), bv.scal, sizeof(double) * o.scal.size(), hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipMemcpyAsync(o.eps.data(), bv.eps, sizeof(double) * o.eps.size(), hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipMemcpyAsync(o.ist.data(), bv.istate, sizeof(int) * o.ist.size(), hipMemcpyDeviceToHost, s));
+    // matrices the callers asked for (total density, embedding operator, overlap): the whole chunk in one copy each
+    // (one synchronous copy per matrix and fragment cost seconds of a 130 000-pair batch)
+    const bool embedded = plan.npc > 0 || plan.hx;
+    bool want_d = embedded, want_s = false;
+    for (int f = 0; f < nf; ++f) {
+        const mqc_hip_scf_result_t* r = b.results[job.start + f];
+        if (r->mulliken_charges) { want_d = true; want_s = true; }
+        if (r->density) want_d = true;
+    }
+    auto fetch = [&](std::vector<double>& h, const double* d) {
+        h.resize(tot);
+        return hipMemcpyAsync(h.data(), d, sizeof(double) * tot, hipMemcpyDeviceToHost, s);
+    };
+    if (want_d) HIP_CHECK_RET(fetch(o.D, bv.D));
+    if (embedded) HIP_CHECK_RET(fetch(o.U, bv.U));
+    if (want_s) HIP_CHECK_RET(fetch(o.S, bv.S));
+    if (want_d && plan.uhf) {
+        std::vector<double> db;
+        HIP_CHECK_RET(fetch(db, bv.Db));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        for (size_t k = 0; k < tot; ++k) o.D[k] += db[k];          // total density = alpha + beta
+    }
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    b.stats.eri_survivors += (int64_t)formed;
+    for (int f = 0; f < nf; ++f) {
+        const int rc = write_result(plan, b, job, o, f, s);
+        if (rc != MQC_HIP_OK) return rc;
+    }
+    b.stats.t_scf_step += now_s() - t4;
+    return MQC_HIP_OK;
+}
+
+// lane < 0: the batch owns both slots (chunks alternate, next chunk prepared ahead); lane 0/1: it runs on that
+// slot only, so that two topology groups can be driven by two host threads at once
+static int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology* aux, const std::vector<const double*>& xyz_in,
+                     const mqc_hip_scf_options_t& opts, const std::vector<mqc_hip_scf_result_t*>& results_in, int lane,
+                     const AtomicGuess* atomic_guess, const std::vector<const mqc_hip_molecule_t*>& mols_in)
+{
     const bool second = lane == 1;
     hipStream_t const lane_stream = second ? ctx->stream2 : ctx->stream;
     const double t_begin = now_s();
     const int ntot = (int)xyz_in.size();
-    // Order the batch by compactness (nuclear repulsion, most compact first).  Lanes of a wave are
-    // consecutive fragments: with similar geometries side by side, the primitive-pair screening and
-    // the Schwarz ballot drop the same work in every lane, so whole waves skip it.
-    std::vector<const double*> xyz(ntot);
-    std::vector<mqc_hip_scf_result_t*> results(ntot);
-    // external point charges (FMO / EE-MBE embedding): the same count in every fragment of the group (part of its key)
-    const int npc = (mols_in && ntot > 0) ? (*mols_in)[0]->n_point_charges : 0;
-    const bool hx = mols_in && ntot > 0 && (*mols_in)[0]->h_extra != nullptr;     // all or none within a group (its key says so)
-    const bool embedded = npc > 0 || hx;
-    std::vector<const mqc_hip_molecule_t*> pcmol(embedded ? ntot : 0);
+    Batch b{topo, aux, opts, atomic_guess};
+    BatchPlan plan;
+    // external point charges (FMO / EE-MBE embedding) and h_extra: the same in every fragment of the group (its key says so)
+    plan.npc = ntot > 0 ? mols_in[0]->n_point_charges : 0;
+    plan.hx = ntot > 0 && mols_in[0]->h_extra != nullptr;
+    const bool embedded = plan.npc > 0 || plan.hx;
     {
+        // Order the batch by compactness (nuclear repulsion, most compact first).  Lanes of a wave are
+        // consecutive fragments: with similar geometries side by side, the primitive-pair screening and
+        // the Schwarz ballot drop the same work in every lane, so whole waves skip it.
         std::vector<std::pair<double, int>> key(ntot);
         for (int i = 0; i < ntot; ++i) key[i] = {-nuclear_repulsion(topo, xyz_in[i]), i};
         std::stable_sort(key.begin(), key.end());
-        for (int k = 0; k < ntot; ++k) { xyz[k] = xyz_in[key[k].second]; results[k] = results_in[key[k].second]; }
-        if (embedded) for (int k = 0; k < ntot; ++k) pcmol[k] = (*mols_in)[key[k].second];
+        for (auto& k : key) {
+            b.xyz.push_back(xyz_in[k.second]); b.results.push_back(results_in[k.second]);
+            if (embedded) b.mols.push_back(mols_in[k.second]);
+        }
     }
     std::string msg;
-    int rc = validate_options(opts, topo, msg);
+    int rc = plan_batch(opts, topo, ntot, plan, msg);
     if (rc == MQC_HIP_OK && embedded && opts.want_gradient) {
         msg = "analytic gradients of a fragment embedded in point charges or an extra one-electron operator are not built (the field's own derivative is missing)";
         rc = MQC_HIP_ERR_UNSUPPORTED;
     }
-    if (rc == MQC_HIP_OK && npc > 0)
+    if (rc == MQC_HIP_OK && plan.npc > 0)
         for (int k = 0; k < ntot && rc == MQC_HIP_OK; ++k)
-            if (!pcmol[k]->point_charge_xyz || !pcmol[k]->point_charges) { msg = "point charges announced but their arrays are NULL"; rc = MQC_HIP_ERR_VALIDATION; }
-    if (rc != MQC_HIP_OK) {
-        for (auto* r : results) { fill_error(r, msg); r->scf_status = MQC_HIP_SCF_NOT_RUN; }
-        return fail(rc, msg);
-    }
-    TopologyDev td;
-    rc = upload_topology(ctx, topo, td, second ? &ctx->pool_topo2 : &ctx->pool_topo, lane_stream);
+            if (!b.mols[k]->point_charge_xyz || !b.mols[k]->point_charges) { msg = "point charges announced but their arrays are NULL"; rc = MQC_HIP_ERR_VALIDATION; }
+    if (rc == MQC_HIP_OK && plan.two_e == TWO_E_DF && !aux) { msg = "density fitting needs an auxiliary basis"; rc = MQC_HIP_ERR_VALIDATION; }
+    if (rc != MQC_HIP_OK) return refuse(b.results, rc, msg);
+    rc = upload_topology(ctx, topo, b.td, second ? &ctx->pool_topo2 : &ctx->pool_topo, lane_stream);
     if (rc != MQC_HIP_OK) return rc;
-    const bool use_df = opts.density_fitting != 0;
-    // exact-ERI path selection (mqc_libcint_bridge.f90:819-892 with an HBM budget instead of 2 GB of host memory)
-    const bool use_direct = !use_df && (opts.eri_mode == MQC_HIP_ERI_DIRECT ||
-                                        (opts.eri_mode == MQC_HIP_ERI_AUTO && !incore_supported(topo.nao)));
-    const double direct_tol = opts.schwarz_tol > 0.0 ? opts.schwarz_tol : 1.0e-11;   // mqc_libcint_direct.f90:61
-    TopologyDev tdx{};
-    int naux = 0;
-    if (use_df) {
-        if (!aux) {
-            const std::string m = "density fitting needs an auxiliary basis";
-            for (auto* r : results) { fill_error(r, m); r->scf_status = MQC_HIP_SCF_NOT_RUN; }
-            return fail(MQC_HIP_ERR_VALIDATION, m);
-        }
-        rc = upload_topology(ctx, *aux, tdx, second ? &ctx->pool_aux2 : &ctx->pool_aux, lane_stream);
+    if (plan.two_e == TWO_E_DF) {
+        rc = upload_topology(ctx, *aux, b.tdx, second ? &ctx->pool_aux2 : &ctx->pool_aux, lane_stream);
         if (rc != MQC_HIP_OK) return rc;
-        naux = aux->nao;
+        plan.naux = aux->nao;
     }
-
-    // ---- exchange-correlation: functional, per-element grid templates, per-topology point list
-    XcSpec xc;
-    {
-        std::string e;
-        parse_functional(opts.functional, xc, e);
-    }
-    GridDev grid;
-    if (xc.ncomp > 0) {
-        std::map<int, std::pair<int, int>> tmpl_of_z;     // Z -> (offset, count) in the packed template arrays
-        std::vector<double> txyz, tw, sb(topo.natoms);
-        std::vector<int> pt_atom, pt_tmpl;
-        for (int a = 0; a < topo.natoms; ++a) {
-            // a ghost centre enters the grid builder with Z = 0 (numbers = nint(mol%charges), mqc_libcint_xc.F90:181-183):
-            // period-1 sizes, xi(0) = 1, Bragg radius(0) = 2 Angstrom -- it still owns grid points
-            const int z = (topo.zeff[a] == 0.0) ? 0 : topo.Z[a];
-            sb[a] = std::sqrt(bragg_radius_bohr(z)) + 1e-200;
-            if (!tmpl_of_z.count(z)) {
-                std::vector<double> x, w; std::string e;
-                if (!build_atom_template(z, opts.grid_level, opts.radial_points, opts.angular_points, x, w, e)) {
-                    for (auto* r : results) { fill_error(r, e); r->scf_status = MQC_HIP_SCF_NOT_RUN; }
-                    return fail(MQC_HIP_ERR_UNSUPPORTED, e);
-                }
-                tmpl_of_z[z] = {(int)tw.size(), (int)w.size()};
-                txyz.insert(txyz.end(), x.begin(), x.end());
-                tw.insert(tw.end(), w.begin(), w.end());
-            }
-            const auto oc = tmpl_of_z[z];
-            for (int k = 0; k < oc.second; ++k) { pt_atom.push_back(a); pt_tmpl.push_back(oc.first + k); }
-        }
-        grid.npts = (int)pt_atom.size();
-        const size_t b_int = (sizeof(int) * pt_atom.size() + 255) & ~size_t(255);
-        const size_t b_xyz = (sizeof(double) * txyz.size() + 255) & ~size_t(255);
-        const size_t b_w = (sizeof(double) * tw.size() + 255) & ~size_t(255);
-        const size_t b_sb = (sizeof(double) * sb.size() + 255) & ~size_t(255);
-        char* gb = (char*)(second ? ctx->pool_grid2 : ctx->pool_grid).ensure(2 * b_int + b_xyz + b_w + b_sb + 1024);
-        if (!gb) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (grid templates)");
-        int* d_pa = (int*)gb; int* d_pt = (int*)(gb + b_int);
-        double* d_x = (double*)(gb + 2 * b_int); double* d_w = (double*)(gb + 2 * b_int + b_xyz);
-        double* d_sb = (double*)(gb + 2 * b_int + b_xyz + b_w);
-        HIP_CHECK_RET(hipMemcpyAsync(d_pa, pt_atom.data(), sizeof(int) * pt_atom.size(), hipMemcpyHostToDevice, lane_stream));
-        HIP_CHECK_RET(hipMemcpyAsync(d_pt, pt_tmpl.data(), sizeof(int) * pt_tmpl.size(), hipMemcpyHostToDevice, lane_stream));
-        HIP_CHECK_RET(hipMemcpyAsync(d_x, txyz.data(), sizeof(double) * txyz.size(), hipMemcpyHostToDevice, lane_stream));
-        HIP_CHECK_RET(hipMemcpyAsync(d_w, tw.data(), sizeof(double) * tw.size(), hipMemcpyHostToDevice, lane_stream));
-        HIP_CHECK_RET(hipMemcpyAsync(d_sb, sb.data(), sizeof(double) * sb.size(), hipMemcpyHostToDevice, lane_stream));
-        HIP_CHECK_RET(hipStreamSynchronize(lane_stream));     // the host vectors go out of scope
-        grid.pt_atom = d_pa; grid.pt_tmpl = d_pt; grid.tmpl_xyz = d_x; grid.tmpl_w = d_w; grid.sqrt_bragg = d_sb;
-    }
-
-    const int n = topo.nao;
-    const size_t np = (size_t)topo.npair;
-    const bool uhf_mem = opts.unrestricted || topo.multiplicity != 1 || (topo.nelec % 2) != 0;
-    // in-core tensor: the square, or -- where the batch takes the triangular block layout (kern_fock.hip) -- 0.53 of it
-    const size_t tensor = jk_tri_layout(n, topo.npair, ntot, uhf_mem) ? (size_t)((topo.npair + 1) / 2) * (size_t)jk_tri_block(topo.npair) : np * np;
-    // range-separated hybrids carry a second tensor (erf(omega r12)/r12) plus J scratch and K_lr per spin (carve_batch)
-    const bool rsh = xc.omega > 0.0;
-    const size_t rsh_doubles = rsh ? tensor + (size_t)n * n * (uhf_mem ? 3 : 2) : 0;
-    const size_t two_e = use_df ? (2 * (size_t)naux * np + 3 * (size_t)naux * naux) : (use_direct ? 2 * (size_t)n * n : tensor + rsh_doubles);
-    // radial cache of the quadrature (MQC_HIP_XC_RADIAL_CACHE=0 turns it off): 2 doubles per shell and (padded) grid point
+    if (plan.xc.ncomp > 0 && (rc = upload_grid(ctx, b, second ? ctx->pool_grid2 : ctx->pool_grid, lane_stream)) != MQC_HIP_OK) return rc;
+    plan.npts = b.grid.npts;
+    // radial cache of the quadrature: MQC_HIP_XC_RADIAL_CACHE=0 turns it off
     static const bool rad_cache_on = [] { const char* e = std::getenv("MQC_HIP_XC_RADIAL_CACHE"); return !(e && e[0] == '0'); }();
-    const int rad_pt = xc_tile_points(n);
-    const size_t rad_tiles = xc.ncomp > 0 ? ((size_t)grid.npts + rad_pt - 1) / rad_pt : 0;
-    const size_t rad_doubles = (xc.ncomp > 0 && rad_cache_on && !uhf_mem) ? rad_tiles * topo.shells.size() * 2 * rad_pt : 0;
-    // point buffer of the split quadrature (n <= 96, s-f shells, 32-point tiles): 4 doubles per padded grid point
-    const size_t pt4_doubles = (rad_doubles && n <= 96 && topo.lmax <= 3 && rad_pt == 32) ? rad_tiles * rad_pt * 4 : 0;
-    const size_t per_frag = sizeof(double) * (per_fragment_main_doubles(n, topo.natoms, uhf_mem, npc, hx) + two_e + (xc.ncomp > 0 ? (size_t)n * n * (uhf_mem ? 2 : 1) + grid.npts : 0) + rad_doubles + pt4_doubles);
+    plan_layout(plan, ntot, (int)topo.shells.size(), topo.lmax, rad_cache_on);
+
+    const size_t per_frag = fragment_bytes(plan);
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
     free_b += ctx->pool_main.capacity() + ctx->pool_eri.capacity() + ctx->pool_df.capacity() + ctx->pool_gridw.capacity()
@@ -489,537 +905,45 @@ int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology* aux, c
     if (chunk < 1) return fail(MQC_HIP_ERR_DEVICE, "not enough device memory for one fragment");
     if (chunk > ntot) chunk = ntot;
     if (chunk > 60000) chunk = 60000;    // grid.y limit of the J/K kernel
-
-    const bool uhf = opts.unrestricted || topo.multiplicity != 1 || (topo.nelec % 2) != 0;
-    const int nalpha = uhf ? (topo.nelec + topo.multiplicity - 1) / 2 : topo.nelec / 2;
-    const int nbeta = uhf ? topo.nelec - nalpha : topo.nelec / 2;
-    const int nocc = uhf ? nalpha : topo.nelec / 2;
-    int* h_counter = nullptr;
-    HIP_CHECK_RET(hipHostMalloc((void**)&h_counter, 256));
-    Slot slots[2] = {
-        {0, ctx->stream, &ctx->pool_main, &ctx->pool_eri, &ctx->pool_misc, &ctx->pool_gridw, &ctx->pool_df,
-         ctx->ev0, ctx->ev1, ctx->ev2, ctx->ev3, ctx->evq0, ctx->evq1, h_counter, ctx->evs[0][0], ctx->evs[0][1]},
-        {1, ctx->stream2, &ctx->pool_main2, &ctx->pool_eri2, &ctx->pool_misc2, &ctx->pool_gridw2, &ctx->pool_df2,
-         ctx->evb0, ctx->evb1, ctx->evb2, ctx->evb3, ctx->evq2, ctx->evq3, h_counter + 32, ctx->evs[1][0], ctx->evs[1][1]}};
-
-    struct Job { int start = 0, nf = 0; BatchView bv{}; std::vector<double> hx, hpc; };
     std::vector<Job> jobs;
     for (int start = 0; start < ntot; start += (int)chunk) {
         Job j; j.start = start; j.nf = (int)std::min<long>(chunk, ntot - start);
         jobs.push_back(std::move(j));
     }
-    // Schwarz screening of the in-core build pays for itself through the quartets it drops; for a handful of fragments
-    // the bounds (one thread per shell pair walking its primitive quartets: 1.6 ms for one cc-pVDZ water dimer) cost
-    // more than the screened quartets save, and the unscreened tensor needs no zero fill.  Energies move by < 1e-11 Eh
-    // either way (that is what the threshold means); MQC_HIP_SCHWARZ_MIN_FRAGMENTS=0 screens always.
-    static const int schwarz_min = [] { const char* e = std::getenv("MQC_HIP_SCHWARZ_MIN_FRAGMENTS"); return e ? std::atoi(e) : 9; }();
-    const double stol = (opts.schwarz_tol > 0.0 && ntot >= schwarz_min) ? opts.schwarz_tol : 0.0;
 
-    // drains both streams before an error return hands the pools back
-    auto bail = [&](int code) {
-        if (lane != 1) (void)hipStreamSynchronize(ctx->stream);
-        if (lane != 0) (void)hipStreamSynchronize(ctx->stream2);
-        (void)hipHostFree(h_counter);
-        return code;
+    int* h_counter = nullptr;
+    HIP_CHECK_RET(hipHostMalloc((void**)&h_counter, 256));
+    Slot slots[2] = {make_slot(ctx, 0, h_counter), make_slot(ctx, 1, h_counter + 32)};
+    auto finish = [&](Slot& sl, Job& job) {
+        int r = scf_loop(plan, b, sl, job);
+        if (r == MQC_HIP_OK) r = fetch_results(plan, b, sl, job);
+        std::vector<double>().swap(job.hx);
+        return r;
     };
-
-    // ---- stage 1 of a chunk: everything up to (and including) the guess, enqueued on the slot's stream
-    auto prepare = [&](Slot& sl, Job& job) -> int {
-        const int nf = job.nf;
-        hipStream_t s = sl.s;
-        const double t0 = now_s();
-        BatchView& bv = job.bv;
-        int rc = carve_batch(ctx, sl, topo, td, nf, !use_df && !use_direct, bv, uhf, npc, hx, rsh && !use_df && !use_direct);
-        if (rc != MQC_HIP_OK) return rc;
-        bv.nalpha = nalpha; bv.nbeta = nbeta;
-        bv.naux = naux; bv.aux = tdx; bv.unit = ctx->d_unit;
-        if (use_df) {
-            const size_t a3 = (size_t)nf * naux * np, mm = (size_t)nf * naux * naux;
-            double* base = (double*)sl.df->ensure(sizeof(double) * (2 * a3 + 3 * mm) + 1024);
-            if (!base) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (fitted tensor)");
-            bv.df_a3 = base; bv.df_b = base + a3; bv.df_metric = base + 2 * a3; bv.df_linv = base + 2 * a3 + mm;
-            bv.df_work = base + 2 * a3 + 2 * mm;
-            HIP_CHECK_RET(hipMemsetAsync(bv.scal, 0, sizeof(double) * (size_t)nf * 8, s));
-        }
-        // range-separated hybrids: K is folded to exx K + exx_lr K_lr before the step, which then takes all of it
-        bv.nocc = nocc; bv.exx = rsh ? 1.0 : xc.exx; bv.e_tol = opts.energy_tol; bv.d_tol = opts.density_tol;
-        bv.xc = xc; bv.grid = grid; bv.Vxc = nullptr;
-        if (xc.ncomp > 0) {
-            char* gw = (char*)sl.gridw->ensure(sizeof(double) * (size_t)nf * ((size_t)grid.npts + (size_t)n * n * (uhf ? 2 : 1) + rad_doubles + pt4_doubles) + 2048);
-            if (!gw) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (grid weights)");
-            bv.grid.weights = (double*)gw;
-            bv.Vxc = (double*)(gw + ((sizeof(double) * (size_t)nf * grid.npts + 255) & ~size_t(255)));
-            bv.grid.rad = nullptr; bv.grid.rad_pt = rad_pt;
-            if (rad_doubles) bv.grid.rad = (double*)((char*)bv.Vxc + ((sizeof(double) * (size_t)nf * n * n * (uhf ? 2 : 1) + 255) & ~size_t(255)));
-            bv.grid.pt4 = nullptr;
-            if (pt4_doubles) bv.grid.pt4 = (double*)((char*)bv.grid.rad + ((sizeof(double) * (size_t)nf * rad_doubles + 255) & ~size_t(255)));
-        }
-        bv.max_iter = opts.max_iter; bv.diis_size = opts.use_diis ? opts.diis_size : 0;
-        job.hx.resize((size_t)nf * topo.natoms * 3);
-        for (int f = 0; f < nf; ++f) std::memcpy(&job.hx[(size_t)f * topo.natoms * 3], xyz[job.start + f], sizeof(double) * topo.natoms * 3);
-        HIP_CHECK_RET(hipMemcpyAsync(bv.xyz, job.hx.data(), sizeof(double) * job.hx.size(), hipMemcpyHostToDevice, s));
-        if (npc > 0) {
-            // layout [charge][x, y, z, q][fragment], FRAGMENT FASTEST: the lanes of a wave are consecutive fragments, so a
-            // wave reads a charge's component as one contiguous 512-byte line -- with [fragment][charge][4] every lane
-            // streamed its own 49 KB array and a wave-load touched 64 cache lines (int1e: 40 % of a 512-fragment FMO run)
-            job.hpc.resize((size_t)nf * npc * 4);
-            for (int f = 0; f < nf; ++f) {
-                const mqc_hip_molecule_t* m = pcmol[job.start + f];
-                for (int g = 0; g < npc; ++g) {
-                    double* q = &job.hpc[(size_t)g * 4 * nf + f];
-                    q[0] = m->point_charge_xyz[3 * g]; q[(size_t)nf] = m->point_charge_xyz[3 * g + 1]; q[2 * (size_t)nf] = m->point_charge_xyz[3 * g + 2];
-                    q[3 * (size_t)nf] = m->point_charges[g];
-                }
-            }
-            HIP_CHECK_RET(hipMemcpyAsync((void*)bv.pc, job.hpc.data(), sizeof(double) * job.hpc.size(), hipMemcpyHostToDevice, s));
-        }
-        if (hx)
-            for (int f = 0; f < nf; ++f)
-                HIP_CHECK_RET(hipMemcpyAsync((void*)(bv.Hx + (size_t)f * n * n), pcmol[job.start + f]->h_extra, sizeof(double) * n * n, hipMemcpyHostToDevice, s));
-        HIP_CHECK_RET(hipMemsetAsync(bv.istate, 0, sizeof(int) * (size_t)nf * 4, s));
-        HIP_CHECK_RET(hipMemsetAsync(bv.eri_count, 0, sizeof(unsigned long long), s));
-        const double t1 = now_s();
-        sx->stats.t_setup += t1 - t0;
-
-        if (!use_df && !use_direct) launch_eri_bounds(bv, topo, stol, s);     // screened build: bounds run next to the 1e stage
-        // The one-electron stage, the orthogonaliser and the starting guess need the geometry (S, H) only and are
-        // latency-bound (six class launches; one workgroup per fragment, Jacobi sweeps): they run on a side stream next
-        // to the compute-bound two-electron stage, which does not wait for them (0.7 ms of a single-fragment call)
-        hipStream_t so = ctx->side[sl.id & 1][2];
-        HIP_CHECK_RET(hipEventRecord(ctx->evo[sl.id & 1][0], s));             // uploads and resets above are in
-        HIP_CHECK_RET(hipStreamWaitEvent(so, ctx->evo[sl.id & 1][0], 0));
-        launch_int1e(bv, topo, so);
-        // block-sharing plan and class lists of the integral stage: host work that depends on the geometry only, done
-        // here while the bounds and one-electron kernels run
-        if (!use_df && !use_direct) eri_plan_lists(bv, topo, s, job.hx.data());
-        if ((rc = stage_check("int1e")) != MQC_HIP_OK) return rc;
-        launch_orthogonalizer(bv, so);
-        if ((rc = stage_check("orthogonalizer")) != MQC_HIP_OK) return rc;
-        if (!atomic_guess) launch_guess(bv, opts.guess == MQC_HIP_GUESS_CORE ? MQC_HIP_GUESS_CORE : MQC_HIP_GUESS_GWH, so);
-        if ((rc = stage_check("guess")) != MQC_HIP_OK) return rc;
-        HIP_CHECK_RET(hipEventRecord(ctx->evo[sl.id & 1][1], so));
-        if (xc.ncomp > 0) { launch_becke_weights(bv, s); if (bv.grid.rad) launch_xc_radial_cache(bv, s); }
-        if ((rc = stage_check("grid weights")) != MQC_HIP_OK) return rc;
-        const double t2 = now_s();
-        sx->stats.t_int1e += t2 - t1;
-
-        HIP_CHECK_RET(hipEventRecord(sl.q0, s));
-        if (use_df) launch_df_build(bv, topo, *aux, s);
-        else if (use_direct) launch_direct_setup(bv, topo, s);
-        else {
-            launch_eri(bv, topo, stol, s, job.hx.data());
-            if (rsh) {
-                // the long-range tensor: same lists, screening (the Coulomb bounds bound it) and block sharing
-                BatchView vl = bv;
-                vl.eri = bv.eri_lr;
-                launch_eri(vl, topo, stol, s, job.hx.data(), xc.omega);
-            }
-            // the bounds of a screened build tell the J/K kernel which pair rows are all zeros (triangular tensor only)
-            if (stol > 0.0 && bv.eri_tri) eri_schwarz_view(bv.slot, &bv.jk_q, &bv.jk_qthresh);
-        }
-        HIP_CHECK_RET(hipEventRecord(sl.q1, s));
-        if ((rc = stage_check("two-electron setup")) != MQC_HIP_OK) return rc;
-        sx->stats.eri_quartets += topo.n_quartets * nf;
-        HIP_CHECK_RET(hipStreamWaitEvent(s, ctx->evo[sl.id & 1][1], 0));      // join: X, C, D of the guess are ready
-        if (atomic_guess) {
-            // superposed atoms (build_restricted_guess / atomic_guess_fock, mqc_libcint_atomic_guess.f90:168-212,
-            // mqc_libcint_rhf.f90:1382-1411): the same block-diagonal density in every fragment of the topology, its
-            // Hartree-Fock Fock matrix from the two-electron stage just built (full exchange), then the usual
-            // diagonalisation and occupation -- both spins of an unrestricted run start from it
-            const size_t nn = (size_t)n * n;
-            double* d0 = (double*)g_guess_pool[sl.id & 1].ensure(sizeof(double) * 2 * nn + 256);
-            if (!d0) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (guess density)");
-            HIP_CHECK_RET(hipMemcpyAsync(d0, atomic_guess->D0.data(), sizeof(double) * nn, hipMemcpyHostToDevice, s));
-            launch_broadcast(bv.D, d0, nn, nf, s);
-            BatchView vg = bv;
-            vg.exx = 1.0; vg.uhf = 0;
-            if (use_df) {
-                HIP_CHECK_RET(hipMemcpyAsync(d0 + nn, atomic_guess->Cp.data(), sizeof(double) * nn, hipMemcpyHostToDevice, s));
-                launch_broadcast(bv.C, d0 + nn, nn, nf, s);
-                vg.nocc = atomic_guess->nmodes;
-                launch_df_jk(vg, false, s);
-            } else if (use_direct) launch_jk_direct(vg, topo, direct_tol, false, s);
-            else launch_jk_incore(vg, false, s);
-            launch_guess(bv, MQC_HIP_GUESS_SAD, s);
-            if ((rc = stage_check("atomic guess")) != MQC_HIP_OK) return rc;
-        }
-        sx->stats.t_eri += now_s() - t2;      // host time to enqueue; the kernels are timed by q0/q1
-        return MQC_HIP_OK;
-    };
-
-    // ---- stage 2: the SCF loop (one int back per iteration) and the result fetch
-    auto iterate_and_fetch = [&](Slot& sl, Job& job) -> int {
-        const int nf = job.nf;
-        hipStream_t s = sl.s;
-        BatchView& bv = job.bv;
-        int rc;
-        const double t3 = now_s();
-        HIP_CHECK_RET(hipStreamSynchronize(s));
-        if ((rc = stage_check("integrals")) != MQC_HIP_OK) return rc;
-        {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, sl.q0, sl.q1);
-            sx->stats.eri_kernel_seconds += ms * 1e-3;
-        }
-        int remaining = nf;
-        int guard = 0;
-        double tri_doubles_per_fragment = -1.0;      // read back after the first J/K launch of the chunk
-        // Kohn-Sham: the quadrature needs the density only, like J/K -- it runs on the lane's side stream next to the
-        // J/K build and joins before the SCF step (the event pair that synchronised orthogonaliser and guess is free now)
-        hipStream_t sxc = ctx->side[sl.id & 1][2];
-        // OFF by default: measured 1206 against 1230 ms per B3LYP evaluation (-2 %), but the J/K launches then wait inside
-        // the quadrature's shadow and their HIP-event times (the bench's per-stage figures) stop meaning anything
-        static const bool xc_side = [] { const char* e = std::getenv("MQC_HIP_XC_SIDE_STREAM"); return e && e[0] == '1'; }();
-        const bool xc_on_side = xc.ncomp > 0 && xc_side;
-        // Small batches are latency-bound: the host round trip after every iteration (one int back, ~50 us) costs as
-        // much as the kernels.  They run BLOCKS of iterations between two reads of the counter -- finished fragments
-        // drop out of every kernel by themselves (state machine), so an iteration enqueued past convergence is three
-        // empty launches.  Large batches keep one read per iteration (MQC_HIP_SCF_SYNC_BLOCK overrides: 1 = always).
-        static const int sync_block_env = [] { const char* e = std::getenv("MQC_HIP_SCF_SYNC_BLOCK"); return e ? std::atoi(e) : 0; }();
-        static const int block_max_frag = [] { const char* e = std::getenv("MQC_HIP_SCF_BLOCK_MAX_FRAGMENTS"); return e ? std::atoi(e) : 256; }();
-        const bool blocked = sync_block_env != 1 && nf <= block_max_frag;
-        int blocks_done = 0;
-        while (remaining > 0 && guard < opts.max_iter + 2) {
-          int block_len = 1;
-          if (blocked) block_len = sync_block_env > 1 ? sync_block_env : (blocks_done == 0 ? 8 : 4);
-          if (block_len > opts.max_iter + 2 - guard) block_len = opts.max_iter + 2 - guard;
-          ++blocks_done;
-          for (int bi = 0; bi < block_len; ++bi) {
-            const bool last_of_block = bi + 1 == block_len;
-            if (xc_on_side) {
-                HIP_CHECK_RET(hipEventRecord(ctx->evo[sl.id & 1][0], s));
-                HIP_CHECK_RET(hipStreamWaitEvent(sxc, ctx->evo[sl.id & 1][0], 0));
-                HIP_CHECK_RET(hipEventRecord(sl.e2, sxc));
-                launch_xc(bv, true, sxc);
-                HIP_CHECK_RET(hipEventRecord(sl.e3, sxc));
-                HIP_CHECK_RET(hipEventRecord(ctx->evo[sl.id & 1][1], sxc));
-            }
-            HIP_CHECK_RET(hipEventRecord(sl.e0, s));
-            if (use_df) {
-                launch_df_jk(bv, true, s);
-                if (uhf) {
-                    // unrestricted density fitting, as run_uks_scf of the cuEST path (mqc_cuest_scf.f90:637-1009): J from each
-                    // spin density, K_s = sum_P (B_P C_s)(B_P C_s)^T; the kernels return the closed-shell 2 W W^T
-                    const size_t tot = (size_t)nf * n * n;
-                    launch_scale(bv.K, tot, 0.5, s);
-                    if (nbeta > 0) {
-                        BatchView vb = bv;
-                        vb.D = bv.Db; vb.J = bv.Jb; vb.K = bv.Kb; vb.C = bv.Cb; vb.nocc = nbeta;
-                        launch_df_jk(vb, true, s);
-                        launch_scale(bv.Kb, tot, 0.5, s);
-                    } else {
-                        HIP_CHECK_RET(hipMemsetAsync(bv.Jb, 0, sizeof(double) * tot, s));
-                        HIP_CHECK_RET(hipMemsetAsync(bv.Kb, 0, sizeof(double) * tot, s));
-                    }
-                }
-            } else if (use_direct) {
-                launch_jk_direct_incremental(bv, topo, direct_tol, true, s);        // restricted: G_ref += G(D - D_ref)
-                if (uhf) {
-                    // the integrals are formed again for the beta density: J[D_b], K[D_b] (twice the direct work)
-                    BatchView vb = bv;
-                    vb.D = bv.Db; vb.J = bv.Jb; vb.K = bv.Kb;
-                    launch_jk_direct(vb, topo, direct_tol, true, s);
-                }
-            } else {
-                launch_jk_incore(bv, true, s);
-                if (uhf) {
-                    // the same stream over the tensor with the beta density: J[D_b], K[D_b]
-                    BatchView vb = bv;
-                    vb.D = bv.Db; vb.J = bv.Jb; vb.K = bv.Kb;
-                    launch_jk_incore(vb, true, s);
-                }
-                if (rsh) {
-                    // K_lr of each spin density from the long-range tensor (its J is not used), folded into K
-                    BatchView vl = bv;
-                    vl.eri = bv.eri_lr; vl.J = bv.Jlr; vl.K = bv.Klr; vl.jk_loaded = nullptr;
-                    launch_jk_incore(vl, true, s);
-                    launch_exchange_fold(bv, bv.K, bv.Klr, xc.exx, xc.exx_lr, s);
-                    if (uhf) {
-                        vl.D = bv.Db; vl.K = bv.Klrb;
-                        launch_jk_incore(vl, true, s);
-                        launch_exchange_fold(bv, bv.Kb, bv.Klrb, xc.exx, xc.exx_lr, s);
-                    }
-                }
-            }
-            HIP_CHECK_RET(hipEventRecord(sl.e1, s));
-            if (guard == 0 && (rc = stage_check("J/K build")) != MQC_HIP_OK) return rc;
-            if (xc_on_side) HIP_CHECK_RET(hipStreamWaitEvent(s, ctx->evo[sl.id & 1][1], 0));
-            else if (xc.ncomp > 0) {
-                HIP_CHECK_RET(hipEventRecord(sl.e2, s));
-                launch_xc(bv, true, s);
-                HIP_CHECK_RET(hipEventRecord(sl.e3, s));
-            }
-            HIP_CHECK_RET(hipEventRecord(sl.s0, s));
-            launch_scf_step(bv, s);
-            HIP_CHECK_RET(hipEventRecord(sl.s1, s));
-            if (!last_of_block) { ++guard; continue; }
-            HIP_CHECK_RET(hipMemcpyAsync(sl.h_counter, bv.counters, sizeof(int), hipMemcpyDeviceToHost, s));
-            HIP_CHECK_RET(hipStreamSynchronize(s));
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, sl.s0, sl.s1);
-            sx->stats.scf_step_seconds += ms * 1e-3 * block_len;
-            (void)hipEventElapsedTime(&ms, sl.e0, sl.e1);
-            if (use_df) {
-                sx->stats.df_bytes += (double)remaining * 8.0 * (double)naux * (double)n * (double)n * block_len;
-                sx->stats.df_flops += (double)remaining * 4.0 * (double)naux * (double)n * (double)n * (1.0 + (xc.exx != 0.0 ? (double)nocc : 0.0)) * block_len;
-            }
-            // density fitting: the J/K kernel reads the fitted tensor once, and it is stored packed [naux][npair] -- about
-            // half of SURVEY 8d's 8 n^2 A (df_bytes keeps that figure; fock_bytes is what the kernel really streams)
-            // in-core: the tensor as stored -- the square, or its lower triangle (BatchView::eri_tri) -- once per spin density;
-            // the triangular kernel skips rows the Schwarz bounds prove zero and reports the chunks it did read
-            if (bv.eri_tri && bv.jk_loaded && tri_doubles_per_fragment < 0.0) {
-                std::vector<int> ld(nf);
-                if (hipMemcpy(ld.data(), bv.jk_loaded, sizeof(int) * (size_t)nf, hipMemcpyDeviceToHost) == hipSuccess) {
-                    double sum = 0.0;
-                    for (int v : ld) sum += v;
-                    tri_doubles_per_fragment = 128.0 * sum / (double)nf;
-                } else tri_doubles_per_fragment = (double)bv.eri_stride;
-            }
-            const double tensor_doubles = (bv.eri_tri && tri_doubles_per_fragment >= 0.0) ? tri_doubles_per_fragment
-                                                                                         : (bv.eri_stride ? (double)bv.eri_stride : (double)np * (double)np);
-            const double launch_bytes = use_df ? (double)remaining * (double)naux * (double)np * 8.0
-                                               : (double)remaining * tensor_doubles * 8.0 * (uhf ? 2.0 : 1.0);
-            sx->stats.fock_kernel_seconds += ms * 1e-3 * block_len;
-            sx->stats.fock_bytes += launch_bytes * block_len;
-            sx->stats.fock_launches += block_len;
-            if (launch_bytes >= 1073741824.0) {
-                sx->stats.fock_big_launches += 1; sx->stats.fock_big_seconds += ms * 1e-3; sx->stats.fock_big_bytes += launch_bytes;
-            }
-            if (xc.ncomp > 0) {
-                float mx = 0.f;
-                (void)hipEventElapsedTime(&mx, sl.e2, sl.e3);
-                sx->stats.xc_kernel_seconds += mx * 1e-3 * block_len;
-                sx->stats.xc_points += (double)remaining * grid.npts * block_len;
-                sx->stats.xc_flops += (double)remaining * grid.npts * (xc.gga ? 8.0 : 4.0) * (double)n * (double)n * block_len;
-            }
-            remaining = sl.h_counter[0];
-            ++guard;
-          }
-        }
-        if ((rc = stage_check("SCF loop")) != MQC_HIP_OK) return rc;
-        const double t4 = now_s();
-        sx->stats.t_fock += t4 - t3;
-
-        std::vector<double> scal((size_t)nf * 8), eps((size_t)nf * n), dip((size_t)nf * 4);
-        std::vector<int> ist((size_t)nf * 4);
-        unsigned long long formed = 0;
-        // ---- analytic gradient (compute_scf_gradient, mqc_cuest_gradient.f90:91-175): device terms here, E_nuc' on the host
-        std::vector<double> hgrad;
-        if (opts.want_gradient) {
-            size_t lint = topo.pairs.size() + 64;
-            for (auto& cl : topo.classes) lint += cl.quartets.size();
-            const size_t nnh = (size_t)n * n;
-            const size_t bytes = sizeof(double) * ((size_t)nf * topo.natoms * 3 + 2 * (size_t)nf * nnh + 8) + sizeof(int) * (lint + 64);
-            char* gb = (char*)g_grad_pool[sl.id & 1].ensure(bytes);
-            if (!gb) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (gradient)");
-            double* d_grad = (double*)gb;
-            double* gwork = d_grad + (((size_t)nf * topo.natoms * 3 + 7) & ~size_t(7));
-            int* glists = (int*)(gwork + 2 * (size_t)nf * nnh);
-            // above n_ao = 140 the two-electron term skips the (quartet, fragment) tasks the direct path's Schwarz bounds
-            // (still resident in this slot) prove below 1e-3 of its threshold: a derivative integral exceeds the bound of
-            // its undifferentiated quartet, and at the threshold itself the dropped tasks moved a (H2O)6 / cc-pVDZ
-            // gradient by 3.8e-9.  MQC_HIP_GRAD_SCREEN=0 forms them all (A/B switch)
-            static const bool grad_screen = [] { const char* e = std::getenv("MQC_HIP_GRAD_SCREEN"); return !(e && e[0] == '0'); }();
-            const double* gq = (grad_screen && use_direct && n > 140) ? direct_schwarz_view(bv.slot) : nullptr;
-            std::string gerr;
-            if (!launch_gradient(bv, topo, aux, d_grad, gwork, glists, lint, s, gerr, gq, 1.0e-3 * direct_tol)) return fail(MQC_HIP_ERR_UNSUPPORTED, gerr);
-            hgrad.resize((size_t)nf * topo.natoms * 3);
-            HIP_CHECK_RET(hipMemcpyAsync(hgrad.data(), d_grad, sizeof(double) * hgrad.size(), hipMemcpyDeviceToHost, s));
-        }
-        launch_dipole(bv, topo, s);
-        std::vector<double> epsb;
-        if (uhf) {
-            BatchView vb = bv;
-            vb.D = bv.Db;
-            launch_dipole(vb, topo, s, true);      // total density = D_a + D_b
-            epsb.resize((size_t)nf * n);
-            HIP_CHECK_RET(hipMemcpyAsync(epsb.data(), bv.epsb, sizeof(double) * epsb.size(), hipMemcpyDeviceToHost, s));
-        }
-        HIP_CHECK_RET(hipMemcpyAsync(dip.data(), bv.dip, sizeof(double) * dip.size(), hipMemcpyDeviceToHost, s));
-        HIP_CHECK_RET(hipMemcpyAsync(&formed, bv.eri_count, sizeof(formed), hipMemcpyDeviceToHost, s));
-        HIP_CHECK_RET(hipMemcpyAsync(scal.data(), bv.scal, sizeof(double) * scal.size(), hipMemcpyDeviceToHost, s));
-        HIP_CHECK_RET(hipMemcpyAsync(eps.data(), bv.eps, sizeof(double) * eps.size(), hipMemcpyDeviceToHost, s));
-        HIP_CHECK_RET(hipMemcpyAsync(ist.data(), bv.istate, sizeof(int) * ist.size(), hipMemcpyDeviceToHost, s));
-        // matrices the callers asked for (total density, embedding operator, overlap): the whole chunk in one copy each
-        std::vector<double> allD, allU, allS;
-        {
-            bool want_d = embedded, want_s = false;
-            for (int f = 0; f < nf; ++f) {
-                const mqc_hip_scf_result_t* r = results[job.start + f];
-                if (r->mulliken_charges) { want_d = true; want_s = true; }
-                if (r->density) want_d = true;
-            }
-            const size_t tot = (size_t)nf * n * n;
-            if (want_d) {
-                allD.resize(tot);
-                HIP_CHECK_RET(hipMemcpyAsync(allD.data(), bv.D, sizeof(double) * tot, hipMemcpyDeviceToHost, s));
-            }
-            if (embedded) {
-                allU.resize(tot);
-                HIP_CHECK_RET(hipMemcpyAsync(allU.data(), bv.U, sizeof(double) * tot, hipMemcpyDeviceToHost, s));
-            }
-            if (want_s) {
-                allS.resize(tot);
-                HIP_CHECK_RET(hipMemcpyAsync(allS.data(), bv.S, sizeof(double) * tot, hipMemcpyDeviceToHost, s));
-            }
-            if (want_d && uhf) {
-                std::vector<double> db(tot);
-                HIP_CHECK_RET(hipMemcpyAsync(db.data(), bv.Db, sizeof(double) * tot, hipMemcpyDeviceToHost, s));
-                HIP_CHECK_RET(hipStreamSynchronize(s));
-                for (size_t k = 0; k < tot; ++k) allD[k] += db[k];          // total density = alpha + beta
-            }
-        }
-        HIP_CHECK_RET(hipStreamSynchronize(s));
-        sx->stats.eri_survivors += (int64_t)formed;
-        for (int f = 0; f < nf; ++f) {
-            mqc_hip_scf_result_t* r = results[job.start + f];
-            const int nmo = ist[4 * f + 2];
-            r->n_ao = n; r->n_mo = nmo; r->n_occ = nocc;
-            if (nocc > nmo) {
-                // nmo check: more occupied orbitals than the basis supports after dropping near-null modes
-                fill_error(r, uhf ? "UHF: more alpha electrons than the basis supports after near-null modes were dropped"
-                                  : "RHF: more occupied orbitals than the basis supports after near-null modes were dropped");
-                r->scf_status = MQC_HIP_SCF_NOT_RUN;
-                continue;
-            }
-            r->e_nuclear = nuclear_repulsion(topo, xyz[job.start + f]);
-            r->e_electronic = scal[8 * f + 4];
-            r->e_total = r->e_electronic + r->e_nuclear;
-            r->e_xc = xc.ncomp > 0 ? scal[8 * f + 5] : 0.0;
-            r->iterations = ist[4 * f + 1];
-            const bool conv = ist[4 * f + 3] != 0 && ist[4 * f] == ST_DONE;
-            r->scf_status = conv ? MQC_HIP_SCF_CONVERGED : MQC_HIP_SCF_NOT_CONVERGED;
-            r->homo = eps[(size_t)f * n + nocc - 1];
-            r->lumo = nocc < nmo ? eps[(size_t)f * n + nocc] : 0.0;
-            r->has_orbitals = 1;
-            r->n_alpha = nalpha; r->n_beta = nbeta; r->s_squared = 0.0;
-            if (opts.want_gradient && r->gradient) {
-                // + nuclear repulsion: dE_nuc/dR_A = -sum_B Z_A Z_B (R_A - R_B)/|R_AB|^3 (ghosts carry no charge)
-                const double* x = xyz[job.start + f];
-                for (int a = 0; a < topo.natoms; ++a) {
-                    double g3[3] = {hgrad[((size_t)f * topo.natoms + a) * 3], hgrad[((size_t)f * topo.natoms + a) * 3 + 1], hgrad[((size_t)f * topo.natoms + a) * 3 + 2]};
-                    for (int b = 0; b < topo.natoms; ++b) {
-                        if (b == a || topo.zeff[a] == 0.0 || topo.zeff[b] == 0.0) continue;
-                        const double dx = x[3 * a] - x[3 * b], dy = x[3 * a + 1] - x[3 * b + 1], dz = x[3 * a + 2] - x[3 * b + 2];
-                        const double r2 = dx * dx + dy * dy + dz * dz, r3 = r2 * std::sqrt(r2);
-                        const double zz = topo.zeff[a] * topo.zeff[b] / r3;
-                        g3[0] -= zz * dx; g3[1] -= zz * dy; g3[2] -= zz * dz;
-                    }
-                    r->gradient[3 * a] = g3[0]; r->gradient[3 * a + 1] = g3[1]; r->gradient[3 * a + 2] = g3[2];
-                }
-                r->has_gradient = 1;
-            }
-            if (uhf) {
-                // <S^2> = S_z (S_z + 1) + n_beta - sum_ij |<a_i|S|b_j>|^2  (spin_contamination, mqc_libcint_rhf.f90)
-                const size_t nnh = (size_t)n * n;
-                std::vector<double> Ca(nnh), Cb(nnh), Sm(nnh);
-                HIP_CHECK_RET(hipMemcpyAsync(Ca.data(), bv.C + (size_t)f * nnh, sizeof(double) * nnh, hipMemcpyDeviceToHost, s));
-                HIP_CHECK_RET(hipMemcpyAsync(Cb.data(), bv.Cb + (size_t)f * nnh, sizeof(double) * nnh, hipMemcpyDeviceToHost, s));
-                HIP_CHECK_RET(hipMemcpyAsync(Sm.data(), bv.S + (size_t)f * nnh, sizeof(double) * nnh, hipMemcpyDeviceToHost, s));
-                HIP_CHECK_RET(hipStreamSynchronize(s));
-                double ov2 = 0.0;
-                std::vector<double> SCb((size_t)n * std::max(nbeta, 1));
-                for (int mu = 0; mu < n; ++mu)
-                    for (int j = 0; j < nbeta; ++j) {
-                        double t = 0.0;
-                        for (int nu = 0; nu < n; ++nu) t += Sm[(size_t)mu * n + nu] * Cb[(size_t)nu * n + j];
-                        SCb[(size_t)mu * nbeta + j] = t;
-                    }
-                for (int i = 0; i < nalpha; ++i)
-                    for (int j = 0; j < nbeta; ++j) {
-                        double t = 0.0;
-                        for (int mu = 0; mu < n; ++mu) t += Ca[(size_t)mu * n + i] * SCb[(size_t)mu * nbeta + j];
-                        ov2 += t * t;
-                    }
-                const double sz = 0.5 * (nalpha - nbeta);
-                r->s_squared = sz * (sz + 1.0) + nbeta - ov2;
-                if (r->orbital_energies_beta) std::memcpy(r->orbital_energies_beta, &epsb[(size_t)f * n], sizeof(double) * nmo);
-            }
-            {
-                // mu = sum_A Z_A (R_A - O) - [tr(D r) - O tr(D S)], O = centre of nuclear charge, tr(D S) = N_electrons
-                // (system_compute_dipole, mqc_cuest_integrals.f90:1443-1521)
-                const double* x = xyz[job.start + f];
-                double ztot = 0.0, o[3] = {0, 0, 0}, mu[3] = {0, 0, 0};
-                for (int a = 0; a < topo.natoms; ++a) { ztot += topo.zeff[a]; for (int c = 0; c < 3; ++c) o[c] += topo.zeff[a] * x[3 * a + c]; }
-                if (ztot > 0.0) for (int c = 0; c < 3; ++c) o[c] /= ztot; else for (int c = 0; c < 3; ++c) o[c] = 0.0;
-                for (int a = 0; a < topo.natoms; ++a) for (int c = 0; c < 3; ++c) mu[c] += topo.zeff[a] * (x[3 * a + c] - o[c]);
-                for (int c = 0; c < 3; ++c) r->dipole[c] = mu[c] - (dip[4 * f + c] - o[c] * (double)topo.nelec);
-                r->has_dipole = 1;
-            }
-            if (r->orbital_energies) std::memcpy(r->orbital_energies, &eps[(size_t)f * n], sizeof(double) * nmo);
-            if (embedded || r->mulliken_charges) {
-                // what the embedded callers read besides the energy: tr(D u), u itself, Mulliken populations
-                // (inner_scf / fragment_charges, mqc_libcint_fmo.f90:1992-2021) -- n^2 host work on the matrices of the
-                // whole chunk, copied back ONCE above (one synchronous copy per matrix and fragment cost seconds of
-                // a 130 000-pair batch)
-                const size_t nn = (size_t)n * n;
-                const double* hd = allD.data() + (size_t)f * nn;
-                if (embedded) {
-                    const double* hu = allU.data() + (size_t)f * nn;
-                    double e = 0.0;
-                    for (size_t k = 0; k < nn; ++k) e += hd[k] * hu[k];
-                    r->e_embedding = e;
-                    if (r->embedding_matrix) std::memcpy(r->embedding_matrix, hu, sizeof(double) * nn);
-                }
-                if (r->mulliken_charges) {
-                    const double* hm = allS.data() + (size_t)f * nn;
-                    for (int a = 0; a < topo.natoms; ++a) r->mulliken_charges[a] = topo.zeff[a];
-                    for (size_t sh = 0; sh < topo.shells.size(); ++sh) {
-                        const int a = topo.shells[sh].atom, o0 = topo.shells[sh].aoff, nf_sh = 2 * topo.shells[sh].l + 1;
-                        for (int mu = o0; mu < o0 + nf_sh; ++mu) {
-                            double pop = 0.0;
-                            for (int nu = 0; nu < n; ++nu) pop += hd[(size_t)mu * n + nu] * hm[(size_t)nu * n + mu];
-                            r->mulliken_charges[a] -= pop;
-                        }
-                    }
-                }
-            }
-            if (r->density) std::memcpy(r->density, allD.data() + (size_t)f * n * n, sizeof(double) * n * n);
-            r->has_error = 0; r->message[0] = '\0';
-            if (use_df && scal[8 * f + 7] == 1.0)
-                fill_error(r, "density fitting: the auxiliary metric (P|Q) could not be factorised or diagonalised");
-            else if (!std::isfinite(r->e_total)) fill_error(r, "SCF produced a non-finite energy");
-            else if (!conv && !opts.allow_crap_scf)
-                fill_error(r, "SCF did not converge in " + std::to_string(r->iterations) + " iterations");
-            sx->stats.scf_iterations_total += r->iterations;
-        }
-        sx->stats.t_scf_step += now_s() - t4;
-        return MQC_HIP_OK;
-    };
-
     const int njobs = (int)jobs.size();
     if (lane >= 0) {
         // one slot only: chunks strictly one after the other
         Slot& sl = slots[lane & 1];
-        for (int k = 0; k < njobs; ++k) {
-            if ((rc = prepare(sl, jobs[k])) != MQC_HIP_OK) return bail(rc);
-            if ((rc = iterate_and_fetch(sl, jobs[k])) != MQC_HIP_OK) return bail(rc);
-            std::vector<double>().swap(jobs[k].hx);
-        }
+        for (int k = 0; k < njobs && rc == MQC_HIP_OK; ++k)
+            if ((rc = prepare(ctx, plan, b, sl, jobs[k])) == MQC_HIP_OK) rc = finish(sl, jobs[k]);
     } else {
-        if ((rc = prepare(slots[0], jobs[0])) != MQC_HIP_OK) return bail(rc);
-        for (int k = 0; k < njobs; ++k) {
+        rc = prepare(ctx, plan, b, slots[0], jobs[0]);
+        for (int k = 0; k < njobs && rc == MQC_HIP_OK; ++k) {
             // chunk k+1's integrals go onto the other stream before the host starts iterating chunk k
-            if (k + 1 < njobs && (rc = prepare(slots[(k + 1) & 1], jobs[k + 1])) != MQC_HIP_OK) return bail(rc);
-            if ((rc = iterate_and_fetch(slots[k & 1], jobs[k])) != MQC_HIP_OK) return bail(rc);
-            std::vector<double>().swap(jobs[k].hx);
+            if (k + 1 < njobs) rc = prepare(ctx, plan, b, slots[(k + 1) & 1], jobs[k + 1]);
+            if (rc == MQC_HIP_OK) rc = finish(slots[k & 1], jobs[k]);
         }
+    }
+    if (rc != MQC_HIP_OK) {
+        // drain the streams before the error return hands the pools back
+        if (lane != 1) (void)hipStreamSynchronize(ctx->stream);
+        if (lane != 0) (void)hipStreamSynchronize(ctx->stream2);
     }
     (void)hipHostFree(h_counter);
-    sx->stats.t_total += now_s() - t_begin;
-    {
-        std::lock_guard<std::mutex> lock(ctx->stats_mutex);
-        Stats& g = ctx->stats;
-        const Stats& l = sx->stats;
-        g.t_setup += l.t_setup; g.t_int1e += l.t_int1e; g.t_eri += l.t_eri; g.t_fock += l.t_fock; g.t_scf_step += l.t_scf_step;
-        g.t_total += l.t_total; g.fock_launches += l.fock_launches; g.eri_quartets += l.eri_quartets;
-        g.scf_iterations_total += l.scf_iterations_total; g.fock_kernel_seconds += l.fock_kernel_seconds;
-        g.fock_bytes += l.fock_bytes; g.eri_kernel_seconds += l.eri_kernel_seconds;
-        g.xc_kernel_seconds += l.xc_kernel_seconds; g.xc_points += l.xc_points;
-        g.fock_big_launches += l.fock_big_launches; g.fock_big_seconds += l.fock_big_seconds; g.fock_big_bytes += l.fock_big_bytes;
-        g.xc_flops += l.xc_flops; g.scf_step_seconds += l.scf_step_seconds; g.eri_survivors += l.eri_survivors;
-        g.df_flops += l.df_flops; g.df_bytes += l.df_bytes;
-    }
+    if (rc != MQC_HIP_OK) return rc;
+    b.stats.t_total += now_s() - t_begin;
+    std::lock_guard<std::mutex> lock(ctx->stats_mutex);
+    ctx->stats += b.stats;
     return MQC_HIP_OK;
 }
 
@@ -1416,7 +1340,7 @@ int mqc_hip_scf_run_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_mol
     }
     auto run_one = [&](Work& w, int lane) {
         (void)hipSetDevice(ctx->device);
-        w.rc = run_batch(ctx, *w.topo, w.aux.get(), w.xyz, *opts, w.res, lane, w.guess.get(), &w.mol);
+        w.rc = run_batch(ctx, *w.topo, w.aux.get(), w.xyz, *opts, w.res, lane, w.guess.get(), w.mol);
         if (w.rc != MQC_HIP_OK) w.msg = mqc_hip_last_error();      // the error text is thread-local
     };
     if (work.size() >= 2 && ctx->concurrent_groups) {
@@ -1461,6 +1385,16 @@ struct StageBatch {
     BatchView bv{};
 };
 
+// the plan of a stage-level call: closed shell, no exchange-correlation, the tensor layout of a batch of ntot
+static BatchPlan stage_plan(const Topology& topo, int two_e, int ntot)
+{
+    BatchPlan p;
+    p.n = topo.nao; p.npair = topo.npair; p.natoms = topo.natoms;
+    p.two_e = two_e;
+    plan_layout(p, ntot, (int)topo.shells.size(), topo.lmax, false);
+    return p;
+}
+
 static int stage_setup(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, bool with_eri, StageBatch& sb)
 {
     if (!ctx || !mol || !bas) return fail(MQC_HIP_ERR_VALIDATION, "null argument");
@@ -1471,12 +1405,9 @@ static int stage_setup(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, cons
     if (with_eri && !incore_supported(sb.topo.nao)) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large for the in-core ERI path");
     rc = upload_topology(ctx, sb.topo, sb.td);
     if (rc != MQC_HIP_OK) return rc;
-    Slot sl0{0, ctx->stream, &ctx->pool_main, &ctx->pool_eri, &ctx->pool_misc, &ctx->pool_gridw, &ctx->pool_df,
-             ctx->ev0, ctx->ev1, ctx->ev2, ctx->ev3, ctx->evq0, ctx->evq1, nullptr, ctx->evs[0][0], ctx->evs[0][1]};
-    rc = carve_batch(ctx, sl0, sb.topo, sb.td, 1, with_eri, sb.bv);
+    rc = carve_slot(ctx, make_slot(ctx, 0, nullptr), stage_plan(sb.topo, with_eri ? TWO_E_INCORE : TWO_E_NONE, 1), sb.td, 1, sb.bv);
     if (rc != MQC_HIP_OK) return rc;
-    sb.bv.nocc = std::max(1, sb.topo.nelec / 2); sb.bv.exx = 1.0; sb.bv.Vxc = nullptr; sb.bv.xc = XcSpec(); sb.bv.xc.ncomp = 0;
-    sb.bv.naux = 0; sb.bv.unit = ctx->d_unit;
+    sb.bv.nocc = std::max(1, sb.topo.nelec / 2); sb.bv.exx = 1.0;
     HIP_CHECK_RET(hipMemcpy(sb.bv.xyz, mol->xyz, sizeof(double) * 3 * mol->n_atoms, hipMemcpyHostToDevice));
     HIP_CHECK_RET(hipMemset(sb.bv.istate, 0, sizeof(int) * 4));
     return MQC_HIP_OK;
@@ -1583,7 +1514,7 @@ int mqc_hip_coulomb_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_mol
     rc = upload_topology(ctx, topo, td);
     if (rc != MQC_HIP_OK) return rc;
     const int n = topo.nao;
-    const size_t nn = (size_t)n * n, np = (size_t)topo.npair;
+    const size_t nn = (size_t)n * n;
     // full mode: in-core (the packed tensor of every fragment of a chunk resident at once, chunks sized to the free HBM).
     // cross mode: the direct digest over the filtered lists -- no tensor at all, the few (leading | source) quartets
     // are contracted with the density as they are formed (Schwarz screening at 1e-12)
@@ -1591,23 +1522,21 @@ int mqc_hip_coulomb_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_mol
     const bool direct = cross && !cross_incore;
     if (!direct && !incore_supported(topo.nao)) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large for the in-core ERI path");
     if (topo.nao > 256) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large (n_ao <= 256)");
-    const size_t per_frag = sizeof(double) * (per_fragment_main_doubles(n, topo.natoms) + (direct ? 4 * nn : np * np));
+    const BatchPlan plan = stage_plan(topo, direct ? TWO_E_DIRECT : TWO_E_INCORE, (int)std::min<int64_t>(nfrag, 1 << 30));
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
     free_b += ctx->pool_main.capacity() + ctx->pool_eri.capacity();
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nfrag, 16384), (int64_t)((double)free_b * 0.7 / (double)per_frag)));
-    Slot sl0{0, ctx->stream, &ctx->pool_main, &ctx->pool_eri, &ctx->pool_misc, &ctx->pool_gridw, &ctx->pool_df,
-             ctx->ev0, ctx->ev1, ctx->ev2, ctx->ev3, ctx->evq0, ctx->evq1, nullptr, ctx->evs[0][0], ctx->evs[0][1]};
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nfrag, 16384), (int64_t)((double)free_b * 0.7 / (double)fragment_bytes(plan))));
+    const Slot sl0 = make_slot(ctx, 0, nullptr);
     std::vector<double> hx;
     for (int64_t start = 0; start < nfrag; start += chunk) {
         const int nf = (int)std::min<int64_t>(chunk, nfrag - start);
         BatchView bv{};
-        rc = carve_batch(ctx, sl0, topo, td, nf, !direct, bv);
+        rc = carve_slot(ctx, sl0, plan, td, nf, bv);
         if (rc != MQC_HIP_OK) return rc;
         // only J is read back: the direct digest skips its exchange updates when exx = 0; the in-core kernels
         // form K alongside J in the same pass over the tensor either way
-        bv.nocc = std::max(1, topo.nelec / 2); bv.exx = direct ? 0.0 : 1.0; bv.Vxc = nullptr; bv.xc = XcSpec(); bv.xc.ncomp = 0;
-        bv.naux = 0; bv.unit = ctx->d_unit;
+        bv.nocc = std::max(1, topo.nelec / 2); bv.exx = direct ? 0.0 : 1.0;
         hx.resize((size_t)nf * topo.natoms * 3);
         for (int f = 0; f < nf; ++f) std::memcpy(&hx[(size_t)f * topo.natoms * 3], mols[start + f].xyz, sizeof(double) * topo.natoms * 3);
         HIP_CHECK_RET(hipMemcpyAsync(bv.xyz, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, ctx->stream));

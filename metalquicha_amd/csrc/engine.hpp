@@ -244,6 +244,48 @@ struct Stats {
     double fock_big_seconds = 0, fock_big_bytes = 0;
     double xc_flops = 0, scf_step_seconds = 0, df_flops = 0, df_bytes = 0;
     int64_t eri_survivors = 0;
+    Stats& operator+=(const Stats& o)
+    {
+        t_setup += o.t_setup; t_int1e += o.t_int1e; t_eri += o.t_eri; t_fock += o.t_fock; t_scf_step += o.t_scf_step; t_total += o.t_total;
+        fock_launches += o.fock_launches; eri_quartets += o.eri_quartets; scf_iterations_total += o.scf_iterations_total;
+        fock_kernel_seconds += o.fock_kernel_seconds; fock_bytes += o.fock_bytes; eri_kernel_seconds += o.eri_kernel_seconds;
+        xc_kernel_seconds += o.xc_kernel_seconds; xc_points += o.xc_points;
+        fock_big_launches += o.fock_big_launches; fock_big_seconds += o.fock_big_seconds; fock_big_bytes += o.fock_big_bytes;
+        xc_flops += o.xc_flops; scf_step_seconds += o.scf_step_seconds; df_flops += o.df_flops; df_bytes += o.df_bytes;
+        eri_survivors += o.eri_survivors;
+        return *this;
+    }
+};
+
+// Everything a batch's stages and device layout depend on, decided once per batch call (engine.cpp, plan_batch)
+enum : int { TWO_E_INCORE = 0, TWO_E_DIRECT = 1, TWO_E_DF = 2, TWO_E_NONE = 3 };
+struct BatchPlan {
+    int n = 0, npair = 0, natoms = 0;
+    bool uhf = false;
+    int nalpha = 0, nbeta = 0, nocc = 0;
+    XcSpec xc;
+    bool rsh = false;                  // range-separated hybrid: a second in-core tensor of erf(omega r12)/r12
+    int two_e = TWO_E_INCORE;          // two-electron path: in-core tensor, direct digest (no tensor), density fitting;
+                                       // TWO_E_NONE: stage-level calls without two-electron work
+    int naux = 0;
+    bool eri_tri = false;              // in-core tensor in the triangular block layout, for every chunk of the batch
+    int npc = 0;                       // external point charges per fragment
+    bool hx = false;                   // the caller's h_extra matrices
+    int npts = 0, rad_pt = 0;          // quadrature points per fragment, points per tile of the radial cache
+    size_t rad_doubles = 0, pt4_doubles = 0;   // per fragment: radial cache and point buffer of the quadrature (0: none)
+    double stol = 0.0, direct_tol = 0.0;       // Schwarz thresholds of the in-core build and of the direct digest
+};
+
+// The device pools one chunk is carved from (a Slot holds one of each)
+enum : int { POOL_MAIN = 0, POOL_ERI, POOL_MISC, POOL_GRIDW, POOL_DF, NPOOL };
+struct ChunkBytes {
+    size_t pool[NPOOL] = {};
+    size_t total() const { size_t t = 0; for (size_t b : pool) t += b; return t; }
+};
+struct CarvedArray {
+    int pool;
+    const void* p;
+    size_t bytes;
 };
 
 }  // namespace mqc
@@ -286,10 +328,22 @@ void release_all_pools();
 // launcher state that holds streams/events of the context's device (kern_eri.hip); reset by mqc_hip_finalize
 void eri_reset_state();
 
-// true when the in-core J/K of a batch of this shape runs from the triangular tensor (kern_fock.hip); block length and
-// the per-block start of the short row
+// triangular J/K stream (kern_fock.hip, jk_tri_kernel): waves per workgroup, largest block in chunks of 128 doubles
+constexpr int JK_TRI_NW = 12, JK_TRI_MAXU2 = 10;
+// true when the in-core J/K of a batch of this shape runs from the triangular tensor; block length and the per-block
+// start of the short row; the kernel's LDS bytes (host_setup.cpp)
 bool jk_tri_layout(int n, int npair, int nfrag, bool uhf);
 int jk_tri_block(int npair, std::vector<int>* short_row_start = nullptr);
+size_t jk_tri_lds_bytes(int n, int npair);
+// the tensor layout and the quadrature buffers of a plan whose other fields are set, for a batch of ntot fragments
+void plan_layout(BatchPlan& p, int ntot, int nshell, int lmax, bool rad_cache);
+// The device arrays of one chunk of nfrag fragments: every array the plan needs, each rounded up to 256 bytes, carved
+// from the five pools at bases[POOL_*] into bv's pointers (with its shape: nfrag, n, npair, uhf, npc, naux, tensor
+// layout).  Returns the bytes each pool needs; bases == nullptr only sizes (the pointers are then offsets).  record
+// (optional) receives every array carved.  The block table of a triangular tensor is left for the caller to upload.
+ChunkBytes carve_chunk(const BatchPlan& p, int nfrag, char* const* bases, BatchView& bv, std::vector<CarvedArray>* record = nullptr);
+// bytes per fragment that bound every chunk: carve_chunk(p, nf) <= nf x this (+ the direct path's own J/K accumulators)
+size_t fragment_bytes(const BatchPlan& p);
 // host-side pieces (basis_norm.cpp, boys_table.cpp, batch.cpp)
 void set_error(const std::string& msg);
 int fail(int code, const std::string& msg);
@@ -299,11 +353,6 @@ int build_topology(const mqc_hip_molecule_t& mol, const mqc_hip_basis_t& bas, To
                    int max_l = KERNEL_LMAX, bool with_quartets = true);
 std::string topology_key(const mqc_hip_molecule_t& mol, const mqc_hip_basis_t& bas);
 double nuclear_repulsion(const Topology& topo, const double* xyz);
-
-// lane < 0: the batch owns both slots (chunks alternate, next chunk prepared ahead); lane 0/1: it runs on that
-// slot only, so that two topology groups can be driven by two host threads at once
-int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology* aux, const std::vector<const double*>& xyz,
-              const mqc_hip_scf_options_t& opts, std::vector<mqc_hip_scf_result_t*>& results, int lane = -1);
 
 // kernel launchers (kern_*.hip)
 void launch_int1e(const BatchView& bv, const Topology& topo, hipStream_t s);

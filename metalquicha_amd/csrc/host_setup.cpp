@@ -1,11 +1,14 @@
 // host_setup.cpp -- host-side preparation below the C ABI: contraction normalisation,
-// topology (shell, pair and quartet-class lists), the Boys table and cart->sph tables.
+// topology (shell, pair and quartet-class lists), the Boys table and cart->sph tables, and the
+// device layout of a batch chunk (carve_chunk: the one place every per-fragment array is sized).
 // Nothing here computes integrals or any part of an SCF; that is all on the device.
 #include "engine.hpp"
 #include "md_integrals.hpp"
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <sstream>
 
@@ -343,6 +346,141 @@ int build_topology(const mqc_hip_molecule_t& mol, const mqc_hip_basis_t& bas, To
         }
     }
     return MQC_HIP_OK;
+}
+
+// ---- device layout of a batch ------------------------------------------------------------
+// doubles per block: the padded long triangle plus the padded short one, worst row pair (even, so that blocks stay
+// 16-byte aligned); optionally where the short row starts in every block
+int jk_tri_block(int np, std::vector<int>* short_row_start)
+{
+    auto shell_row = [](int idx) { int k = (int)((std::sqrt(8.0 * idx + 1.0) - 1.0) * 0.5); while ((k + 1) * (k + 2) / 2 <= idx) ++k; while (k * (k + 1) / 2 > idx) --k; return k; };
+    const int npairs = (np + 1) / 2;
+    // table: [npairs] start of the short row in every block, then [np] the shell row i of every pair row (ij)
+    if (short_row_start) {
+        short_row_start->assign((size_t)npairs + np, 0);
+        for (int r = 0; r < np; ++r) (*short_row_start)[(size_t)npairs + r] = shell_row(r);
+    }
+    int worst = 0;
+    for (int t = 0; t < npairs; ++t) {
+        const int rl = np - 1 - t, il = shell_row(rl), is = shell_row(t);
+        const int sb = (il + 1) * (il + 2) / 2;
+        const int need = sb + (t < rl ? (is + 1) * (is + 2) / 2 : 0);
+        if (short_row_start) (*short_row_start)[t] = sb;
+        if (need > worst) worst = need;
+    }
+    return (worst + 1) & ~1;
+}
+
+size_t jk_tri_lds_bytes(int n, int np)
+{
+    // row buffers, packed D' and J (+ 2), Kh; zero-row flags, function -> shell map, per-wave maxima
+    return sizeof(double) * ((size_t)JK_TRI_NW * jk_tri_block(np) + 2 * ((size_t)np + 2) + (size_t)n * n) + (((size_t)np + 15) & ~(size_t)15) + 64 * sizeof(int) + JK_TRI_NW * sizeof(double);
+}
+
+// The triangular layout is taken for the batches the tuned square kernel served: restricted, dimer-sized fragments
+// (n <= 64, a multiple of 8; 640 < npair; a block within ten chunks of 128) in batches of at least 64.
+// MQC_HIP_ERI_TRI=0: the square.
+bool jk_tri_layout(int n, int np, int nfrag, bool uhf)
+{
+    static const bool on = [] { const char* e = std::getenv("MQC_HIP_ERI_TRI"); return !(e && e[0] == '0'); }();
+    if (!on || uhf || nfrag < 64 || n > 64 || n % 8 != 0 || np <= 10 * 64) return false;
+    if (jk_tri_block(np) > JK_TRI_MAXU2 * 128) return false;
+    return jk_tri_lds_bytes(n, np) <= (size_t)160 * 1024 - 1024;
+}
+
+void plan_layout(BatchPlan& p, int ntot, int nshell, int lmax, bool rad_cache)
+{
+    p.eri_tri = p.two_e == TWO_E_INCORE && jk_tri_layout(p.n, p.npair, ntot, p.uhf);
+    // radial cache of the quadrature: 2 doubles per shell and (padded) grid point; point buffer of the split quadrature
+    // (n <= 96, s-f shells, 32-point tiles): 4 doubles per padded grid point
+    p.rad_pt = xc_tile_points(p.n);
+    const size_t tiles = p.xc.ncomp > 0 ? ((size_t)p.npts + p.rad_pt - 1) / p.rad_pt : 0;
+    p.rad_doubles = (p.xc.ncomp > 0 && rad_cache && !p.uhf) ? tiles * (size_t)nshell * 2 * p.rad_pt : 0;
+    p.pt4_doubles = (p.rad_doubles && p.n <= 96 && lmax <= 3 && p.rad_pt == 32) ? tiles * p.rad_pt * 4 : 0;
+}
+
+ChunkBytes carve_chunk(const BatchPlan& p, int nfrag, char* const* bases, BatchView& bv, std::vector<CarvedArray>* record)
+{
+    const size_t nf = (size_t)nfrag, n = (size_t)p.n, nn = n * n, np = (size_t)p.npair;
+    ChunkBytes used;
+    auto take = [&](int pool, size_t bytes) -> void* {
+        const uintptr_t at = (uintptr_t)(bases ? bases[pool] : nullptr) + used.pool[pool];
+        used.pool[pool] += (bytes + 255) & ~size_t(255);
+        if (record) record->push_back({pool, (const void*)at, bytes});
+        return (void*)at;
+    };
+    auto doubles = [&](int pool, size_t count) { return (double*)take(pool, sizeof(double) * count); };
+    bv.nfrag = nfrag; bv.n = p.n; bv.npair = p.npair; bv.uhf = p.uhf ? 1 : 0; bv.npc = p.npc; bv.naux = p.naux;
+
+    // the SCF matrices: S H X F D C J K, W = 6 work matrices, the DIIS histories; beta spin: D C F J K Vprev, histories
+    bv.xyz = doubles(POOL_MAIN, nf * p.natoms * 3);
+    for (double** m : {&bv.S, &bv.H, &bv.X, &bv.F, &bv.D, &bv.C, &bv.J, &bv.K}) *m = doubles(POOL_MAIN, nf * nn);
+    bv.W = doubles(POOL_MAIN, nf * 6 * nn);
+    bv.Vprev = doubles(POOL_MAIN, nf * nn);
+    bv.diis_f = doubles(POOL_MAIN, nf * DIIS_MAX * nn);
+    bv.diis_e = doubles(POOL_MAIN, nf * DIIS_MAX * nn);
+    bv.diis_b = doubles(POOL_MAIN, nf * DIIS_MAX * DIIS_MAX);
+    bv.eps = doubles(POOL_MAIN, nf * n);
+    bv.scal = doubles(POOL_MAIN, nf * 8);
+    bv.dip = doubles(POOL_MAIN, nf * 4);
+    bv.Db = bv.Cb = bv.Fb = bv.Jb = bv.Kb = bv.Vprevb = bv.epsb = bv.diis_fb = bv.diis_eb = nullptr;
+    if (p.uhf) {
+        for (double** m : {&bv.Db, &bv.Cb, &bv.Fb, &bv.Jb, &bv.Kb, &bv.Vprevb}) *m = doubles(POOL_MAIN, nf * nn);
+        bv.diis_fb = doubles(POOL_MAIN, nf * DIIS_MAX * nn);
+        bv.diis_eb = doubles(POOL_MAIN, nf * DIIS_MAX * nn);
+        bv.epsb = doubles(POOL_MAIN, nf * n);
+    }
+    bv.diis_state = (int*)take(POOL_MAIN, sizeof(int) * nf * 2);
+    bv.istate = (int*)take(POOL_MAIN, sizeof(int) * nf * 4);
+    // embedding: the point charges (x, y, z, q), the operator U, the caller's h_extra
+    bv.pc = p.npc > 0 ? doubles(POOL_MAIN, nf * p.npc * 4) : nullptr;
+    bv.U = (p.npc > 0 || p.hx) ? doubles(POOL_MAIN, nf * nn) : nullptr;
+    bv.Hx = p.hx ? doubles(POOL_MAIN, nf * nn) : nullptr;
+
+    // counters (the quartet count of the integral stage at int 16); a triangular tensor's block table and read counters
+    bv.counters = (int*)take(POOL_MISC, 256);
+    bv.eri_count = (unsigned long long*)(bv.counters + 16);
+    bv.eri_tri = p.eri_tri ? 1 : 0;
+    bv.eri_tri_pb = p.eri_tri ? jk_tri_block(p.npair) : 0;
+    bv.eri_tri_sb = p.eri_tri ? (const int*)take(POOL_MISC, sizeof(int) * ((np + 1) / 2 + np)) : nullptr;
+    bv.jk_loaded = p.eri_tri ? (int*)take(POOL_MISC, sizeof(int) * nf) : nullptr;
+
+    // the in-core tensor, square or in triangular blocks; a range-separated hybrid's tensor of erf(omega r12)/r12 in
+    // the same layout, the J scratch of its J/K stream and K_lr of each spin
+    const bool incore = p.two_e == TWO_E_INCORE;
+    bv.eri_stride = !incore ? 0 : p.eri_tri ? (np + 1) / 2 * (size_t)bv.eri_tri_pb : np * np;
+    bv.eri = incore ? doubles(POOL_ERI, nf * bv.eri_stride) : nullptr;
+    const bool lr = incore && p.rsh;
+    bv.eri_lr = lr ? doubles(POOL_ERI, nf * bv.eri_stride) : nullptr;
+    bv.Jlr = lr ? doubles(POOL_ERI, nf * nn) : nullptr;
+    bv.Klr = lr ? doubles(POOL_ERI, nf * nn) : nullptr;
+    bv.Klrb = lr && p.uhf ? doubles(POOL_ERI, nf * nn) : nullptr;
+
+    // Kohn-Sham: grid weights, the V_xc accumulator of each spin, radial cache, point buffer
+    const bool ks = p.xc.ncomp > 0;
+    bv.grid.weights = ks ? doubles(POOL_GRIDW, nf * p.npts) : nullptr;
+    bv.Vxc = ks ? doubles(POOL_GRIDW, nf * nn * (p.uhf ? 2 : 1)) : nullptr;
+    bv.grid.rad = ks && p.rad_doubles ? doubles(POOL_GRIDW, nf * p.rad_doubles) : nullptr;
+    bv.grid.pt4 = ks && p.pt4_doubles ? doubles(POOL_GRIDW, nf * p.pt4_doubles) : nullptr;
+    if (ks) bv.grid.rad_pt = p.rad_pt;
+
+    // density fitting: (P|mu nu), the fitted tensor, the metric, its inverse root and the fit's scratch
+    const bool df = p.two_e == TWO_E_DF;
+    const size_t a3 = nf * p.naux * np, mm = nf * p.naux * p.naux;
+    bv.df_a3 = df ? doubles(POOL_DF, a3) : nullptr;
+    bv.df_b = df ? doubles(POOL_DF, a3) : nullptr;
+    bv.df_metric = df ? doubles(POOL_DF, mm) : nullptr;
+    bv.df_linv = df ? doubles(POOL_DF, mm) : nullptr;
+    bv.df_work = df ? doubles(POOL_DF, mm) : nullptr;
+    return used;
+}
+
+size_t fragment_bytes(const BatchPlan& p)
+{
+    BatchView probe{};
+    // each array of nf fragments is rounded up to 256 bytes once, so a chunk never needs more than nf single fragments;
+    // the direct path's launcher keeps its J and K accumulators in pools of its own
+    return carve_chunk(p, 1, nullptr, probe).total() + (p.two_e == TWO_E_DIRECT ? sizeof(double) * 2 * (size_t)p.n * p.n : 0);
 }
 
 double nuclear_repulsion(const Topology& topo, const double* xyz)

@@ -732,46 +732,6 @@ __global__ void __launch_bounds__(64 * NW) jk_tri_kernel(BatchView bv, int only_
     }
 }
 
-// doubles per block: the padded long triangle plus the padded short one, worst row pair (even, so that blocks stay
-// 16-byte aligned); optionally where the short row starts in every block
-int jk_tri_block(int np, std::vector<int>* short_row_start)
-{
-    auto shell_row = [](int idx) { int k = (int)((std::sqrt(8.0 * idx + 1.0) - 1.0) * 0.5); while ((k + 1) * (k + 2) / 2 <= idx) ++k; while (k * (k + 1) / 2 > idx) --k; return k; };
-    const int npairs = (np + 1) / 2;
-    // table: [npairs] start of the short row in every block, then [np] the shell row i of every pair row (ij)
-    if (short_row_start) {
-        short_row_start->assign((size_t)npairs + np, 0);
-        for (int r = 0; r < np; ++r) (*short_row_start)[(size_t)npairs + r] = shell_row(r);
-    }
-    int worst = 0;
-    for (int t = 0; t < npairs; ++t) {
-        const int rl = np - 1 - t, il = shell_row(rl), is = shell_row(t);
-        const int sb = (il + 1) * (il + 2) / 2;
-        const int need = sb + (t < rl ? (is + 1) * (is + 2) / 2 : 0);
-        if (short_row_start) (*short_row_start)[t] = sb;
-        if (need > worst) worst = need;
-    }
-    return (worst + 1) & ~1;
-}
-
-constexpr int JK_TRI_NW = 12, JK_TRI_MAXU2 = 10;
-static size_t jk_tri_lds_bytes(int n, int np)
-{
-    // row buffers, packed D' and J (+ 2), Kh; zero-row flags, function -> shell map, per-wave maxima
-    return sizeof(double) * ((size_t)JK_TRI_NW * jk_tri_block(np) + 2 * ((size_t)np + 2) + (size_t)n * n) + (((size_t)np + 15) & ~(size_t)15) + 64 * sizeof(int) + JK_TRI_NW * sizeof(double);
-}
-
-// The triangular layout is taken for the batches the tuned square kernel served: restricted, dimer-sized fragments
-// (n <= 64, a multiple of 8; 640 < npair; a block within ten chunks of 128) in batches of at least 64.
-// MQC_HIP_ERI_TRI=0: the square.
-bool jk_tri_layout(int n, int np, int nfrag, bool uhf)
-{
-    static const bool on = [] { const char* e = std::getenv("MQC_HIP_ERI_TRI"); return !(e && e[0] == '0'); }();
-    if (!on || uhf || nfrag < 64 || n > 64 || n % 8 != 0 || np <= 10 * 64) return false;
-    if (jk_tri_block(np) > JK_TRI_MAXU2 * 128) return false;
-    return jk_tri_lds_bytes(n, np) <= (size_t)160 * 1024 - 1024;
-}
-
 static int jk_grid_x(const BatchView& bv, int nw)
 {
     // enough workgroups to cover 256 CUs several times over, but few enough that the per-workgroup

@@ -217,6 +217,46 @@ int hostcheck_twin_cut(const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas
     return 0;
 }
 
+// carve_chunk for the plan of spec = {n, natoms, nshell, lmax, uhf, two_e, naux, rsh, npc, hx, ks, npts, rad_cache,
+// ntot}: the bytes of a chunk of nfrag fragments (a carve with null bases), then the carve into host buffers of exactly
+// those sizes.  nbad counts the arrays that fall outside their pool, are not 256-byte aligned or overlap another.
+int hostcheck_carve(const int* spec, int nfrag, unsigned long long* pool_bytes, unsigned long long* frag_bytes, int* eri_tri,
+                    unsigned long long* eri_stride, int* nbad)
+{
+    BatchPlan p;
+    p.n = spec[0]; p.npair = spec[0] * (spec[0] + 1) / 2; p.natoms = spec[1];
+    p.uhf = spec[4] != 0; p.two_e = spec[5]; p.naux = spec[6];
+    p.rsh = spec[7] != 0; p.xc.omega = p.rsh ? 0.3 : 0.0;
+    p.npc = spec[8]; p.hx = spec[9] != 0;
+    p.xc.ncomp = spec[10] ? 1 : 0; p.npts = spec[11];
+    plan_layout(p, spec[13], spec[2], spec[3], spec[12] != 0);
+    BatchView probe{};
+    const ChunkBytes need = carve_chunk(p, nfrag, nullptr, probe);
+    std::vector<std::vector<char>> mem(NPOOL);
+    char* bases[NPOOL];
+    for (int k = 0; k < NPOOL; ++k) {
+        mem[k].resize(need.pool[k] + 256);
+        bases[k] = mem[k].data() + (256 - (uintptr_t)mem[k].data() % 256) % 256;
+    }
+    BatchView bv{};
+    std::vector<CarvedArray> arrays;
+    const ChunkBytes got = carve_chunk(p, nfrag, bases, bv, &arrays);
+    *nbad = 0;
+    for (int k = 0; k < NPOOL; ++k) if (got.pool[k] != need.pool[k]) ++*nbad;
+    std::sort(arrays.begin(), arrays.end(), [](const CarvedArray& a, const CarvedArray& b) { return a.p < b.p; });
+    for (size_t i = 0; i < arrays.size(); ++i) {
+        const CarvedArray& a = arrays[i];
+        const char* lo = (const char*)a.p;
+        if ((uintptr_t)lo % 256 != 0 || lo < bases[a.pool] || lo + a.bytes > bases[a.pool] + need.pool[a.pool]) ++*nbad;
+        if (i + 1 < arrays.size() && lo + a.bytes > (const char*)arrays[i + 1].p) ++*nbad;
+    }
+    for (int k = 0; k < NPOOL; ++k) pool_bytes[k] = need.pool[k];
+    *frag_bytes = fragment_bytes(p);
+    *eri_tri = bv.eri_tri;
+    *eri_stride = bv.eri_stride;
+    return 0;
+}
+
 void hostcheck_boys(int L, double T, double* F)
 {
     ensure_tables();

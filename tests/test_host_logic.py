@@ -161,6 +161,72 @@ def test_topology_twin_cut_covers_every_quartet_once(hostcheck, zs, basis, expec
     assert (nent.value > 0) == (expect_twins > 0)
 
 
+# ---- device layout of a batch chunk (carve_chunk) ----------------------------------------------
+TWO_E = {"incore": 0, "direct": 1, "df": 2}
+# n, natoms, nshell, lmax of the fragments: STO-3G water, cc-pVDZ water and water dimer, larger cc-pVDZ clusters
+WATER_STO3G, WATER_DZ, DIMER_DZ, HEXAMER_DZ, N256 = (7, 3, 5, 1), (24, 3, 12, 2), (48, 6, 24, 2), (144, 18, 72, 2), (256, 32, 120, 2)
+CARVE_PLANS = {
+    "rhf_sto3g": dict(frag=WATER_STO3G),
+    "rhf_square": dict(frag=DIMER_DZ, ntot=8),
+    "rhf_triangular": dict(frag=DIMER_DZ, ntot=120),
+    "uhf_incore": dict(frag=DIMER_DZ, uhf=1, ntot=120),
+    "rsh_triangular": dict(frag=DIMER_DZ, rsh=1, ks=1, npts=20000, rad_cache=1, ntot=120),
+    "rsh_uhf": dict(frag=WATER_DZ, uhf=1, rsh=1, ks=1, npts=10000, rad_cache=1),
+    "ks_radial_and_points": dict(frag=DIMER_DZ, ks=1, npts=20000, rad_cache=1),
+    "ks_no_radial_cache": dict(frag=DIMER_DZ, ks=1, npts=20000, rad_cache=0),
+    "uks_direct": dict(frag=HEXAMER_DZ, uhf=1, two_e="direct", ks=1, npts=60000, rad_cache=1),
+    "direct_256": dict(frag=N256, two_e="direct", ks=1, npts=90000, rad_cache=1),
+    "df": dict(frag=DIMER_DZ, two_e="df", naux=232),
+    "df_uhf": dict(frag=WATER_DZ, two_e="df", naux=116, uhf=1, ks=1, npts=10000, rad_cache=1),
+    "point_charges": dict(frag=WATER_DZ, npc=300, ntot=512),
+    "h_extra": dict(frag=WATER_DZ, hx=1),
+    "point_charges_and_h_extra_direct": dict(frag=HEXAMER_DZ, two_e="direct", npc=50, hx=1),
+}
+
+
+def _carve(hostcheck, nfrag, frag, uhf=0, two_e="incore", naux=0, rsh=0, npc=0, hx=0, ks=0, npts=0, rad_cache=0, ntot=64):
+    u64 = ctypes.c_ulonglong
+    spec = np.array(list(frag) + [uhf, TWO_E[two_e], naux, rsh, npc, hx, ks, npts, rad_cache, ntot], dtype=np.int32)
+    pools, frag_bytes, stride = (u64 * 5)(), u64(), u64()
+    tri, nbad = ctypes.c_int(-1), ctypes.c_int(-1)
+    assert hostcheck.hostcheck_carve(spec.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), nfrag, pools, ctypes.byref(frag_bytes),
+                                     ctypes.byref(tri), ctypes.byref(stride), ctypes.byref(nbad)) == 0
+    return list(pools), frag_bytes.value, tri.value, stride.value, nbad.value
+
+
+@pytest.mark.parametrize("name", sorted(CARVE_PLANS))
+def test_chunk_carve_fits_its_pools_and_the_per_fragment_bound(hostcheck, name):
+    """Every array of a chunk lies inside the pool size carve_chunk reports for it, 256-B aligned, without overlaps,
+    and no chunk needs more than its fragment count times the per-fragment figure the chunk sizes come from."""
+    plan = CARVE_PLANS[name]
+    one, per_frag, _, _, nbad = _carve(hostcheck, 1, **plan)
+    assert nbad == 0
+    assert per_frag >= sum(one) > 0
+    for nf in (1, 50, 63, 64, 65, 200):
+        pools, _, _, _, nbad = _carve(hostcheck, nf, **plan)
+        assert nbad == 0, (name, nf)
+        assert sum(pools) <= nf * per_frag, (name, nf)
+        assert all(p <= nf * q for p, q in zip(pools, one)), (name, nf, pools, one)
+    if plan.get("two_e") in ("direct", "df"):
+        assert one[1] == 0                                 # no in-core tensor
+    if plan.get("two_e") != "df":
+        assert one[4] == 0
+    assert (one[3] > 0) == bool(plan.get("ks"))
+
+
+def test_every_chunk_takes_the_tensor_layout_of_its_batch(hostcheck):
+    """The layout is decided once per batch: a plan for 120 dimers gives its 50- and 200-fragment chunks the same
+    triangular stride as the whole batch; a batch of 8 and an unrestricted batch keep the square tensor."""
+    npair = DIMER_DZ[0] * (DIMER_DZ[0] + 1) // 2
+    _, _, tri, stride, _ = _carve(hostcheck, 120, DIMER_DZ, ntot=120)
+    assert tri == 1 and stride < npair * npair
+    for nf in (1, 50, 200):
+        assert _carve(hostcheck, nf, DIMER_DZ, ntot=120)[2:4] == (1, stride)
+    assert _carve(hostcheck, 64, DIMER_DZ, ntot=8)[2:4] == (0, npair * npair)
+    assert _carve(hostcheck, 64, DIMER_DZ, uhf=1, ntot=120)[2:4] == (0, npair * npair)
+    assert _carve(hostcheck, 64, DIMER_DZ, two_e="direct", ntot=120)[2:4] == (0, 0)
+
+
 # ---- MBE assembly ----------------------------------------------------------------------------
 def test_mbe_term_list_and_coefficients():
     system = mbe.water_cluster(2)
