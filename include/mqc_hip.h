@@ -204,6 +204,14 @@ int mqc_hip_eri_packed_attenuated(mqc_hip_context *ctx, const mqc_hip_molecule_t
 /* J[D], K[D] from the in-core tensor (build_fock, mqc_libcint_rhf.f90:1491-1574) */
 int mqc_hip_jk_incore(mqc_hip_context *ctx, const mqc_hip_molecule_t *mol, const mqc_hip_basis_t *orbital,
                       const double *D, double *J, double *K);
+/* J[D], K[D] of ONE fragment by the direct (integral-recomputing) build, no tensor (build_fock_direct,
+ * mqc_libcint_direct.f90:306-620): the Schwarz bounds, then the digest kernels over the unique shell quartets, n_ao <= 256.
+ * schwarz_tol is the density-weighted screen of that build (a quartet is kept iff
+ * Q_ab Q_cd deg max(max(Dab, Dcd)/2, (exx/8) max(Dac, Dad, Dbc, Dbd)) >= schwarz_tol; 0 keeps every quartet); exx is the
+ * exact-exchange fraction the screen weighs K with.  K is the plain exchange matrix, NOT scaled by exx.  exx = 0 skips the
+ * exchange digest: K is then written as all zeros (J is the same as for any other exx, up to the screen). */
+int mqc_hip_jk_direct(mqc_hip_context *ctx, const mqc_hip_molecule_t *mol, const mqc_hip_basis_t *orbital,
+                      double schwarz_tol, double exx, const double *D, double *J, double *K);
 /* symmetric eigen-decomposition by the engine's LDS Jacobi kernel: A (n x n) -> w ascending,
  * V columns = eigenvectors, row-major (diagonalize_fock_device, mqc_cuest_scf.f90:1132-1221) */
 /* J[D] for MANY fragments of ONE topology (same elements and basis, n geometries, n densities) in single launches:

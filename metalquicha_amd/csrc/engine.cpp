@@ -1395,7 +1395,8 @@ static BatchPlan stage_plan(const Topology& topo, int two_e, int ntot)
     return p;
 }
 
-static int stage_setup(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, bool with_eri, StageBatch& sb)
+static int stage_setup(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, bool with_eri, StageBatch& sb,
+                       int two_e = -1)
 {
     if (!ctx || !mol || !bas) return fail(MQC_HIP_ERR_VALIDATION, "null argument");
     HIP_CHECK_RET(hipSetDevice(ctx->device));
@@ -1405,7 +1406,8 @@ static int stage_setup(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, cons
     if (with_eri && !incore_supported(sb.topo.nao)) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large for the in-core ERI path");
     rc = upload_topology(ctx, sb.topo, sb.td);
     if (rc != MQC_HIP_OK) return rc;
-    rc = carve_slot(ctx, make_slot(ctx, 0, nullptr), stage_plan(sb.topo, with_eri ? TWO_E_INCORE : TWO_E_NONE, 1), sb.td, 1, sb.bv);
+    if (two_e < 0) two_e = with_eri ? TWO_E_INCORE : TWO_E_NONE;
+    rc = carve_slot(ctx, make_slot(ctx, 0, nullptr), stage_plan(sb.topo, two_e, 1), sb.td, 1, sb.bv);
     if (rc != MQC_HIP_OK) return rc;
     sb.bv.nocc = std::max(1, sb.topo.nelec / 2); sb.bv.exx = 1.0;
     HIP_CHECK_RET(hipMemcpy(sb.bv.xyz, mol->xyz, sizeof(double) * 3 * mol->n_atoms, hipMemcpyHostToDevice));
@@ -1466,6 +1468,30 @@ int mqc_hip_jk_incore(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const
     launch_eri(sb.bv, sb.topo, 0.0, ctx->stream);
     HIP_CHECK_RET(hipMemcpyAsync(sb.bv.D, D, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));
     launch_jk_incore(sb.bv, false, ctx->stream);
+    HIP_CHECK_RET(hipStreamSynchronize(ctx->stream));
+    HIP_CHECK_RET(hipGetLastError());
+    HIP_CHECK_RET(hipMemcpy(J, sb.bv.J, sizeof(double) * nn, hipMemcpyDeviceToHost));
+    HIP_CHECK_RET(hipMemcpy(K, sb.bv.K, sizeof(double) * nn, hipMemcpyDeviceToHost));
+    return MQC_HIP_OK;
+}
+
+// J and K of one fragment by the direct build: no tensor, the digest kernels over every unique quartet
+int mqc_hip_jk_direct(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, double schwarz_tol, double exx,
+                      const double* D, double* J, double* K)
+{
+    if (!D || !J || !K) return fail(MQC_HIP_ERR_VALIDATION, "null argument");
+    if (!(schwarz_tol >= 0.0) || !(exx >= 0.0) || !std::isfinite(schwarz_tol) || !std::isfinite(exx))
+        return fail(MQC_HIP_ERR_VALIDATION, "direct J/K: schwarz_tol and exx must be finite and not negative");
+    StageBatch sb;
+    int rc = stage_setup(ctx, mol, bas, false, sb, TWO_E_DIRECT);
+    if (rc != MQC_HIP_OK) return rc;
+    if (sb.topo.nao > 256) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large (n_ao <= 256)");
+    const size_t nn = (size_t)sb.topo.nao * sb.topo.nao;
+    sb.bv.exx = exx;
+    HIP_CHECK_RET(hipMemsetAsync(sb.bv.eri_count, 0, sizeof(unsigned long long), ctx->stream));
+    HIP_CHECK_RET(hipMemcpyAsync(sb.bv.D, D, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));
+    launch_direct_setup(sb.bv, sb.topo, ctx->stream);
+    launch_jk_direct(sb.bv, sb.topo, schwarz_tol, false, ctx->stream);
     HIP_CHECK_RET(hipStreamSynchronize(ctx->stream));
     HIP_CHECK_RET(hipGetLastError());
     HIP_CHECK_RET(hipMemcpy(J, sb.bv.J, sizeof(double) * nn, hipMemcpyDeviceToHost));

@@ -1,5 +1,5 @@
-"""Stage-level entry points of the C ABI (mqc_hip_int1e, _eri_packed, _jk_incore, _syev,
-_diis_coefficients) as numpy-in / numpy-out functions.  They run the same kernels the SCF
+"""Stage-level entry points of the C ABI (mqc_hip_int1e, _eri_packed, _eri_packed_attenuated, _jk_incore, _jk_direct,
+_coulomb_batch, _syev, _diis_coefficients) as numpy-in / numpy-out functions.  They run the same kernels the SCF
 driver launches and exist so that each row of the hot-path table can be parity-tested alone.
 Test infrastructure: a ctypes helper for tests/, not part of the product package."""
 from __future__ import annotations
@@ -35,6 +35,15 @@ def eri_packed(basis_set: str, fragment: PhysicalFragment, schwarz_tol: float = 
     return M
 
 
+def eri_packed_attenuated(basis_set: str, fragment: PhysicalFragment, omega: float, schwarz_tol: float = 0.0) -> np.ndarray:
+    m = _marshal(basis_set, fragment)
+    npair = m.fb.nao * (m.fb.nao + 1) // 2
+    M = np.zeros((npair, npair))
+    capi.check(capi.load_library().mqc_hip_eri_packed_attenuated(capi.get_context(), C.byref(m.mol), C.byref(m.bas),
+                                                                 C.c_double(omega), C.c_double(schwarz_tol), capi.dptr(M)))
+    return M
+
+
 def jk_incore(basis_set: str, fragment: PhysicalFragment, D: np.ndarray):
     m = _marshal(basis_set, fragment)
     n = m.fb.nao
@@ -42,6 +51,17 @@ def jk_incore(basis_set: str, fragment: PhysicalFragment, D: np.ndarray):
     J, K = np.zeros((n, n)), np.zeros((n, n))
     capi.check(capi.load_library().mqc_hip_jk_incore(capi.get_context(), C.byref(m.mol), C.byref(m.bas),
                                                      capi.dptr(D), capi.dptr(J), capi.dptr(K)))
+    return J, K
+
+
+def jk_direct(basis_set: str, fragment: PhysicalFragment, D: np.ndarray, schwarz_tol: float = 0.0, exx: float = 1.0):
+    """mqc_hip_jk_direct: J and K by the direct digest kernels.  K comes back as all NaN where the engine did not write it."""
+    m = _marshal(basis_set, fragment)
+    n = m.fb.nao
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    J, K = np.full((n, n), np.nan), np.full((n, n), np.nan)
+    capi.check(capi.load_library().mqc_hip_jk_direct(capi.get_context(), C.byref(m.mol), C.byref(m.bas), C.c_double(schwarz_tol),
+                                                     C.c_double(exx), capi.dptr(D), capi.dptr(J), capi.dptr(K)))
     return J, K
 
 

@@ -470,12 +470,6 @@ def test_jk_incore_larger_fragments_all_kernel_variants():
 
 
 # ---- Kohn-Sham: XC quadrature kernel -----------------------------------------------------------
-import json
-import os
-
-from metalquicha_amd.basis import ANGSTROM_TO_BOHR, SYMBOL_TO_Z
-from oracle import xc_oracle
-
 _CASES = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "manifest_subset.json")))["cases"]
 _KS = [c for c in _CASES if c["method"] == "dft" and c["functional"] in xc_oracle.RESTRICTED_FUNCTIONALS and "grid 3" in c["name"]
        and not c["unrestricted"] and not c["density_fitting"]]

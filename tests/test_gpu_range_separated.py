@@ -18,21 +18,13 @@ from oracle import scf_oracle as so
 from tests import range_separated_reference as rr
 from tests import stages
 from tests.helpers import fragment_bohr, oracle_mol, water_at
+from tests.stages import eri_packed_attenuated
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WATER = ([8, 1, 1], [[0.0, 0.0, -0.1364652], [0.0, 1.4304924, 1.0826636], [0.0, -1.4304924, 1.0826636]])
 OMEGA = rr.WB97X_OMEGA
-
-
-def eri_packed_attenuated(basis_set, fragment, omega, schwarz_tol=0.0):
-    m = stages._marshal(basis_set, fragment)
-    npair = m.fb.nao * (m.fb.nao + 1) // 2
-    M = np.zeros((npair, npair))
-    capi.check(capi.load_library().mqc_hip_eri_packed_attenuated(capi.get_context(), C.byref(m.mol), C.byref(m.bas),
-                                                                 C.c_double(omega), C.c_double(schwarz_tol), capi.dptr(M)))
-    return M
 
 
 @pytest.mark.parametrize("basis", ["6-31g", "cc-pvdz"])
