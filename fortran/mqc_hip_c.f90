@@ -98,7 +98,7 @@ module mqc_hip_c
 
    public :: mqc_hip_backend_available, mqc_hip_context_get, mqc_hip_finalize, mqc_hip_last_error, &
              mqc_hip_abi_version, mqc_hip_default_options, mqc_hip_scf_run, mqc_hip_scf_run_batch, &
-             mqc_hip_coulomb_batch
+             mqc_hip_coulomb_batch, mqc_hip_esp_batch
 
    interface
       function mqc_hip_backend_available() bind(C, name="mqc_hip_backend_available") result(r)
@@ -161,6 +161,23 @@ module mqc_hip_c
          integer(c_int32_t), value :: n_source_atoms
          real(c_double), intent(in) :: d(*)
          real(c_double), intent(inout) :: j(*)
+         integer(c_int) :: r
+      end function
+      !! electrostatic potential of n densities (one topology) at their own points: esp(max_points, n); n_points is
+      !! c_null_ptr (max_points each) or c_loc of an int32 array of n counts; points(3, max_points, n) in Bohr
+      function mqc_hip_esp_batch(ctx, n, mols, orbital, d, max_points, n_points, points, include_nuclei, esp) &
+         bind(C, name="mqc_hip_esp_batch") result(r)
+         import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double, mqc_hip_molecule_t, mqc_hip_basis_t
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: n
+         type(mqc_hip_molecule_t), intent(in) :: mols(*)
+         type(mqc_hip_basis_t), intent(in) :: orbital
+         real(c_double), intent(in) :: d(*)
+         integer(c_int32_t), value :: max_points
+         type(c_ptr), value :: n_points
+         real(c_double), intent(in) :: points(*)
+         integer(c_int32_t), value :: include_nuclei
+         real(c_double), intent(inout) :: esp(*)
          integer(c_int) :: r
       end function
       !! packed in-core ERI matrix of erf(omega r12)/r12, m(npair*npair) with pair(i,j) = i(i+1)/2 + j (0-based, i >= j)

@@ -225,6 +225,22 @@ int mqc_hip_jk_direct(mqc_hip_context *ctx, const mqc_hip_molecule_t *mol, const
 int mqc_hip_coulomb_batch(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip_molecule_t *mols,
                           const mqc_hip_basis_t *orbital, int32_t n_source_atoms, const double *D, double *J);
 
+/* Electrostatic potential of converged (or any) densities at arbitrary points, for MANY fragments of ONE topology:
+ *     V(r) = sum_A Z_A / |r - R_A|  -  sum_{mu nu} D_{mu nu} (mu| 1/|r' - r| |nu)          (ghost atoms: Z = 0)
+ * the quantity behind ESP maps and potential-fitted (CHELPG) charges.  D is [n][n_ao*n_ao] row-major (symmetric), points
+ * is [n][3*max_points] (x, y, z per point, Bohr), esp is [n][max_points].  Point counts may be ragged: n_points[i] <=
+ * max_points points of fragment i are used (NULL = max_points each); entries beyond a fragment's count are neither read
+ * nor written.  include_nuclei = 0 returns the electronic part alone (minus sign included); a point on a nucleus is
+ * then legal.  n_ao <= 256, s-f shells; fragments are processed in chunks sized to the free HBM.
+ * MQC_HIP_ERR_VALIDATION: non-finite coordinates, a negative count or one above max_points, a fragment whose elements
+ * differ from the first's, or -- with include_nuclei = 1 -- a point within 1e-10 Bohr of a nucleus with Z > 0.
+ * max_points = 0 or n_fragments = 0 returns MQC_HIP_OK and writes nothing.  (Added without an ABI bump: no struct changed.) */
+int mqc_hip_esp_batch(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip_molecule_t *mols,
+                      const mqc_hip_basis_t *orbital, const double *D /* [n][n_ao*n_ao] */,
+                      int32_t max_points, const int32_t *n_points /* [n] or NULL = max_points each */,
+                      const double *points /* [n][3*max_points], Bohr */, int32_t include_nuclei,
+                      double *esp /* [n][max_points] */);
+
 int mqc_hip_syev(mqc_hip_context *ctx, int32_t n, const double *A, double *w, double *V);
 /* DIIS coefficients from an age-ordered overlap matrix, the device routine's algorithm
  * (diis_coefficients/solve_diis, src/methods/mqc_diis.f90:164-273) */

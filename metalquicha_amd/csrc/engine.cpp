@@ -29,6 +29,12 @@ void int1e_reset_state();                                                 // ker
 void eri_schwarz_view(int slot, const double** q, double* thresh);        // kern_eri.hip
 void launch_jk_direct_incremental(const BatchView& bv, const Topology& topo, double thresh, bool only_active, hipStream_t s);   // kern_eri.hip
 static DevicePool g_grad_pool[2];
+// kern_esp.hip: potential of nfrag densities at their points (device arrays of one chunk); doubles of records per fragment
+void launch_esp(const TopologyDev& td, const Topology& topo, const double* boys_table, const double* c2s, int nfrag, const double* d_xyz,
+                const double* d_D, double* d_rec, const double* d_pts, const int* d_npts, int max_points, int include_nuclei, double* d_out,
+                hipStream_t s);
+size_t esp_record_doubles(const Topology& topo);
+static DevicePool g_esp_pool;
 
 static int stage_check(const char* stage)
 {
@@ -1581,6 +1587,100 @@ int mqc_hip_coulomb_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_mol
         HIP_CHECK_RET(hipStreamSynchronize(ctx->stream));
         HIP_CHECK_RET(hipGetLastError());
         HIP_CHECK_RET(hipMemcpy(J + (size_t)start * nn, bv.J, sizeof(double) * nn * nf, hipMemcpyDeviceToHost));
+    }
+    return MQC_HIP_OK;
+}
+
+// V(r) = sum_A Z_A/|r - R_A| - tr(D u_r) at the points of every fragment (kern_esp.hip).  Validation first (nothing is
+// written on a refusal), then chunks of fragments sized to the free HBM: geometry, densities and points up, the
+// primitive-pair records formed on the device, the point kernels, the potentials back.
+int mqc_hip_esp_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols, const mqc_hip_basis_t* bas, const double* D,
+                      int32_t max_points, const int32_t* n_points, const double* points, int32_t include_nuclei, double* esp)
+{
+    if (!ctx || nfrag < 0 || max_points < 0) return fail(MQC_HIP_ERR_VALIDATION, "esp batch: null context or negative count");
+    if (n_points)
+        for (int64_t i = 0; i < nfrag; ++i)
+            if (n_points[i] < 0 || n_points[i] > max_points)
+                return fail(MQC_HIP_ERR_VALIDATION, "esp batch: n_points[" + std::to_string(i) + "] = " + std::to_string(n_points[i]) +
+                                                        " is outside 0 .. max_points");
+    if (nfrag == 0 || max_points == 0) return MQC_HIP_OK;
+    if (!mols || !bas || !D || !points || !esp) return fail(MQC_HIP_ERR_VALIDATION, "null argument");
+    HIP_CHECK_RET(hipSetDevice(ctx->device));
+    const int na = mols[0].n_atoms;
+    for (int64_t i = 0; i < nfrag; ++i) {
+        if (!mols[i].atomic_numbers || !mols[i].xyz || mols[i].n_atoms != na ||
+            std::memcmp(mols[i].atomic_numbers, mols[0].atomic_numbers, sizeof(int32_t) * na) != 0 || mols[i].ghost != mols[0].ghost)
+            return fail(MQC_HIP_ERR_VALIDATION, "esp batch: every fragment must have the elements of the first (one topology per call)");
+        for (int k = 0; k < 3 * na; ++k)
+            if (!std::isfinite(mols[i].xyz[k])) return fail(MQC_HIP_ERR_VALIDATION, "esp batch: non-finite atomic coordinate in fragment " + std::to_string(i));
+    }
+    Topology topo;
+    std::string err;
+    int rc = build_topology(mols[0], *bas, topo, err, KERNEL_LMAX, false);
+    if (rc != MQC_HIP_OK) return fail(rc, err);
+    if (topo.nao > 256) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large (n_ao <= 256)");
+    const size_t mp = (size_t)max_points;
+    for (int64_t i = 0; i < nfrag; ++i) {
+        const int np = n_points ? n_points[i] : max_points;
+        const double* p = points + (size_t)i * 3 * mp;
+        for (int k = 0; k < 3 * np; ++k)
+            if (!std::isfinite(p[k])) return fail(MQC_HIP_ERR_VALIDATION, "esp batch: non-finite coordinate of point " + std::to_string(k / 3) + " of fragment " + std::to_string(i));
+        if (!include_nuclei) continue;
+        for (int a = 0; a < na; ++a) {
+            if (topo.zeff[a] == 0.0) continue;
+            const double* r = mols[i].xyz + 3 * a;
+            for (int k = 0; k < np; ++k) {
+                const double dx = p[3 * k] - r[0], dy = p[3 * k + 1] - r[1], dz = p[3 * k + 2] - r[2];
+                if (dx * dx + dy * dy + dz * dz < 1.0e-20)
+                    return fail(MQC_HIP_ERR_VALIDATION, "esp batch: point " + std::to_string(k) + " of fragment " + std::to_string(i) +
+                                                            " lies on nucleus " + std::to_string(a) + " (the nuclear potential diverges; include_nuclei = 0 gives the electronic part)");
+            }
+        }
+    }
+    TopologyDev td;
+    rc = upload_topology(ctx, topo, td);
+    if (rc != MQC_HIP_OK) return rc;
+    const size_t nn = (size_t)topo.nao * topo.nao, rec = esp_record_doubles(topo);
+    auto up = [](size_t doubles) { return (doubles + 31) & ~size_t(31); };     // every array starts on 256 bytes
+    const size_t per_frag = sizeof(double) * (up(3 * (size_t)na) + nn + rec + up(3 * mp) + up(mp) + 32) + 64;
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    free_b += g_esp_pool.capacity();
+    // MQC_HIP_ESP_CHUNK: a smaller cap on the fragments of one chunk (memory-tight hosts; the tests cross a chunk boundary with it)
+    int64_t cap = 16384;
+    if (const char* e = std::getenv("MQC_HIP_ESP_CHUNK")) cap = std::max(1, std::min(16384, std::atoi(e)));
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nfrag, cap), (int64_t)((double)free_b * 0.7 / (double)per_frag)));
+    std::vector<double> hx, hout;
+    std::vector<int> hn;
+    for (int64_t start = 0; start < nfrag; start += chunk) {
+        const int nf = (int)std::min<int64_t>(chunk, nfrag - start);
+        const size_t n_xyz = up((size_t)nf * 3 * na), n_D = up((size_t)nf * nn), n_rec = (size_t)nf * rec, n_pts = up((size_t)nf * 3 * mp),
+                     n_out = up((size_t)nf * mp);
+        double* base = (double*)g_esp_pool.ensure(sizeof(double) * (n_xyz + n_D + n_rec + n_pts + n_out) + sizeof(int) * ((size_t)nf + 64));
+        if (!base) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (esp batch)");
+        double *d_xyz = base, *d_D = d_xyz + n_xyz, *d_rec = d_D + n_D, *d_pts = d_rec + n_rec, *d_out = d_pts + n_pts;
+        int* d_np = (int*)(d_out + n_out);
+        hx.resize((size_t)nf * 3 * na); hn.resize(nf);
+        for (int f = 0; f < nf; ++f) {
+            std::memcpy(&hx[(size_t)f * 3 * na], mols[start + f].xyz, sizeof(double) * 3 * na);
+            hn[f] = n_points ? n_points[start + f] : max_points;
+        }
+        HIP_CHECK_RET(hipMemcpyAsync(d_xyz, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_CHECK_RET(hipMemcpyAsync(d_np, hn.data(), sizeof(int) * hn.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_CHECK_RET(hipMemcpyAsync(d_D, D + (size_t)start * nn, sizeof(double) * nn * nf, hipMemcpyHostToDevice, ctx->stream));
+        // a fragment's points beyond its count are not touched on the host: each fragment's live part goes up on its own
+        const bool full = std::all_of(hn.begin(), hn.end(), [&](int v) { return v == max_points; });
+        if (full) HIP_CHECK_RET(hipMemcpyAsync(d_pts, points + (size_t)start * 3 * mp, sizeof(double) * 3 * mp * nf, hipMemcpyHostToDevice, ctx->stream));
+        for (int f = 0; f < nf && !full; ++f)
+            if (hn[f] > 0)
+                HIP_CHECK_RET(hipMemcpyAsync(d_pts + (size_t)f * 3 * mp, points + (size_t)(start + f) * 3 * mp, sizeof(double) * 3 * hn[f],
+                                             hipMemcpyHostToDevice, ctx->stream));
+        launch_esp(td, topo, ctx->d_boys, ctx->d_c2s, nf, d_xyz, d_D, d_rec, d_pts, d_np, max_points, include_nuclei ? 1 : 0, d_out, ctx->stream);
+        HIP_CHECK_RET(hipStreamSynchronize(ctx->stream));
+        HIP_CHECK_RET(hipGetLastError());
+        hout.resize((size_t)nf * mp);
+        HIP_CHECK_RET(hipMemcpy(hout.data(), d_out, sizeof(double) * hout.size(), hipMemcpyDeviceToHost));
+        for (int f = 0; f < nf; ++f) std::memcpy(esp + (size_t)(start + f) * mp, &hout[(size_t)f * mp], sizeof(double) * hn[f]);
     }
     return MQC_HIP_OK;
 }

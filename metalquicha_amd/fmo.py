@@ -26,8 +26,14 @@ bookkeeping the reference's Fortran host code does:
 * `esp = "none"` is the plain many-body expansion through this driver; `far_field = "ignore"` drops the distant
   fragments from the field instead of approximating them (:1119-1124).
 
-Scope: whole-molecule fragments (no severed bonds, caps or AFO projector), closed shells, Mulliken or ignored far field
--- CHELPG charges stay with the reference.
+* `far_field = "chelpg"`: wherever a Mulliken charge stands for an outside atom (every field atom for `esp = "ptc"`, the
+  far fragments for `esp = "exact"`) a potential-fitted charge takes its place: after every monomer pass the `charges`
+  callable gets all fragments of the pass with their densities, by default `charges.hip_chelpg_charges` (the engine's
+  potential on a CHELPG grid per monomer, ONE `mqc_hip_esp_batch` call per element sequence).  Published CHELPG
+  defaults; parity with the reference's own variant is not claimed (charges.py).
+
+Scope: whole-molecule fragments (no severed bonds, caps or AFO projector), closed shells; Mulliken, CHELPG or ignored
+far field.
 """
 from __future__ import annotations
 
@@ -63,6 +69,8 @@ class EmbeddedResult:
 Solver = Callable[[Sequence[EmbeddedJob]], List[EmbeddedResult]]
 CoulombRequest = Tuple[Sequence[int], Sequence[int], np.ndarray]      # (atoms, neighbour's atoms, neighbour's density)
 Coulomb = Callable[[Sequence[CoulombRequest]], List[np.ndarray]]      # -> J[D_K] in the basis of `atoms`, one per request
+ChargeRequest = Tuple[Sequence[int], np.ndarray]                      # (atoms of a fragment, its density)
+Charges = Callable[[Sequence[ChargeRequest]], List[np.ndarray]]       # -> one charge per atom of `atoms`, one array per request
 
 # Bondi's van der Waals radii with Rowland and Taylor's hydrogen, Angstrom, Z = 1..18 (src/core/mqc_elements.f90:58-60)
 VDW_ANGSTROM = (1.10, 1.40, 1.81, 1.53, 1.92, 1.70, 1.55, 1.52, 1.47, 1.54, 2.27, 1.73, 1.84, 2.10, 1.80, 1.80, 1.75, 1.88)
@@ -197,7 +205,7 @@ class FmoRun:
     response_sum: float
     outer_iterations: int
     converged: bool
-    charges: np.ndarray                        # Mulliken charge of every atom of the system, in the settled field
+    charges: np.ndarray                        # charge of every atom of the system in the settled field (Mulliken, or the far-field model's)
     pair_corrections: Dict[Tuple[int, ...], float] = field(default_factory=dict)   # dE_S of every n-mer, |S| >= 2
     scf_iterations: int = 0
     errors: List[str] = field(default_factory=list)
@@ -207,27 +215,37 @@ def run_fmo2(system: FragmentedSystem, settings: ScfSettings, expansion: str = "
              outer_tol: float = 1.0e-7, rank: int = 0, world: int = 1,
              allreduce: Optional[Callable[[np.ndarray], np.ndarray]] = None, solver: Optional[Solver] = None,
              esp: str = "ptc", resppc: float = 2.0, coulomb: Optional[Coulomb] = None, level: int = 2,
-             far_field: str = "mulliken") -> FmoRun:
+             far_field: str = "mulliken", charges: Optional[Charges] = None) -> FmoRun:
     """FMO2 ("fmo") or electrostatically embedded MBE2 ("mbe") of whole-molecule fragments; the field of the others is
     Mulliken point charges (`esp = "ptc"`) or, for fragments within `resppc`, bare nuclei plus the exact Coulomb
     operator of their electrons (`esp = "exact"`, the reference's FMO default).
 
     With `world` > 1 every rank runs this on the same system, solves the fragments / pairs with index = rank (mod world)
     and `allreduce` (element-wise SUM over ranks of a float64 array) is the one exchange per pass.  `level` is the
-    largest n-mer (2 = FMO2; at level = number of fragments the corrections telescope to the supermolecular energy)."""
+    largest n-mer (2 = FMO2; at level = number of fragments the corrections telescope to the supermolecular energy).
+
+    `far_field = "chelpg"` takes the charges that stand for outside atoms from `charges` (all fragments of a pass with
+    their densities in one call; default: the engine-backed `charges.hip_chelpg_charges`) instead of the SCF's Mulliken
+    charges; the exchange between ranks carries whatever that model produced."""
     if expansion not in ("fmo", "mbe"):
         raise ValueError("expansion must be 'fmo' or 'mbe'")
     if world > 1 and allreduce is None:
         raise ValueError("several ranks need an allreduce")
     if esp not in ("ptc", "exact", "none"):
         raise ValueError("esp must be 'ptc', 'exact' or 'none'")
-    if far_field not in ("mulliken", "ignore"):
-        raise ValueError("far_field must be 'mulliken' or 'ignore' (CHELPG charges are not built)")
+    if far_field not in ("mulliken", "ignore", "chelpg"):
+        raise ValueError("far_field must be 'mulliken', 'chelpg' or 'ignore'")
+    if charges is not None and far_field != "chelpg":
+        raise ValueError("a charges callable is only used with far_field = 'chelpg'")
     solve = solver or hip_solver(system, settings)
     cutoff = resppc if esp == "exact" else 0.0                  # effective_resppc, :1032-1045
     exact = esp == "exact" and cutoff != 0.0
     if exact and coulomb is None:
         coulomb = hip_cross_coulomb(system, settings)
+    fitted = far_field == "chelpg" and esp != "none"
+    if fitted and charges is None:
+        from .charges import hip_chelpg_charges
+        charges = hip_chelpg_charges(system, settings)
     z_all = np.asarray(system.element_numbers)
     share = allreduce if world > 1 else (lambda a: a)
     n_atoms, nfrag = len(system.element_numbers), system.n_monomers
@@ -291,11 +309,18 @@ def run_fmo2(system: FragmentedSystem, settings: ScfSettings, expansion: str = "
         monomer_jobs = [EmbeddedJob(frags[i]) for i in mine] if (bare or esp == "none") else embedded_jobs([[i] for i in mine])
         res = solve(monomer_jobs)
         new_e = np.zeros(nfrag); new_i = np.zeros(nfrag); new_q = np.zeros(n_atoms)
+        model_q: Dict[int, np.ndarray] = {}
+        if fitted:
+            # the far-field model's charges of this rank's fragments, all of the pass in one request
+            done = [(i, r) for i, r in zip(mine, res) if not r.error]
+            if done:
+                for (i, _), q in zip(done, charges([(frags[i], r.density) for i, r in done])):
+                    model_q[i] = np.asarray(q, dtype=np.float64)
         for i, r in zip(mine, res):
             if r.error:
                 errors.append("fragment %d: %s" % (i, r.error)); continue
             new_e[i] = r.e_total; new_i[i] = r.e_total - r.e_embedding
-            new_q[list(frags[i])] = r.charges
+            new_q[list(frags[i])] = model_q[i] if fitted else r.charges
             dens[i] = r.density; nao[i] = r.density.shape[0]
             total_iters += r.iterations
         e_total[:] = share(new_e); e_int[:] = share(new_i); q_all[:] = share(new_q)

@@ -8,6 +8,7 @@
   hip_backend_available <- cuest_backend_available (:20-30)
   HFMethod.calc_energy  <- hf_calc_energy / hf_run (src/methods/mqc_method_hf.F90:113-217)
   run_hip_scf_batch   <- the batch-submit entry the worker loop would use
+  run_hip_esp         <- (no counterpart) the potential of converged densities at arbitrary points (mqc_hip_esp_batch)
 
 Same names, argument meaning and error behaviour; the numerics all happen in libmqc_hip.so.
 """
@@ -446,6 +447,51 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
     for m in sizes:
         out.append(rec[lo:lo + m])
         lo += m
+    return out
+
+
+def run_hip_esp(settings: ScfSettings, group: FragmentGroup, densities, points, n_points=None,
+                include_nuclei: bool = True, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """Electrostatic potential V(r) = sum_A Z_A/|r - R_A| - sum D_uv (u|1/|r' - r||v) of the m fragments of one group at
+    their own points, in ONE mqc_hip_esp_batch call.
+
+    densities (m, n_ao, n_ao); points (m, max_points, 3) in Bohr; n_points (m,) or None = max_points each (ragged
+    counts: entries of `points` beyond a fragment's count are not read, and the matching entries of the result stay as
+    they were: 0, or what the caller's `out` (m, max_points) held).  include_nuclei = False gives the electronic part
+    alone.  -> (m, max_points) in Hartree per unit charge."""
+    xyz = np.ascontiguousarray(group.xyz, dtype=np.float64)
+    z = np.ascontiguousarray(group.element_numbers, dtype=np.int32)
+    m, na = int(xyz.shape[0]), int(len(z))
+    if xyz.shape != (m, na, 3):
+        raise ValueError("FragmentGroup.xyz must be (m, n_atoms, 3) in Bohr")
+    fb = _flat_basis_z(settings.basis_set, z)
+    D = np.ascontiguousarray(densities, dtype=np.float64)
+    if D.shape != (m, fb.nao, fb.nao):
+        raise ValueError("densities must be (m, n_ao, n_ao)")
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.ndim != 3 or pts.shape[0] != m or pts.shape[2] != 3:
+        raise ValueError("points must be (m, max_points, 3) in Bohr")
+    max_points = int(pts.shape[1])
+    counts = None if n_points is None else np.ascontiguousarray(n_points, dtype=np.int32)
+    if counts is not None and counts.shape != (m,):
+        raise ValueError("n_points must be (m,)")
+    if out is None:
+        out = np.zeros((m, max_points))
+    elif out.shape != (m, max_points) or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"]:
+        raise ValueError("out must be a C-contiguous float64 array of shape (m, max_points)")
+    lib = capi.load_library()
+    ctx = capi.get_context(settings.device_rank)
+    ghost = None if group.ghost is None else np.ascontiguousarray(group.ghost, dtype=np.uint8)
+    mols = np.zeros(max(m, 1), dtype=_MOL_DTYPE)
+    mols["n_atoms"] = na; mols["atomic_numbers"] = z.ctypes.data
+    mols["xyz"][:m] = xyz.ctypes.data + np.arange(m, dtype=np.uint64) * np.uint64(na * 3 * 8)
+    mols["ghost"] = 0 if ghost is None else ghost.ctypes.data
+    mols["multiplicity"] = 1
+    mols["nelec"] = int(np.sum(z if ghost is None else z[ghost == 0]))
+    bas = np.zeros(1, dtype=_BAS_DTYPE); bas[0] = _basis_record(fb, na)
+    capi.check(lib.mqc_hip_esp_batch(ctx, m, mols.ctypes.data_as(C.POINTER(capi.Molecule)), bas.ctypes.data_as(C.POINTER(capi.Basis)),
+                                     capi.dptr(D), max_points, None if counts is None else counts.ctypes.data_as(capi.c_int32_p),
+                                     capi.dptr(pts), 1 if include_nuclei else 0, capi.dptr(out)))
     return out
 
 
