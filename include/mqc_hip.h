@@ -241,6 +241,22 @@ int mqc_hip_esp_batch(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip_m
                       const double *points /* [n][3*max_points], Bohr */, int32_t include_nuclei,
                       double *esp /* [n][max_points] */);
 
+/* The exchange-correlation quadrature of GIVEN densities, for MANY fragments of ONE topology: what one SCF iteration's
+ * quadrature stage computes, alone.  The call takes the plan of an SCF batch of n_fragments with this functional (spin,
+ * two-electron path, radial cache, point buffer: the same device layout), builds the grid and the Becke weights, fills the
+ * radial cache where the plan has one and runs the SCF driver's own dispatch once.  Per fragment: e_xc, the integrated
+ * electron number, and V_xc = A + A^T of the kernels' accumulator A, as the Fock assembly forms it.
+ * Restricted: D and V_xc are [n][n_ao*n_ao] (D the total density).  unrestricted != 0: [n][2][n_ao*n_ao], alpha then beta
+ * (spin densities C_s C_s^T, not doubled); an open-shell molecule needs unrestricted != 0.  Range-separated functionals:
+ * the semi-local grid part only (K_lr belongs to the J/K stage).  The accumulator is poisoned before the launch and its
+ * neighbours in the pool are compared before and after (MQC_HIP_ERR_DEVICE when the quadrature wrote outside).
+ * Refused with the SCF's own codes: whatever an SCF of these settings refuses (n_ao > 256, meta-GGA or unrestricted
+ * above 140, more than 64 atoms, unknown functional); MQC_HIP_ERR_VALIDATION: null pointers, n_fragments < 1, a
+ * functional without a grid part, fragments of different elements.  (Added without an ABI bump: no struct changed.) */
+int mqc_hip_xc_batch(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip_molecule_t *mols,
+                     const mqc_hip_basis_t *orbital, const char *functional, int32_t grid_level, int32_t unrestricted,
+                     const double *D, double *e_xc /* [n] */, double *n_electrons /* [n] */, double *V_xc);
+
 int mqc_hip_syev(mqc_hip_context *ctx, int32_t n, const double *A, double *w, double *V);
 /* DIIS coefficients from an age-ordered overlap matrix, the device routine's algorithm
  * (diis_coefficients/solve_diis, src/methods/mqc_diis.f90:164-273) */

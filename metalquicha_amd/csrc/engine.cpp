@@ -315,6 +315,13 @@ struct Job {
     std::vector<double> hx, hpc;
 };
 
+// radial cache of the quadrature: MQC_HIP_XC_RADIAL_CACHE=0 turns it off
+static bool xc_radial_cache_on()
+{
+    static const bool on = [] { const char* e = std::getenv("MQC_HIP_XC_RADIAL_CACHE"); return !(e && e[0] == '0'); }();
+    return on;
+}
+
 // ---- exchange-correlation: per-element grid templates and the per-topology point list
 static int upload_grid(mqc_hip_context* ctx, Batch& b, DevicePool& pool, hipStream_t s)
 {
@@ -879,9 +886,7 @@ static int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology*
     }
     if (plan.xc.ncomp > 0 && (rc = upload_grid(ctx, b, second ? ctx->pool_grid2 : ctx->pool_grid, lane_stream)) != MQC_HIP_OK) return rc;
     plan.npts = b.grid.npts;
-    // radial cache of the quadrature: MQC_HIP_XC_RADIAL_CACHE=0 turns it off
-    static const bool rad_cache_on = [] { const char* e = std::getenv("MQC_HIP_XC_RADIAL_CACHE"); return !(e && e[0] == '0'); }();
-    plan_layout(plan, ntot, (int)topo.shells.size(), topo.lmax, rad_cache_on);
+    plan_layout(plan, ntot, (int)topo.shells.size(), topo.lmax, xc_radial_cache_on());
 
     const size_t per_frag = fragment_bytes(plan);
     size_t free_b = 0, total_b = 0;
@@ -1681,6 +1686,117 @@ int mqc_hip_esp_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecul
         hout.resize((size_t)nf * mp);
         HIP_CHECK_RET(hipMemcpy(hout.data(), d_out, sizeof(double) * hout.size(), hipMemcpyDeviceToHost));
         for (int f = 0; f < nf; ++f) std::memcpy(esp + (size_t)(start + f) * mp, &hout[(size_t)f * mp], sizeof(double) * hn[f]);
+    }
+    return MQC_HIP_OK;
+}
+
+// The quadrature stage of an SCF iteration on given densities (include/mqc_hip.h).  Nothing here is private to the
+// call: plan_batch and plan_layout decide what an SCF batch of nfrag fragments with this functional would get, carve_slot
+// lays the chunk out, and the grid, the weights, the radial cache and launch_xc are the driver's own (prepare, scf_loop).
+int mqc_hip_xc_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols, const mqc_hip_basis_t* bas, const char* functional,
+                     int32_t grid_level, int32_t unrestricted, const double* D, double* e_xc, double* n_electrons, double* V_xc)
+{
+    if (!ctx || !mols || !bas || !functional || !D || !e_xc || !n_electrons || !V_xc) return fail(MQC_HIP_ERR_VALIDATION, "xc batch: null argument");
+    if (nfrag < 1) return fail(MQC_HIP_ERR_VALIDATION, "xc batch: n_fragments must be at least 1");
+    HIP_CHECK_RET(hipSetDevice(ctx->device));
+    for (int64_t i = 0; i < nfrag; ++i) {
+        if (!mols[i].atomic_numbers || !mols[i].xyz || mols[i].n_atoms <= 0 || mols[i].n_atoms != mols[0].n_atoms ||
+            std::memcmp(mols[i].atomic_numbers, mols[0].atomic_numbers, sizeof(int32_t) * mols[0].n_atoms) != 0 || mols[i].ghost != mols[0].ghost)
+            return fail(MQC_HIP_ERR_VALIDATION, "xc batch: every fragment must have the elements of the first (one topology per call)");
+    }
+    mqc_hip_scf_options_t opts;
+    mqc_hip_default_options(&opts);
+    if (std::strlen(functional) >= sizeof(opts.functional)) return fail(MQC_HIP_ERR_UNSUPPORTED, "xc batch: functional name too long");
+    std::snprintf(opts.functional, sizeof(opts.functional), "%s", functional);
+    opts.grid_level = grid_level;
+    opts.unrestricted = unrestricted ? 1 : 0;
+    Topology topo;
+    std::string msg;
+    int rc = build_topology(mols[0], *bas, topo, msg, KERNEL_LMAX, false);
+    if (rc != MQC_HIP_OK) return fail(rc, msg);
+    const int ntot = (int)std::min<int64_t>(nfrag, 1 << 30);
+    BatchPlan plan;
+    if ((rc = plan_batch(opts, topo, ntot, plan, msg)) != MQC_HIP_OK) return fail(rc, msg);
+    if (plan.xc.ncomp == 0) return fail(MQC_HIP_ERR_VALIDATION, "xc batch: the functional has no grid part (Hartree-Fock)");
+    if (plan.uhf && !unrestricted) return fail(MQC_HIP_ERR_VALIDATION, "xc batch: an open-shell fragment takes spin densities (unrestricted != 0)");
+    Batch b{topo, nullptr, opts, nullptr};
+    if ((rc = upload_topology(ctx, topo, b.td)) != MQC_HIP_OK) return rc;
+    if ((rc = upload_grid(ctx, b, ctx->pool_grid, ctx->stream)) != MQC_HIP_OK) return rc;
+    plan.npts = b.grid.npts;
+    plan_layout(plan, ntot, (int)topo.shells.size(), topo.lmax, xc_radial_cache_on());
+
+    const int n = topo.nao, nspin = plan.uhf ? 2 : 1;
+    const size_t nn = (size_t)n * n;
+    constexpr size_t GUARD = 4096;         // bytes compared on either side of the accumulator
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    free_b += ctx->pool_main.capacity() + ctx->pool_eri.capacity() + ctx->pool_gridw.capacity();
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nfrag, 16384), (int64_t)((double)free_b * 0.7 / (double)fragment_bytes(plan))));
+    const Slot sl0 = make_slot(ctx, 0, nullptr);
+    hipStream_t s = ctx->stream;
+    std::vector<double> hx, acc, scal;
+    std::vector<unsigned char> before(2 * GUARD), after(2 * GUARD);
+    for (int64_t start = 0; start < nfrag; start += chunk) {
+        const int nf = (int)std::min<int64_t>(chunk, nfrag - start);
+        {
+            // room behind the last array of the quadrature's pool, so that the guard band exists where nothing follows V_xc
+            BatchView probe{};
+            const ChunkBytes need = carve_chunk(plan, nf, nullptr, probe);
+            if (!sl0.pool[POOL_GRIDW]->ensure(need.pool[POOL_GRIDW] + GUARD + 256)) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (grid weights)");
+        }
+        BatchView bv{};
+        bv.nalpha = plan.nalpha; bv.nbeta = plan.nbeta; bv.nocc = plan.nocc;
+        bv.exx = plan.rsh ? 1.0 : plan.xc.exx; bv.e_tol = opts.energy_tol; bv.d_tol = opts.density_tol;
+        bv.max_iter = opts.max_iter; bv.diis_size = opts.diis_size;
+        bv.xc = plan.xc; bv.grid = b.grid;
+        if ((rc = carve_slot(ctx, sl0, plan, b.td, nf, bv)) != MQC_HIP_OK) return rc;
+        hx.resize((size_t)nf * topo.natoms * 3);
+        for (int f = 0; f < nf; ++f) std::memcpy(&hx[(size_t)f * topo.natoms * 3], mols[start + f].xyz, sizeof(double) * topo.natoms * 3);
+        HIP_CHECK_RET(hipMemcpyAsync(bv.xyz, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemsetAsync(bv.istate, 0, sizeof(int) * (size_t)nf * 4, s));
+        if (plan.uhf) {
+            for (int f = 0; f < nf; ++f) {
+                const double* d = D + (size_t)(start + f) * 2 * nn;
+                HIP_CHECK_RET(hipMemcpyAsync(bv.D + (size_t)f * nn, d, sizeof(double) * nn, hipMemcpyHostToDevice, s));
+                HIP_CHECK_RET(hipMemcpyAsync(bv.Db + (size_t)f * nn, d + nn, sizeof(double) * nn, hipMemcpyHostToDevice, s));
+            }
+        } else HIP_CHECK_RET(hipMemcpyAsync(bv.D, D + (size_t)start * nn, sizeof(double) * nn * nf, hipMemcpyHostToDevice, s));
+        launch_becke_weights(bv, s);
+        if (bv.grid.rad) launch_xc_radial_cache(bv, s);
+        if ((rc = stage_check("grid weights")) != MQC_HIP_OK) return rc;
+        // Poison.  launch_xc zeroes the accumulator itself, so a tile no workgroup owns reads as zero, not NaN, and the
+        // comparison with the reference finds it; what the poison of the array cannot show is a write OUTSIDE it.  The
+        // bytes on either side -- the end of the Becke weights in front, the radial cache behind or (where the plan has
+        // none) poisoned spare room of the pool -- do not change in a quadrature launch: they are compared across it.
+        const size_t vx_bytes = sizeof(double) * (size_t)nf * nn * nspin;
+        unsigned char* lo = (unsigned char*)bv.Vxc - GUARD;
+        unsigned char* hi = (unsigned char*)bv.Vxc + vx_bytes;
+        if ((unsigned char*)bv.grid.weights > lo) return fail(MQC_HIP_ERR_DEVICE, "xc batch: the grid is smaller than the guard band");
+        HIP_CHECK_RET(hipMemsetAsync(bv.Vxc, 0xFF, vx_bytes, s));
+        if (!bv.grid.rad) HIP_CHECK_RET(hipMemsetAsync(hi, 0xFF, GUARD, s));
+        HIP_CHECK_RET(hipMemcpyAsync(before.data(), lo, GUARD, hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipMemcpyAsync(before.data() + GUARD, hi, GUARD, hipMemcpyDeviceToHost, s));
+        launch_xc(bv, false, s);
+        HIP_CHECK_RET(hipMemcpyAsync(after.data(), lo, GUARD, hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipMemcpyAsync(after.data() + GUARD, hi, GUARD, hipMemcpyDeviceToHost, s));
+        acc.resize((size_t)nf * nn * nspin); scal.resize((size_t)nf * 8);
+        HIP_CHECK_RET(hipMemcpyAsync(acc.data(), bv.Vxc, vx_bytes, hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipMemcpyAsync(scal.data(), bv.scal, sizeof(double) * scal.size(), hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        if ((rc = stage_check("exchange-correlation quadrature")) != MQC_HIP_OK) return rc;
+        if (std::memcmp(before.data(), after.data(), 2 * GUARD) != 0)
+            return fail(MQC_HIP_ERR_DEVICE, "xc batch: the quadrature wrote outside the V_xc accumulator");
+        // V_xc = A + A^T (scf_step's Fock assembly); the beta accumulators follow the alpha ones of the whole chunk
+        for (int f = 0; f < nf; ++f) {
+            e_xc[start + f] = scal[8 * (size_t)f + 5];
+            n_electrons[start + f] = scal[8 * (size_t)f + 6];
+            for (int sp = 0; sp < nspin; ++sp) {
+                const double* a = acc.data() + ((size_t)sp * nf + f) * nn;
+                double* v = V_xc + ((size_t)(start + f) * nspin + sp) * nn;
+                for (int i = 0; i < n; ++i)
+                    for (int j = 0; j < n; ++j) v[(size_t)i * n + j] = a[(size_t)i * n + j] + a[(size_t)j * n + i];
+            }
+        }
     }
     return MQC_HIP_OK;
 }

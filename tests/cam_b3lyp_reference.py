@@ -114,6 +114,23 @@ class CAMB3LYP:
         self.pts, self.w, _ = grid_oracle.build_grid(numbers, self.mol.xyz, self.level)
         self.eri_lr = eri4_erf(self.mol, self.omega)
 
+    @classmethod
+    def grid_only(cls, mol, level=3, block=4096):
+        """The grid part alone (grid_potential): no long-range integrals are formed, k_lr and potential are not available."""
+        self = cls.__new__(cls)
+        for f in cls.__dataclass_fields__.values():
+            if f.name != "mol":
+                setattr(self, f.name, f.default)
+        self.mol, self.level, self.block = mol, level, block
+        numbers = [int(round(z)) for z in mol.z]
+        self.pts, self.w, _ = grid_oracle.build_grid(numbers, mol.xyz, level)
+        self.eri_lr = None
+        return self
+
+    def grid_potential(self, Da, Db):
+        """Semi-local part for spin densities Da, Db: -> (E, V_a, V_b), without the long-range exchange."""
+        return self._grid(Da, Db)
+
     def _grid(self, Da, Db):
         n = self.mol.nao
         Va = np.zeros((n, n)); Vb = np.zeros((n, n))

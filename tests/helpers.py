@@ -43,6 +43,39 @@ def synthetic_density(n):
     return 0.5 * (d + d.T)
 
 
+def most_diffuse_ao(mol):
+    """Index of the first function of the shell whose tightest primitive is the loosest of the basis."""
+    tight = [np.max(mol.exps[p:p + k]) for p, k in zip(mol.sh_poff, mol.sh_nprim)]
+    return int(mol.sh_aoff[int(np.argmin(tight))])
+
+
+def orthonormal_orbitals(S, seed, diffuse_ao=None):
+    """C = S^{-1/2} Q, Q from the QR factorisation of a seeded normal matrix: C^T S C = 1, none of the molecule's
+    symmetry (symmetry hides swapped indices).  diffuse_ao = mu: the first column of that matrix is S^{1/2} e_mu, so
+    that orbital 0 is the basis function mu alone -- with most_diffuse_ao, an orbital that puts many grid points at
+    small rho, where v_sigma is large."""
+    n = S.shape[0]
+    w, U = np.linalg.eigh(S)
+    M = np.random.default_rng(seed).normal(size=(n, n))
+    if diffuse_ao is not None:
+        M[:, 0] = ((U * w ** 0.5) @ U.T)[:, diffuse_ao]
+    Q, _ = np.linalg.qr(M)
+    return (U * w ** -0.5) @ U.T @ Q
+
+
+def quadrature_density(C, nocc):
+    """Densities an exchange-correlation quadrature can take (synthetic_density is indefinite: rho < 0 at points), from
+    orthonormal orbitals C.  nocc an integer: restricted, D = 2 C_occ C_occ^T.  nocc = (n_alpha, n_beta): the spin
+    densities C_occ,s C_occ,s^T of the leading columns of the same C, stacked (2, n, n).  rho >= 0 everywhere and
+    tr(D S) is the electron number; nothing is converged."""
+    def proj(k):
+        p = C[:, :k] @ C[:, :k].T
+        return 0.5 * (p + p.T)          # a blocked matrix product is symmetric to rounding only
+    if isinstance(nocc, (tuple, list)):
+        return np.stack([proj(k) for k in nocc])
+    return 2.0 * proj(nocc)
+
+
 # ---- recorded oracle results ------------------------------------------------------------------------------------------
 # The handful of oracle SCFs that take a minute or more of numpy time each (benzene DF-B3LYP, the 147-function cluster,
 # def2-TZVP dimers ...) are stored as fixtures: tests/golden/oracle_fixtures.json holds energy and iteration count per

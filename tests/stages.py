@@ -1,5 +1,5 @@
 """Stage-level entry points of the C ABI (mqc_hip_int1e, _eri_packed, _eri_packed_attenuated, _jk_incore, _jk_direct,
-_coulomb_batch, _syev, _diis_coefficients) as numpy-in / numpy-out functions.  They run the same kernels the SCF
+_coulomb_batch, _xc_batch, _syev, _diis_coefficients) as numpy-in / numpy-out functions.  They run the same kernels the SCF
 driver launches and exist so that each row of the hot-path table can be parity-tested alone.
 Test infrastructure: a ctypes helper for tests/, not part of the product package."""
 from __future__ import annotations
@@ -99,3 +99,19 @@ def coulomb_batch(basis_set: str, fragments, D: np.ndarray, n_source_atoms: int 
     capi.check(capi.load_library().mqc_hip_coulomb_batch(capi.get_context(), len(ms), mols, C.byref(ms[0].bas),
                                                          n_source_atoms, capi.dptr(D), capi.dptr(J)))
     return J
+
+
+def xc_batch(basis_set: str, fragments, functional: str, D: np.ndarray, grid_level: int = 3, unrestricted: bool = False):
+    """mqc_hip_xc_batch for fragments of one element sequence: D (m, n, n), or (m, 2, n, n) alpha then beta when
+    unrestricted -> E_xc (m,), integrated electron number (m,), V_xc in the shape of D.  functional = None passes a
+    null pointer (refusal tests)."""
+    ms = [_marshal(basis_set, f) for f in fragments]
+    mols = (capi.Molecule * max(1, len(ms)))(*[m.mol for m in ms])
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    V = np.full_like(D, np.nan)
+    e, nel = np.full(max(1, len(ms)), np.nan), np.full(max(1, len(ms)), np.nan)
+    name = None if functional is None else functional.encode()
+    capi.check(capi.load_library().mqc_hip_xc_batch(capi.get_context(), len(ms), mols, C.byref(ms[0].bas) if ms else None, name,
+                                                    int(grid_level), 1 if unrestricted else 0, capi.dptr(D), capi.dptr(e), capi.dptr(nel),
+                                                    capi.dptr(V)))
+    return e, nel, V
