@@ -98,7 +98,7 @@ module mqc_hip_c
 
    public :: mqc_hip_backend_available, mqc_hip_context_get, mqc_hip_finalize, mqc_hip_last_error, &
              mqc_hip_abi_version, mqc_hip_default_options, mqc_hip_scf_run, mqc_hip_scf_run_batch, &
-             mqc_hip_coulomb_batch, mqc_hip_esp_batch
+             mqc_hip_coulomb_batch, mqc_hip_esp_batch, mqc_hip_scf_gradient_embedded_batch
 
    interface
       function mqc_hip_backend_available() bind(C, name="mqc_hip_backend_available") result(r)
@@ -148,6 +148,23 @@ module mqc_hip_c
          type(c_ptr), value :: auxes
          type(mqc_hip_scf_options_t), intent(in) :: opts
          type(mqc_hip_scf_result_t), intent(inout) :: res(*)
+         integer(c_int) :: r
+      end function
+      !! mqc_hip_scf_run_batch with the gradient forced on, for fragments embedded in point charges: res(i)%gradient is
+      !! d e_total / d R_A; site_gradients is c_null_ptr (no fragment carries charges) or c_loc of an array of n c_ptr,
+      !! entry i the address of double [3*n_point_charges_i] (d e_total / d R_g) or c_null_ptr to skip that fragment's site gradient
+      function mqc_hip_scf_gradient_embedded_batch(ctx, n, mols, orbitals, auxes, opts, res, site_gradients) &
+         bind(C, name="mqc_hip_scf_gradient_embedded_batch") result(r)
+         import :: c_int, c_int64_t, c_ptr, mqc_hip_molecule_t, mqc_hip_basis_t, mqc_hip_scf_options_t, &
+            mqc_hip_scf_result_t
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: n
+         type(mqc_hip_molecule_t), intent(in) :: mols(*)
+         type(mqc_hip_basis_t), intent(in) :: orbitals(*)
+         type(c_ptr), value :: auxes
+         type(mqc_hip_scf_options_t), intent(in) :: opts
+         type(mqc_hip_scf_result_t), intent(inout) :: res(*)
+         type(c_ptr), value :: site_gradients
          integer(c_int) :: r
       end function
       !! J[D] for many fragments of one topology; n_source_atoms > 0: only the (leading | source) block (local_coulomb)

@@ -257,6 +257,24 @@ int mqc_hip_xc_batch(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip_mo
                      const mqc_hip_basis_t *orbital, const char *functional, int32_t grid_level, int32_t unrestricted,
                      const double *D, double *e_xc /* [n] */, double *n_electrons /* [n] */, double *V_xc);
 
+/* Analytic gradients of fragments EMBEDDED IN POINT CHARGES (FMO / EE-MBE / QM-MM callers): mqc_hip_scf_run_batch with
+ * opts->want_gradient forced on -- grouping by topology, chunking and per-fragment failures in results[i] as there -- and
+ * two outputs per fragment, both exact derivatives of the e_total the engine reports (which contains tr(D u) and does NOT
+ * contain the nuclei-charge term sum Z_A q_g / R_Ag: the charges stay out of E_nuc, so that term and its derivative are the
+ * caller's):
+ *     results[i].gradient          [3*n_atoms]          d e_total / d R_A, the charges held fixed
+ *     point_charge_gradients[i]    [3*n_point_charges]  d e_total / d R_g, index 3*g + c
+ * Fragments with n_point_charges = 0 get the plain gradient and their pointer entry is ignored; a NULL array is legal when
+ * no fragment carries charges (MQC_HIP_ERR_VALIDATION otherwise); a NULL entry for a fragment that has charges skips its
+ * site gradient only.  A fragment with h_extra != NULL is refused with MQC_HIP_ERR_UNSUPPORTED (the engine does not know
+ * that operator's derivative), and every refusal of a plain gradient applies unchanged: meta-GGA and range-separated
+ * functionals, g shells, density fitting above n_ao = 140.  mqc_hip_scf_run_batch keeps refusing want_gradient with
+ * charges: its result record has no slot for the second output.  (Added without an ABI bump: no struct changed.) */
+int mqc_hip_scf_gradient_embedded_batch(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip_molecule_t *mols,
+                                        const mqc_hip_basis_t *orbitals, const mqc_hip_basis_t *auxes /* NULL unless DF */,
+                                        const mqc_hip_scf_options_t *opts, mqc_hip_scf_result_t *results,
+                                        double *const *point_charge_gradients /* [n_fragments]; entry i -> [3*n_point_charges_i] or NULL */);
+
 int mqc_hip_syev(mqc_hip_context *ctx, int32_t n, const double *A, double *w, double *V);
 /* DIIS coefficients from an age-ordered overlap matrix, the device routine's algorithm
  * (diis_coefficients/solve_diis, src/methods/mqc_diis.f90:164-273) */

@@ -35,6 +35,11 @@ void launch_esp(const TopologyDev& td, const Topology& topo, const double* boys_
                 hipStream_t s);
 size_t esp_record_doubles(const Topology& topo);
 static DevicePool g_esp_pool;
+// kern_grad_pc.hip: the point charges' part of an embedded fragment's gradient (atoms' part added into d_grad, the sites'
+// gradient into d_pcgrad [nfrag][npc][3]); doubles of records per fragment
+bool launch_pc_gradient(const BatchView& bv, const Topology& topo, const double* Dtot, double* d_grad, double* d_pcgrad, double* d_rec,
+                        hipStream_t s, std::string& err);
+size_t gradpc_record_doubles(const Topology& topo);
 
 static int stage_check(const char* stage)
 {
@@ -304,6 +309,7 @@ struct Batch {
     std::vector<const double*> xyz;
     std::vector<mqc_hip_scf_result_t*> results;
     std::vector<const mqc_hip_molecule_t*> mols;     // embedded groups only (point charges, h_extra)
+    std::vector<double*> pcgrad;                     // mqc_hip_scf_gradient_embedded_batch only: the callers' site gradients (or null)
     TopologyDev td{}, tdx{};
     GridDev grid;
     Stats stats;
@@ -695,7 +701,7 @@ static void embedding_and_mulliken(const Topology& topo, const double* D, const 
 
 // what a chunk's results are made of, read back once after its SCF loop
 struct ChunkOut {
-    std::vector<double> scal, eps, epsb, dip, grad;
+    std::vector<double> scal, eps, epsb, dip, grad, pcgrad;
     std::vector<double> D, U, S;      // total density, embedding operator, overlap: only where a caller reads them
     std::vector<int> ist;
 };
@@ -732,6 +738,9 @@ static int write_result(const BatchPlan& plan, Batch& b, const Job& job, const C
         nuclear_gradient(topo, x, &o.grad[(size_t)f * topo.natoms * 3], r->gradient);
         r->has_gradient = 1;
     }
+    // the charges stay out of E_nuc, so their gradient is the device's as it stands
+    if (b.opts.want_gradient && plan.npc > 0 && !b.pcgrad.empty() && b.pcgrad[job.start + f])
+        std::memcpy(b.pcgrad[job.start + f], &o.pcgrad[(size_t)f * plan.npc * 3], sizeof(double) * (size_t)plan.npc * 3);
     if (plan.uhf) {
         std::vector<double> Ca(nn), Cb(nn), Sm(nn);
         HIP_CHECK_RET(hipMemcpyAsync(Ca.data(), job.bv.C + (size_t)f * nn, sizeof(double) * nn, hipMemcpyDeviceToHost, s));
@@ -776,12 +785,17 @@ static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& j
         size_t lint = topo.pairs.size() + 64;
         for (auto& cl : topo.classes) lint += cl.quartets.size();
         const size_t nnh = (size_t)n * n;
-        const size_t bytes = sizeof(double) * ((size_t)nf * topo.natoms * 3 + 2 * (size_t)nf * nnh + 8) + sizeof(int) * (lint + 64);
+        // embedded fragments: the sites' gradient [nf][npc][3] and the Hermite records of the charges' part
+        const size_t pcg = plan.npc > 0 ? (((size_t)nf * plan.npc * 3 + 7) & ~size_t(7)) : 0;
+        const size_t pcrec = plan.npc > 0 ? (size_t)nf * gradpc_record_doubles(topo) : 0;
+        const size_t bytes = sizeof(double) * ((size_t)nf * topo.natoms * 3 + 2 * (size_t)nf * nnh + 8 + pcg + pcrec) + sizeof(int) * (lint + 64);
         char* gb = (char*)g_grad_pool[sl.id & 1].ensure(bytes);
         if (!gb) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (gradient)");
         double* d_grad = (double*)gb;
         double* gwork = d_grad + (((size_t)nf * topo.natoms * 3 + 7) & ~size_t(7));
-        int* glists = (int*)(gwork + 2 * (size_t)nf * nnh);
+        double* d_pcgrad = gwork + 2 * (size_t)nf * nnh;
+        double* d_pcrec = d_pcgrad + pcg;
+        int* glists = (int*)(d_pcrec + pcrec);
         // above n_ao = 140 the two-electron term skips the (quartet, fragment) tasks the direct path's Schwarz bounds
         // (still resident in this slot) prove below 1e-3 of its threshold: a derivative integral exceeds the bound of
         // its undifferentiated quartet, and at the threshold itself the dropped tasks moved a (H2O)6 / cc-pVDZ
@@ -790,6 +804,13 @@ static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& j
         const double* gq = (grad_screen && plan.two_e == TWO_E_DIRECT && n > 140) ? direct_schwarz_view(bv.slot) : nullptr;
         std::string gerr;
         if (!launch_gradient(bv, topo, b.aux, d_grad, gwork, glists, lint, s, gerr, gq, 1.0e-3 * plan.direct_tol)) return fail(MQC_HIP_ERR_UNSUPPORTED, gerr);
+        if (plan.npc > 0) {
+            // launch_gradient leaves the total density of an unrestricted run behind its energy-weighted density
+            const double* Dtot = plan.uhf ? gwork + (size_t)nf * nnh : bv.D;
+            if (!launch_pc_gradient(bv, topo, Dtot, d_grad, d_pcgrad, d_pcrec, s, gerr)) return fail(MQC_HIP_ERR_UNSUPPORTED, gerr);
+            o.pcgrad.resize((size_t)nf * plan.npc * 3);
+            HIP_CHECK_RET(hipMemcpyAsync(o.pcgrad.data(), d_pcgrad, sizeof(double) * o.pcgrad.size(), hipMemcpyDeviceToHost, s));
+        }
         o.grad.resize((size_t)nf * topo.natoms * 3);
         HIP_CHECK_RET(hipMemcpyAsync(o.grad.data(), d_grad, sizeof(double) * o.grad.size(), hipMemcpyDeviceToHost, s));
     }
@@ -842,7 +863,8 @@ static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& j
 // slot only, so that two topology groups can be driven by two host threads at once
 static int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology* aux, const std::vector<const double*>& xyz_in,
                      const mqc_hip_scf_options_t& opts, const std::vector<mqc_hip_scf_result_t*>& results_in, int lane,
-                     const AtomicGuess* atomic_guess, const std::vector<const mqc_hip_molecule_t*>& mols_in)
+                     const AtomicGuess* atomic_guess, const std::vector<const mqc_hip_molecule_t*>& mols_in,
+                     const std::vector<double*>* pcgrad_in = nullptr /* mqc_hip_scf_gradient_embedded_batch: the site gradients */)
 {
     const bool second = lane == 1;
     hipStream_t const lane_stream = second ? ctx->stream2 : ctx->stream;
@@ -864,13 +886,20 @@ static int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology*
         for (auto& k : key) {
             b.xyz.push_back(xyz_in[k.second]); b.results.push_back(results_in[k.second]);
             if (embedded) b.mols.push_back(mols_in[k.second]);
+            if (pcgrad_in) b.pcgrad.push_back((*pcgrad_in)[k.second]);      // the same permutation as the results
         }
     }
     std::string msg;
     int rc = plan_batch(opts, topo, ntot, plan, msg);
     if (rc == MQC_HIP_OK && embedded && opts.want_gradient) {
-        msg = "analytic gradients of a fragment embedded in point charges or an extra one-electron operator are not built (the field's own derivative is missing)";
-        rc = MQC_HIP_ERR_UNSUPPORTED;
+        if (!pcgrad_in) {
+            msg = "analytic gradients of a fragment embedded in point charges or an extra one-electron operator are not returned by this entry "
+                  "(the result record has no slot for the charges' own gradient): point charges go through mqc_hip_scf_gradient_embedded_batch";
+            rc = MQC_HIP_ERR_UNSUPPORTED;
+        } else if (plan.hx) {
+            msg = "analytic gradients of a fragment with an extra one-electron operator (h_extra) are not built: the engine does not know its derivative";
+            rc = MQC_HIP_ERR_UNSUPPORTED;
+        }
     }
     if (rc == MQC_HIP_OK && plan.npc > 0)
         for (int k = 0; k < ntot && rc == MQC_HIP_OK; ++k)
@@ -888,7 +917,9 @@ static int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology*
     plan.npts = b.grid.npts;
     plan_layout(plan, ntot, (int)topo.shells.size(), topo.lmax, xc_radial_cache_on());
 
-    const size_t per_frag = fragment_bytes(plan);
+    size_t per_frag = fragment_bytes(plan);
+    // the charges' part of an embedded gradient: Hermite records and the sites' gradient, from the gradient pool
+    if (opts.want_gradient && plan.npc > 0) per_frag += sizeof(double) * (gradpc_record_doubles(topo) + 3 * (size_t)plan.npc);
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
     free_b += ctx->pool_main.capacity() + ctx->pool_eri.capacity() + ctx->pool_df.capacity() + ctx->pool_gridw.capacity()
@@ -1249,9 +1280,11 @@ static void init_result(mqc_hip_scf_result_t* r)
     r->scf_status = MQC_HIP_SCF_NOT_RUN;
 }
 
-int mqc_hip_scf_run_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,
-                          const mqc_hip_basis_t* orbitals, const mqc_hip_basis_t* auxes,
-                          const mqc_hip_scf_options_t* opts, mqc_hip_scf_result_t* results)
+// the body of both batch entries; site_gradients != nullptr or embedded_entry: mqc_hip_scf_gradient_embedded_batch
+static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,
+                              const mqc_hip_basis_t* orbitals, const mqc_hip_basis_t* auxes,
+                              const mqc_hip_scf_options_t* opts, mqc_hip_scf_result_t* results, bool embedded_entry,
+                              double* const* site_gradients)
 {
     if (!ctx) return fail(MQC_HIP_ERR_VALIDATION, "null context (call mqc_hip_context_get first)");
     if (nfrag < 0 || (nfrag > 0 && (!mols || !orbitals || !opts || !results)))
@@ -1296,6 +1329,7 @@ int mqc_hip_scf_run_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_mol
         std::vector<const double*> xyz;
         std::vector<const mqc_hip_molecule_t*> mol;
         std::vector<mqc_hip_scf_result_t*> res;
+        std::vector<double*> pcg;
         std::shared_ptr<AtomicGuess> guess;
         int rc = MQC_HIP_OK;
         std::string msg;
@@ -1346,12 +1380,15 @@ int mqc_hip_scf_run_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_mol
                 w.guess.reset();
             }
         }
-        for (auto i : idx) { w.xyz.push_back(mols[i].xyz); w.mol.push_back(&mols[i]); w.res.push_back(&results[i]); }
+        for (auto i : idx) {
+            w.xyz.push_back(mols[i].xyz); w.mol.push_back(&mols[i]); w.res.push_back(&results[i]);
+            if (embedded_entry) w.pcg.push_back(site_gradients ? site_gradients[i] : nullptr);
+        }
         work.push_back(std::move(w));
     }
     auto run_one = [&](Work& w, int lane) {
         (void)hipSetDevice(ctx->device);
-        w.rc = run_batch(ctx, *w.topo, w.aux.get(), w.xyz, *opts, w.res, lane, w.guess.get(), w.mol);
+        w.rc = run_batch(ctx, *w.topo, w.aux.get(), w.xyz, *opts, w.res, lane, w.guess.get(), w.mol, embedded_entry ? &w.pcg : nullptr);
         if (w.rc != MQC_HIP_OK) w.msg = mqc_hip_last_error();      // the error text is thread-local
     };
     if (work.size() >= 2 && ctx->concurrent_groups) {
@@ -1381,6 +1418,28 @@ int mqc_hip_scf_run_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_mol
     // single-fragment calls report the fragment's failure as the call's status, like run_cuest_scf
     if (nfrag == 1 && worst != MQC_HIP_OK) return worst;
     return (nfrag == 1) ? MQC_HIP_OK : worst;
+}
+
+int mqc_hip_scf_run_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,
+                          const mqc_hip_basis_t* orbitals, const mqc_hip_basis_t* auxes,
+                          const mqc_hip_scf_options_t* opts, mqc_hip_scf_result_t* results)
+{
+    return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, opts, results, false, nullptr);
+}
+
+int mqc_hip_scf_gradient_embedded_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,
+                                        const mqc_hip_basis_t* orbitals, const mqc_hip_basis_t* auxes,
+                                        const mqc_hip_scf_options_t* opts, mqc_hip_scf_result_t* results,
+                                        double* const* point_charge_gradients)
+{
+    if (!opts) return fail(MQC_HIP_ERR_VALIDATION, "null argument");
+    if (!point_charge_gradients && mols)
+        for (int64_t i = 0; i < nfrag; ++i)
+            if (mols[i].n_point_charges > 0)
+                return fail(MQC_HIP_ERR_VALIDATION, "point_charge_gradients is NULL but fragment " + std::to_string(i) + " carries point charges");
+    mqc_hip_scf_options_t o = *opts;
+    o.want_gradient = 1;
+    return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, &o, results, true, point_charge_gradients);
 }
 
 int mqc_hip_scf_run(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* orbital,

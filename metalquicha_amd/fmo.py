@@ -32,6 +32,11 @@ bookkeeping the reference's Fortran host code does:
   potential on a CHELPG grid per monomer, ONE `mqc_hip_esp_batch` call per element sequence).  Published CHELPG
   defaults; parity with the reference's own variant is not claimed (charges.py).
 
+* `run_eembe_fixed_charges` (no counterpart in the reference): the level-2 EE-MBE in a FIXED charge per atom (force-field
+  style: no self-consistency, no response), with its analytic gradient -- every fragment's gradient on its own atoms and
+  on the sites of its field come from ONE `mqc_hip_scf_gradient_embedded_batch` call for all monomers and one for all
+  dimers; the classical nuclei-charge term and the assembly are host arithmetic here.
+
 Scope: whole-molecule fragments (no severed bonds, caps or AFO projector), closed shells; Mulliken, CHELPG or ignored
 far field.
 """
@@ -399,3 +404,139 @@ def run_fmo2(system: FragmentedSystem, settings: ScfSettings, expansion: str = "
     pair_sum = float(sum(corr[t] for t in terms))
     return FmoRun(float(np.sum(mono)) + pair_sum, mono, pair_sum, float(np.sum(resp)), outer_done, converged and not errors,
                   q_all.copy(), {t: corr[t] for t in terms}, total_iters, errors)
+
+
+# ---- EE-MBE2 in fixed charges, with forces --------------------------------------------------------------------------
+@dataclass
+class EmbeddedGradient:
+    e_total: float = 0.0                           # the engine's e_total: tr(D u) inside, no nuclei-charge term
+    atom_gradient: Optional[np.ndarray] = None     # (len(job.atoms), 3) d e_total / d R_A, the charges held fixed
+    site_gradient: Optional[np.ndarray] = None     # (len(job.field_atoms), 3) d e_total / d R_g
+    iterations: int = 0
+    error: str = ""
+
+
+GradientSolver = Callable[[Sequence[EmbeddedJob], bool], List[EmbeddedGradient]]     # (jobs, want_gradient)
+
+
+def hip_gradient_solver(system: FragmentedSystem, settings: ScfSettings) -> GradientSolver:
+    """The product solver of run_eembe_fixed_charges: every job of a phase in ONE engine call
+    (mqc_hip_scf_gradient_embedded_batch; mqc_hip_scf_run_batch when only energies are wanted)."""
+    from .methods import run_hip_embedded_gradients, run_hip_scf_groups
+    coords = np.ascontiguousarray(system.coordinates.T)
+    z_all = np.asarray(system.element_numbers)
+
+    def solve(jobs: Sequence[EmbeddedJob], want_gradient: bool) -> List[EmbeddedGradient]:
+        by_key: Dict[tuple, List[int]] = {}
+        for k, job in enumerate(jobs):
+            by_key.setdefault((tuple(int(v) for v in z_all[list(job.atoms)]), len(job.field_atoms)), []).append(k)
+        groups, index = [], []
+        for (zseq, npc), ks in by_key.items():
+            xyz = np.stack([coords[list(jobs[k].atoms)] for k in ks])
+            g = FragmentGroup(np.array(zseq, dtype=np.int32), xyz, np.zeros(len(ks), dtype=np.int32))
+            if npc:
+                g.point_charge_xyz = np.stack([coords[np.asarray(jobs[k].field_atoms, dtype=np.int64)] for k in ks])
+                g.point_charges = np.stack([np.asarray(jobs[k].field_charges, dtype=np.float64) for k in ks])
+            groups.append(g); index.append(ks)
+        if want_gradient:
+            recs, atom, site = run_hip_embedded_gradients(settings, groups)
+        else:
+            recs, atom, site = run_hip_scf_groups(settings, groups), None, None
+        out = [EmbeddedGradient() for _ in jobs]
+        for gi, (ks, rec) in enumerate(zip(index, recs)):
+            for pos, k in enumerate(ks):
+                r = out[k]
+                if rec["has_error"][pos] or (want_gradient and not rec["has_gradient"][pos]):
+                    r.error = bytes(rec["message"][pos]).split(b"\0", 1)[0].decode(errors="replace") or "no gradient came back"
+                    continue
+                r.e_total = float(rec["e_total"][pos]); r.iterations = int(rec["iterations"][pos])
+                if want_gradient:
+                    r.atom_gradient = atom[gi][pos]; r.site_gradient = site[gi][pos]
+        return out
+
+    return solve
+
+
+@dataclass
+class EembeRun:
+    energy: float
+    monomer_energy: np.ndarray                     # E'_I: embedded monomer energies, nuclei-charge term included
+    pair_corrections: Dict[Tuple[int, int], float]
+    gradient: Optional[np.ndarray] = None          # (3, n_atoms) Hartree/Bohr
+    scf_iterations: int = 0
+    errors: List[str] = field(default_factory=list)
+
+
+def run_eembe_fixed_charges(system: FragmentedSystem, settings: ScfSettings, charges, want_gradient: bool = True,
+                            rank: int = 0, world: int = 1, allreduce: Optional[Callable[[np.ndarray], np.ndarray]] = None,
+                            solver: Optional[GradientSolver] = None) -> EembeRun:
+    """Level-2 EE-MBE of whole-molecule fragments in a fixed charge per atom, `charges` (n_atoms,), and its gradient.
+
+    Every monomer and every dimer X is solved in the field of the charges of all atoms outside it,
+        E'_X = e_total_X + sum_{A in X, g not in X} Z_A q_g / R_Ag        (the engine keeps the charges out of E_nuc),
+        E    = sum_I E'_I + sum_{I<J} (E'_IJ - E'_I - E'_J).
+    The charges do not depend on the geometry and nothing is iterated, so the gradient needs no response: each job's
+    gradient on its atoms lands on those atoms, its gradient on the charges' sites -- plus the classical term's
+    derivative on both -- on the atoms that supplied the charges, weighted as the energy (a monomer counts
+    1 - (n_fragments - 1) times, a dimer once).  All monomers are ONE batch call and all dimers one.
+
+    `rank`, `world`, `allreduce` as run_fmo2: jobs round-robin over the ranks, one element-wise SUM at the end."""
+    if world > 1 and allreduce is None:
+        raise ValueError("several ranks need an allreduce")
+    z_all = np.asarray(system.element_numbers, dtype=np.float64)
+    xyz = np.ascontiguousarray(system.coordinates.T)
+    n_atoms, nfrag = len(z_all), system.n_monomers
+    q_all = np.asarray(charges, dtype=np.float64)
+    if q_all.shape != (n_atoms,):
+        raise ValueError("charges must hold one value per atom of the system")
+    solve = solver or hip_gradient_solver(system, settings)
+    share = allreduce if world > 1 else (lambda a: a)
+    frags = [tuple(int(a) for a in m) for m in system.monomers]
+    pairs = list(itertools.combinations(range(nfrag), 2))
+
+    def job_of(members: Sequence[int]) -> EmbeddedJob:
+        atoms = tuple(a for m in members for a in frags[m])
+        outside = np.ones(n_atoms, dtype=bool); outside[list(atoms)] = False
+        out = np.nonzero(outside)[0]
+        return EmbeddedJob(atoms, out, q_all[out])
+
+    my_mono = [i for i in range(nfrag) if i % world == rank]
+    my_pair = [k for k in range(len(pairs)) if k % world == rank]
+    # [E'_I | E'_IJ | gradient (n_atoms, 3) | SCF iterations | failures]
+    packed = np.zeros(nfrag + len(pairs) + 3 * n_atoms + 2)
+    e_mono, e_pair = packed[:nfrag], packed[nfrag:nfrag + len(pairs)]
+    grad = packed[nfrag + len(pairs):nfrag + len(pairs) + 3 * n_atoms].reshape(n_atoms, 3)
+    errors: List[str] = []
+
+    def absorb(job: EmbeddedJob, r: EmbeddedGradient, weight: float) -> float:
+        atoms = np.asarray(job.atoms, dtype=np.int64); out = np.asarray(job.field_atoms, dtype=np.int64)
+        d = xyz[atoms][:, None, :] - xyz[out][None, :, :]                    # (atoms, sites, 3)
+        dist = np.linalg.norm(d, axis=2)
+        zq = z_all[atoms][:, None] * np.asarray(job.field_charges)[None, :]
+        e = r.e_total + float(np.sum(zq / dist)) if out.size else r.e_total
+        if want_gradient:
+            np.add.at(grad, atoms, weight * r.atom_gradient)
+            if out.size:
+                pull = -(zq / dist ** 3)[:, :, None] * d                     # d/dR_A of Z_A q_g / R_Ag; d/dR_g is its negative
+                np.add.at(grad, atoms, weight * pull.sum(axis=1))
+                np.add.at(grad, out, weight * (r.site_gradient - pull.sum(axis=0)))
+        return e
+
+    for which, mine, e_out, weight in (("fragment", my_mono, e_mono, 1.0 - (nfrag - 1)), ("pair", my_pair, e_pair, 1.0)):
+        jobs = [job_of([i] if which == "fragment" else pairs[i]) for i in mine]
+        res = solve(jobs, want_gradient) if jobs else []
+        for i, job, r in zip(mine, jobs, res):
+            if r.error:
+                errors.append("%s %s: %s" % (which, i if which == "fragment" else pairs[i], r.error)); continue
+            e_out[i] = absorb(job, r, weight)
+            packed[-2] += r.iterations
+    packed[-1] = float(len(errors))
+    packed = np.asarray(share(packed), dtype=np.float64)
+    e_mono, e_pair = packed[:nfrag], packed[nfrag:nfrag + len(pairs)]
+    grad = packed[nfrag + len(pairs):nfrag + len(pairs) + 3 * n_atoms].reshape(n_atoms, 3)
+    if packed[-1] != 0.0:
+        # a failed job would enter as energy 0: no total instead, and every rank learns of it
+        return EembeRun(float("nan"), e_mono.copy(), {}, None, int(packed[-2]), errors or ["an SCF failed on another rank"])
+    corr = {p: float(e_pair[k] - e_mono[p[0]] - e_mono[p[1]]) for k, p in enumerate(pairs)}
+    energy = float(np.sum(e_mono)) + float(sum(corr.values()))
+    return EembeRun(energy, e_mono.copy(), corr, grad.T.copy() if want_gradient else None, int(packed[-2]), errors)

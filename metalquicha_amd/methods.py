@@ -8,6 +8,8 @@
   hip_backend_available <- cuest_backend_available (:20-30)
   HFMethod.calc_energy  <- hf_calc_energy / hf_run (src/methods/mqc_method_hf.F90:113-217)
   run_hip_scf_batch   <- the batch-submit entry the worker loop would use
+  run_hip_embedded_gradients <- (no counterpart) gradients of fragments in point charges, on atoms and on the charges
+                         (mqc_hip_scf_gradient_embedded_batch)
   run_hip_esp         <- (no counterpart) the potential of converged densities at arbitrary points (mqc_hip_esp_batch)
 
 Same names, argument meaning and error behaviour; the numerics all happen in libmqc_hip.so.
@@ -332,7 +334,8 @@ class FragmentGroup:
 
 def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], want_gradient: bool = False,
                        gradients_out: Optional[list] = None, extras: Sequence[str] = (),
-                       extras_out: Optional[list] = None) -> List[np.ndarray]:
+                       extras_out: Optional[list] = None, site_gradients_out: Optional[list] = None,
+                       status_out: Optional[list] = None) -> List[np.ndarray]:
     """All fragments of all groups in ONE mqc_hip_scf_run_batch call; returns, per group, a structured array
     viewing the engine's result records (fields of capi.ScfResult: e_total, iterations, has_error, message ...).
 
@@ -341,7 +344,13 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
     handful of vector operations rather than a Python loop over ctypes objects.
 
     `extras` names per-fragment arrays to bring back besides the records -- "density" (m, n, n), "embedding_matrix"
-    (m, n, n), "mulliken_charges" (m, n_atoms) -- appended to `extras_out` as one dict per group."""
+    (m, n, n), "mulliken_charges" (m, n_atoms) -- appended to `extras_out` as one dict per group.
+
+    `site_gradients_out` (a list) sends the batch through mqc_hip_scf_gradient_embedded_batch instead: the gradient is
+    forced on, and one (m, n_pc, 3) array per group (n_pc = 0 for a group without charges) is appended to it -- the
+    derivative of e_total with respect to the charges' positions.  `status_out` receives the call's status code."""
+    embedded = site_gradients_out is not None
+    want_gradient = bool(want_gradient) or embedded
     sizes = [int(g.xyz.shape[0]) for g in groups]
     n = int(sum(sizes))
     if n == 0:
@@ -436,9 +445,28 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
             if extras_out is not None:
                 extras_out.append(got)
             keep.append(got)
-    rc = lib.mqc_hip_scf_run_batch(ctx, n, mols.ctypes.data_as(C.POINTER(capi.Molecule)),
-                                   bass.ctypes.data_as(C.POINTER(capi.Basis)),
-                                   auxs.ctypes.data_as(C.POINTER(capi.Basis)) if df else None, C.byref(opts), res)
+    if embedded:
+        # one (m, n_pc, 3) array per group; entry i of the pointer array is fragment i's slice (0 = no charges)
+        site_ptr = np.zeros(n, dtype=np.uint64)
+        sites, lo = [], 0
+        for g, m in zip(groups, sizes):
+            npc = 0 if g.point_charges is None else int(np.asarray(g.point_charges).shape[1])
+            sg = np.zeros((m, npc, 3))
+            sites.append(sg)
+            if m and npc:
+                site_ptr[lo:lo + m] = sg.ctypes.data + np.arange(m, dtype=np.uint64) * np.uint64(npc * 3 * 8)
+            lo += m
+        site_gradients_out.extend(sites)
+        rc = lib.mqc_hip_scf_gradient_embedded_batch(ctx, n, mols.ctypes.data_as(C.POINTER(capi.Molecule)),
+                                                     bass.ctypes.data_as(C.POINTER(capi.Basis)),
+                                                     auxs.ctypes.data_as(C.POINTER(capi.Basis)) if df else None, C.byref(opts), res,
+                                                     site_ptr.ctypes.data_as(C.POINTER(capi.c_double_p)))
+    else:
+        rc = lib.mqc_hip_scf_run_batch(ctx, n, mols.ctypes.data_as(C.POINTER(capi.Molecule)),
+                                       bass.ctypes.data_as(C.POINTER(capi.Basis)),
+                                       auxs.ctypes.data_as(C.POINTER(capi.Basis)) if df else None, C.byref(opts), res)
+    if status_out is not None:
+        status_out.append(int(rc))
     rec = np.frombuffer(res, dtype=_RES_DTYPE)
     if rc != capi.MQC_HIP_OK and not np.any(rec["has_error"]):
         capi.check(rc)
@@ -448,6 +476,23 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
         out.append(rec[lo:lo + m])
         lo += m
     return out
+
+
+def run_hip_embedded_gradients(settings: ScfSettings, groups: Sequence[FragmentGroup], extras: Sequence[str] = (),
+                               extras_out: Optional[list] = None, status_out: Optional[list] = None):
+    """Analytic gradients of fragments embedded in point charges, all groups in ONE mqc_hip_scf_gradient_embedded_batch
+    call -> (records, atom_gradients, site_gradients): per group the result records (as run_hip_scf_groups), the
+    gradient on the fragment's atoms (m, n_atoms, 3) with the charges held fixed, and the gradient on the charges' sites
+    (m, n_pc, 3).  Both are derivatives of the records' e_total, which holds tr(D u) but not the classical
+    nuclei-charge term sum Z_A q_g / R_Ag: that term and its derivative are the caller's.  Groups without charges get
+    the plain gradient and an (m, 0, 3) site array; a group with h_extra is refused in its records."""
+    atom, site = [], []
+    rec = run_hip_scf_groups(settings, groups, want_gradient=True, gradients_out=atom, extras=extras, extras_out=extras_out,
+                             site_gradients_out=site, status_out=status_out)
+    if not atom:      # an empty batch
+        atom = [np.zeros((0, len(g.element_numbers), 3)) for g in groups]
+        site = [np.zeros((0, 0, 3)) for g in groups]
+    return rec, atom, site
 
 
 def run_hip_esp(settings: ScfSettings, group: FragmentGroup, densities, points, n_points=None,
