@@ -98,7 +98,8 @@ module mqc_hip_c
 
    public :: mqc_hip_backend_available, mqc_hip_context_get, mqc_hip_finalize, mqc_hip_last_error, &
              mqc_hip_abi_version, mqc_hip_default_options, mqc_hip_scf_run, mqc_hip_scf_run_batch, &
-             mqc_hip_coulomb_batch, mqc_hip_esp_batch, mqc_hip_scf_gradient_embedded_batch
+             mqc_hip_coulomb_batch, mqc_hip_esp_batch, mqc_hip_scf_gradient_embedded_batch, &
+             mqc_hip_scf_run_batch_restart
 
    interface
       function mqc_hip_backend_available() bind(C, name="mqc_hip_backend_available") result(r)
@@ -165,6 +166,25 @@ module mqc_hip_c
          type(mqc_hip_scf_options_t), intent(in) :: opts
          type(mqc_hip_scf_result_t), intent(inout) :: res(*)
          type(c_ptr), value :: site_gradients
+         integer(c_int) :: r
+      end function
+      !! mqc_hip_scf_run_batch started from supplied densities: initial_density is c_null_ptr or c_loc of an array of n
+      !! c_ptr, entry i c_null_ptr (start from opts%guess) or the address of double [n_ao*n_ao] (restricted run: the total
+      !! density) / [2*n_ao*n_ao] (unrestricted run: alpha, beta); spin_densities_out likewise, entry i c_null_ptr or the
+      !! address of double [2*n_ao*n_ao] that an unrestricted run fills with its converged alpha and beta densities
+      function mqc_hip_scf_run_batch_restart(ctx, n, mols, orbitals, auxes, opts, res, initial_density, spin_densities_out) &
+         bind(C, name="mqc_hip_scf_run_batch_restart") result(r)
+         import :: c_int, c_int64_t, c_ptr, mqc_hip_molecule_t, mqc_hip_basis_t, mqc_hip_scf_options_t, &
+            mqc_hip_scf_result_t
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: n
+         type(mqc_hip_molecule_t), intent(in) :: mols(*)
+         type(mqc_hip_basis_t), intent(in) :: orbitals(*)
+         type(c_ptr), value :: auxes
+         type(mqc_hip_scf_options_t), intent(in) :: opts
+         type(mqc_hip_scf_result_t), intent(inout) :: res(*)
+         type(c_ptr), value :: initial_density
+         type(c_ptr), value :: spin_densities_out
          integer(c_int) :: r
       end function
       !! J[D] for many fragments of one topology; n_source_atoms > 0: only the (leading | source) block (local_coulomb)

@@ -275,6 +275,32 @@ int mqc_hip_scf_gradient_embedded_batch(mqc_hip_context *ctx, int64_t n_fragment
                                         const mqc_hip_scf_options_t *opts, mqc_hip_scf_result_t *results,
                                         double *const *point_charge_gradients /* [n_fragments]; entry i -> [3*n_point_charges_i] or NULL */);
 
+/* mqc_hip_scf_run_batch started from SUPPLIED DENSITIES: the previous step of a trajectory, the previous pass of an FMO
+ * loop, the block-diagonal sum of two monomers for their dimer.  Grouping by topology, chunking under
+ * MQC_HIP_HBM_BUDGET_GB, concurrent groups, per-fragment failures in results[i] and every refusal are those of
+ * mqc_hip_scf_run_batch; so is the convergence test (a converged result needs more than one iteration, so a restart
+ * from an already converged density takes exactly 2).
+ *     initial_density[i]      NULL: fragment i starts from opts->guess and gives what mqc_hip_scf_run_batch gives.
+ *                             Otherwise row-major [n_ao*n_ao], the TOTAL density, when the fragment runs restricted, and
+ *                             [2][n_ao*n_ao], alpha then beta (C_s C_s^T, not doubled), when it runs unrestricted.  Which
+ *                             one is decided as everywhere: unrestricted iff opts->unrestricted, multiplicity != 1 or an
+ *                             odd electron count -- the expected size follows from that decision, not from the caller.
+ *     spin_densities_out[i]   NULL, or [2][n_ao*n_ao]: the converged alpha and beta densities of an unrestricted run
+ *                             (results[i].density stays the total density); restricted runs write nothing there.
+ * Either array may be NULL; with both NULL the call is mqc_hip_scf_run_batch.
+ * The density need not be good.  It is projected on the device onto the nearest SCF state of THIS geometry: the
+ * generalised eigenproblem of -S D0s S (D0s = D0 symmetrised) in the metric S yields D0's natural orbitals, the n_occ
+ * most occupied ones are filled (per spin in an unrestricted run), and the run starts from their idempotent density and
+ * orbitals.  A wrong trace, a density that is not idempotent in the new overlap, all zeros: all legal.  A density
+ * that already is an SCF state of this overlap is reproduced.  A non-finite entry gives MQC_HIP_ERR_VALIDATION, reported in
+ * that fragment's record only (the other fragments of the call run).  A group in which every fragment brings a density
+ * skips the free-atom solves of the SAD / SAC guesses.  (Added without an ABI bump: no struct changed.) */
+int mqc_hip_scf_run_batch_restart(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip_molecule_t *mols,
+                                  const mqc_hip_basis_t *orbitals, const mqc_hip_basis_t *auxes /* NULL unless DF */,
+                                  const mqc_hip_scf_options_t *opts, mqc_hip_scf_result_t *results,
+                                  const double *const *initial_density /* NULL, or [n_fragments]; entry i NULL or -> density */,
+                                  double *const *spin_densities_out /* NULL, or [n_fragments]; entry i NULL or -> [2][n_ao*n_ao] */);
+
 int mqc_hip_syev(mqc_hip_context *ctx, int32_t n, const double *A, double *w, double *V);
 /* DIIS coefficients from an age-ordered overlap matrix, the device routine's algorithm
  * (diis_coefficients/solve_diis, src/methods/mqc_diis.f90:164-273) */

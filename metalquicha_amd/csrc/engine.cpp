@@ -254,13 +254,13 @@ static int validate_options(const mqc_hip_scf_options_t& o, const Topology& topo
 
 // The decisions of a batch call of ntot fragments that do not wait for the grid: functional, spin, two-electron path,
 // Schwarz thresholds; then the refusals of validate_options
+static bool runs_unrestricted(const mqc_hip_scf_options_t& o, int multiplicity, int nelec);
 static int plan_batch(const mqc_hip_scf_options_t& o, const Topology& topo, int ntot, BatchPlan& p, std::string& msg)
 {
     p.n = topo.nao; p.npair = topo.npair; p.natoms = topo.natoms;
     if (!parse_functional(o.functional, p.xc, msg)) return MQC_HIP_ERR_UNSUPPORTED;
     p.rsh = p.xc.omega > 0.0;
-    // restricted iff multiplicity 1, even electron count and not forced (mqc_cuest_driver.f90:127)
-    p.uhf = o.unrestricted || topo.multiplicity != 1 || (topo.nelec % 2) != 0;
+    p.uhf = runs_unrestricted(o, topo.multiplicity, topo.nelec);
     p.nalpha = p.uhf ? (topo.nelec + topo.multiplicity - 1) / 2 : topo.nelec / 2;
     p.nbeta = p.uhf ? topo.nelec - p.nalpha : topo.nelec / 2;
     p.nocc = p.nalpha;
@@ -275,6 +275,12 @@ static int plan_batch(const mqc_hip_scf_options_t& o, const Topology& topo, int 
     static const int schwarz_min = [] { const char* e = std::getenv("MQC_HIP_SCHWARZ_MIN_FRAGMENTS"); return e ? std::atoi(e) : 9; }();
     p.stol = (o.schwarz_tol > 0.0 && ntot >= schwarz_min) ? o.schwarz_tol : 0.0;
     return validate_options(o, topo, p, msg);
+}
+
+// restricted iff multiplicity 1, even electron count and not forced (mqc_cuest_driver.f90:127)
+static bool runs_unrestricted(const mqc_hip_scf_options_t& o, int multiplicity, int nelec)
+{
+    return o.unrestricted || multiplicity != 1 || (nelec % 2) != 0;
 }
 
 static void fill_error(mqc_hip_scf_result_t* r, const std::string& msg)
@@ -298,6 +304,7 @@ struct AtomicGuess {
     int nmodes = 0;
 };
 static DevicePool g_guess_pool[2];
+static DevicePool g_restart_pool[2];     // per slot: which fragments of the chunk restart from a supplied density
 
 // What the stages of one batch call share besides the plan: the inputs, ordered by compactness, the device topology
 // and grid, and the statistics, gathered locally (two lanes may run at once) and merged at the end
@@ -310,6 +317,10 @@ struct Batch {
     std::vector<mqc_hip_scf_result_t*> results;
     std::vector<const mqc_hip_molecule_t*> mols;     // embedded groups only (point charges, h_extra)
     std::vector<double*> pcgrad;                     // mqc_hip_scf_gradient_embedded_batch only: the callers' site gradients (or null)
+    // mqc_hip_scf_run_batch_restart only: the callers' starting densities (null entry: opts.guess) and where an
+    // unrestricted run's spin densities go (null entry: nowhere); empty when the call brought none
+    std::vector<const double*> d0;
+    std::vector<double*> spin_out;
     TopologyDev td{}, tdx{};
     GridDev grid;
     Stats stats;
@@ -319,6 +330,7 @@ struct Job {
     int start = 0, nf = 0;
     BatchView bv{};
     std::vector<double> hx, hpc;
+    std::vector<int> restart;      // per fragment of the chunk: 1 = starts from its supplied density
 };
 
 // radial cache of the quadrature: MQC_HIP_XC_RADIAL_CACHE=0 turns it off
@@ -478,7 +490,14 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
     if ((rc = stage_check("int1e")) != MQC_HIP_OK) return rc;
     launch_orthogonalizer(bv, so);
     if ((rc = stage_check("orthogonalizer")) != MQC_HIP_OK) return rc;
-    if (!b.guess) launch_guess(bv, opts.guess == MQC_HIP_GUESS_CORE ? MQC_HIP_GUESS_CORE : MQC_HIP_GUESS_GWH, so);
+    // fragments that bring a starting density are projected below; a chunk made of them alone needs no other guess
+    int n_restart = 0;
+    if (!b.d0.empty()) {
+        job.restart.assign(nf, 0);
+        for (int f = 0; f < nf; ++f) if (b.d0[job.start + f]) { job.restart[f] = 1; ++n_restart; }
+    }
+    const bool all_restart = n_restart == nf;
+    if (!b.guess && !all_restart) launch_guess(bv, opts.guess == MQC_HIP_GUESS_CORE ? MQC_HIP_GUESS_CORE : MQC_HIP_GUESS_GWH, so);
     if ((rc = stage_check("guess")) != MQC_HIP_OK) return rc;
     HIP_CHECK_RET(hipEventRecord(ctx->evo[sl.id & 1][1], so));
     if (plan.xc.ncomp > 0) { launch_becke_weights(bv, s); if (bv.grid.rad) launch_xc_radial_cache(bv, s); }
@@ -504,7 +523,7 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
     if ((rc = stage_check("two-electron setup")) != MQC_HIP_OK) return rc;
     b.stats.eri_quartets += topo.n_quartets * nf;
     HIP_CHECK_RET(hipStreamWaitEvent(s, ctx->evo[sl.id & 1][1], 0));      // join: X, C, D of the guess are ready
-    if (b.guess) {
+    if (b.guess && !all_restart) {
         // superposed atoms (build_restricted_guess / atomic_guess_fock, mqc_libcint_atomic_guess.f90:168-212,
         // mqc_libcint_rhf.f90:1382-1411): the same block-diagonal density in every fragment of the topology, its
         // Hartree-Fock Fock matrix from the two-electron stage just built (full exchange), then the usual
@@ -524,6 +543,23 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
         jk_one(plan, topo, vg, false, s);
         launch_guess(bv, MQC_HIP_GUESS_SAD, s);
         if ((rc = stage_check("atomic guess")) != MQC_HIP_OK) return rc;
+    }
+    if (n_restart > 0) {
+        // supplied densities: each into its fragment's W0 (alpha, beta of an unrestricted run: W0, W1), then the
+        // projection onto an SCF state of this geometry (kern_scf.hip, restart_kernel) over what the guess left there
+        const size_t nn = (size_t)n * n, cnt = plan.uhf ? 2 * nn : nn;
+        for (int f = 0; f < nf; ++f)
+            if (job.restart[f])
+                HIP_CHECK_RET(hipMemcpyAsync(bv.W + (size_t)f * 6 * nn, b.d0[job.start + f], sizeof(double) * cnt, hipMemcpyHostToDevice, s));
+        const int* d_flags = nullptr;
+        if (!all_restart) {
+            int* df = (int*)g_restart_pool[sl.id & 1].ensure(sizeof(int) * (size_t)nf + 256);
+            if (!df) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (restart flags)");
+            HIP_CHECK_RET(hipMemcpyAsync(df, job.restart.data(), sizeof(int) * (size_t)nf, hipMemcpyHostToDevice, s));
+            d_flags = df;
+        }
+        launch_restart(bv, d_flags, s);
+        if ((rc = stage_check("restart projection")) != MQC_HIP_OK) return rc;
     }
     b.stats.t_eri += now_s() - t2;      // host time to enqueue; the kernels are timed by q0/q1
     return MQC_HIP_OK;
@@ -703,6 +739,7 @@ static void embedding_and_mulliken(const Topology& topo, const double* D, const 
 struct ChunkOut {
     std::vector<double> scal, eps, epsb, dip, grad, pcgrad;
     std::vector<double> D, U, S;      // total density, embedding operator, overlap: only where a caller reads them
+    std::vector<double> Da, Db;       // spin densities of an unrestricted chunk, where a caller asked for them
     std::vector<int> ist;
 };
 
@@ -758,6 +795,10 @@ static int write_result(const BatchPlan& plan, Batch& b, const Job& job, const C
         embedding_and_mulliken(topo, o.D.data() + f * nn, embedded ? o.U.data() + f * nn : nullptr,
                                r->mulliken_charges ? o.S.data() + f * nn : nullptr, r);
     if (r->density) std::memcpy(r->density, o.D.data() + f * nn, sizeof(double) * nn);
+    if (plan.uhf && !b.spin_out.empty() && b.spin_out[job.start + f]) {
+        std::memcpy(b.spin_out[job.start + f], o.Da.data() + f * nn, sizeof(double) * nn);
+        std::memcpy(b.spin_out[job.start + f] + nn, o.Db.data() + f * nn, sizeof(double) * nn);
+    }
     r->has_error = 0; r->message[0] = '\0';
     if (plan.two_e == TWO_E_DF && o.scal[8 * f + 7] == 1.0)
         fill_error(r, "density fitting: the auxiliary metric (P|Q) could not be factorised or diagonalised");
@@ -843,6 +884,10 @@ static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& j
     if (want_d) HIP_CHECK_RET(fetch(o.D, bv.D));
     if (embedded) HIP_CHECK_RET(fetch(o.U, bv.U));
     if (want_s) HIP_CHECK_RET(fetch(o.S, bv.S));
+    bool want_spin = false;
+    if (plan.uhf && !b.spin_out.empty())
+        for (int f = 0; f < nf; ++f) want_spin = want_spin || b.spin_out[job.start + f] != nullptr;
+    if (want_spin) { HIP_CHECK_RET(fetch(o.Da, bv.D)); HIP_CHECK_RET(fetch(o.Db, bv.Db)); }
     if (want_d && plan.uhf) {
         std::vector<double> db;
         HIP_CHECK_RET(fetch(db, bv.Db));
@@ -864,7 +909,9 @@ static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& j
 static int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology* aux, const std::vector<const double*>& xyz_in,
                      const mqc_hip_scf_options_t& opts, const std::vector<mqc_hip_scf_result_t*>& results_in, int lane,
                      const AtomicGuess* atomic_guess, const std::vector<const mqc_hip_molecule_t*>& mols_in,
-                     const std::vector<double*>* pcgrad_in = nullptr /* mqc_hip_scf_gradient_embedded_batch: the site gradients */)
+                     const std::vector<double*>* pcgrad_in = nullptr /* mqc_hip_scf_gradient_embedded_batch: the site gradients */,
+                     const std::vector<const double*>* d0_in = nullptr /* mqc_hip_scf_run_batch_restart: starting densities ... */,
+                     const std::vector<double*>* spin_in = nullptr /* ... and the spin densities' destinations */)
 {
     const bool second = lane == 1;
     hipStream_t const lane_stream = second ? ctx->stream2 : ctx->stream;
@@ -887,6 +934,8 @@ static int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology*
             b.xyz.push_back(xyz_in[k.second]); b.results.push_back(results_in[k.second]);
             if (embedded) b.mols.push_back(mols_in[k.second]);
             if (pcgrad_in) b.pcgrad.push_back((*pcgrad_in)[k.second]);      // the same permutation as the results
+            if (d0_in) b.d0.push_back((*d0_in)[k.second]);
+            if (spin_in) b.spin_out.push_back((*spin_in)[k.second]);
         }
     }
     std::string msg;
@@ -1280,11 +1329,13 @@ static void init_result(mqc_hip_scf_result_t* r)
     r->scf_status = MQC_HIP_SCF_NOT_RUN;
 }
 
-// the body of both batch entries; site_gradients != nullptr or embedded_entry: mqc_hip_scf_gradient_embedded_batch
+// the body of the batch entries; site_gradients != nullptr or embedded_entry: mqc_hip_scf_gradient_embedded_batch;
+// initial_density / spin_densities_out (either may be NULL): mqc_hip_scf_run_batch_restart
 static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,
                               const mqc_hip_basis_t* orbitals, const mqc_hip_basis_t* auxes,
                               const mqc_hip_scf_options_t* opts, mqc_hip_scf_result_t* results, bool embedded_entry,
-                              double* const* site_gradients)
+                              double* const* site_gradients, const double* const* initial_density = nullptr,
+                              double* const* spin_densities_out = nullptr)
 {
     if (!ctx) return fail(MQC_HIP_ERR_VALIDATION, "null context (call mqc_hip_context_get first)");
     if (nfrag < 0 || (nfrag > 0 && (!mols || !orbitals || !opts || !results)))
@@ -1330,6 +1381,8 @@ static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip
         std::vector<const mqc_hip_molecule_t*> mol;
         std::vector<mqc_hip_scf_result_t*> res;
         std::vector<double*> pcg;
+        std::vector<const double*> d0;
+        std::vector<double*> spin;
         std::shared_ptr<AtomicGuess> guess;
         int rc = MQC_HIP_OK;
         std::string msg;
@@ -1370,7 +1423,29 @@ static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip
                 continue;
             }
         }
-        if (opts->guess == MQC_HIP_GUESS_SAD || opts->guess == MQC_HIP_GUESS_SAC) {
+        // supplied densities: their size follows from the run's spin treatment; one with a non-finite entry fails its own
+        // fragment and nothing else
+        std::vector<int64_t> run_idx;
+        bool any_d0 = false, all_d0 = initial_density != nullptr;
+        {
+            const size_t nn = (size_t)w.topo->nao * w.topo->nao;
+            const size_t cnt = runs_unrestricted(*opts, w.topo->multiplicity, w.topo->nelec) ? 2 * nn : nn;
+            for (auto i : idx) {
+                const double* d = initial_density ? initial_density[i] : nullptr;
+                bool finite = true;
+                if (d) for (size_t k = 0; k < cnt && finite; ++k) finite = std::isfinite(d[k]);
+                if (!finite) {
+                    fill_error(&results[i], "initial density: a non-finite entry");
+                    set_error("initial density of fragment " + std::to_string(i) + ": a non-finite entry");
+                    worst = MQC_HIP_ERR_VALIDATION;
+                    continue;
+                }
+                run_idx.push_back(i);
+                if (d) any_d0 = true; else all_d0 = false;
+            }
+        }
+        if (run_idx.empty()) continue;
+        if ((opts->guess == MQC_HIP_GUESS_SAD || opts->guess == MQC_HIP_GUESS_SAC) && !all_d0) {
             // the free atoms are solved here, before any group of this call holds the pools (nested one-atom calls)
             w.guess = std::make_shared<AtomicGuess>();
             rc = build_atomic_guess(ctx, mols[idx[0]], orbitals[idx[0]], *w.topo, opts->guess, opts->density_fitting != 0, *w.guess, err);
@@ -1380,15 +1455,18 @@ static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip
                 w.guess.reset();
             }
         }
-        for (auto i : idx) {
+        for (auto i : run_idx) {
             w.xyz.push_back(mols[i].xyz); w.mol.push_back(&mols[i]); w.res.push_back(&results[i]);
             if (embedded_entry) w.pcg.push_back(site_gradients ? site_gradients[i] : nullptr);
+            if (any_d0) w.d0.push_back(initial_density[i]);
+            if (spin_densities_out) w.spin.push_back(spin_densities_out[i]);
         }
         work.push_back(std::move(w));
     }
     auto run_one = [&](Work& w, int lane) {
         (void)hipSetDevice(ctx->device);
-        w.rc = run_batch(ctx, *w.topo, w.aux.get(), w.xyz, *opts, w.res, lane, w.guess.get(), w.mol, embedded_entry ? &w.pcg : nullptr);
+        w.rc = run_batch(ctx, *w.topo, w.aux.get(), w.xyz, *opts, w.res, lane, w.guess.get(), w.mol, embedded_entry ? &w.pcg : nullptr,
+                         w.d0.empty() ? nullptr : &w.d0, w.spin.empty() ? nullptr : &w.spin);
         if (w.rc != MQC_HIP_OK) w.msg = mqc_hip_last_error();      // the error text is thread-local
     };
     if (work.size() >= 2 && ctx->concurrent_groups) {
@@ -1425,6 +1503,14 @@ int mqc_hip_scf_run_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_mol
                           const mqc_hip_scf_options_t* opts, mqc_hip_scf_result_t* results)
 {
     return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, opts, results, false, nullptr);
+}
+
+int mqc_hip_scf_run_batch_restart(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,
+                                  const mqc_hip_basis_t* orbitals, const mqc_hip_basis_t* auxes,
+                                  const mqc_hip_scf_options_t* opts, mqc_hip_scf_result_t* results,
+                                  const double* const* initial_density, double* const* spin_densities_out)
+{
+    return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, opts, results, false, nullptr, initial_density, spin_densities_out);
 }
 
 int mqc_hip_scf_gradient_embedded_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,

@@ -376,6 +376,9 @@ void launch_direct_setup(const BatchView& bv, const Topology& topo, hipStream_t 
 void launch_jk_direct(const BatchView& bv, const Topology& topo, double thresh, bool only_active, hipStream_t s);
 void launch_orthogonalizer(const BatchView& bv, hipStream_t s);
 void launch_guess(const BatchView& bv, int guess_kind, hipStream_t s);
+// restart: the densities uploaded to W0 (beta: W1) of the fragments with flags[f] != 0 (nullptr: all) projected onto
+// SCF states of this geometry (kern_scf.hip, restart_kernel)
+void launch_restart(const BatchView& bv, const int* flags, hipStream_t s);
 void launch_broadcast(double* dst, const double* src, size_t count, int nfrag, hipStream_t s);   // dst[f][i] = src[i]
 void launch_scf_step(const BatchView& bv, hipStream_t s);
 void launch_syev(int n, double* dA, double* dw, double* dV, hipStream_t s);

@@ -610,6 +610,49 @@ __global__ void __launch_bounds__(NT) guess_kernel(BatchView bv, int guess_kind)
     }
 }
 
+// Restart from the caller's densities (mqc_hip_scf_run_batch_restart).  D0 of fragment f sits in its W0 (the beta spin's
+// in W1); fragments with flags[f] == 0 keep the guess they already have (flags == nullptr: every fragment restarts).
+// D0 comes from another geometry, another field or two monomers side by side: it is not idempotent in THIS overlap
+// metric and need not even carry the right trace.  The generalised eigenproblem of F_r = -S D0s S (D0s = (D0 + D0^T)/2)
+// in the metric S has D0's natural orbitals as eigenvectors and minus their occupations as eigenvalues, so its lowest
+// n_occ pairs are the most occupied orbitals, and the density diagonalize_and_density forms from them is the idempotent
+// density of the right electron count closest to D0 -- D0 itself when D0 already was one.  Unrestricted runs project each
+// spin density with its own occupation.  The orbitals come with it (the fitted exchange needs C_occ), Vprev is set for
+// the warm-started Jacobi, and the state the first step reads is set as guess_kernel sets it.
+// q.D and q.C serve as scratch on the way: both are rewritten by the diagonalisation.
+template <int JM>
+__global__ void __launch_bounds__(NT) restart_kernel(BatchView bv, const int* __restrict__ flags)
+{
+    extern __shared__ double lds[];
+    const int f = blockIdx.x, n = bv.n, tid = threadIdx.x;
+    if (flags != nullptr && flags[f] == 0) return;
+    FragPtrs p = frag_ptrs(bv, f);
+    const int m = p.istate[2];
+    const size_t nn = (size_t)n * n;
+    JacobiLds jl = carve_jacobi(lds, m, JM, nullptr, (JM == 0) ? bv.W + ((size_t)blockIdx.x * 6 + 4) * n * n + n : nullptr);
+    const int nspin = bv.uhf ? 2 : 1;
+    for (int spin = 0; spin < nspin; ++spin) {
+        FragPtrs q = spin ? frag_ptrs_beta(bv, f) : p;
+        const double* D0 = p.W + (size_t)spin * nn;
+        double* const Ds = q.D; double* const SD = q.C; double* const Fr = q.F;
+        for (int idx = tid; idx < n * n; idx += NT) {
+            const int i = idx / n, j = idx - i * n;
+            Ds[idx] = 0.5 * (D0[idx] + D0[j * n + i]);
+        }
+        __syncthreads();
+        wg_gemm_mfma<false, false>(n, n, n, q.S, n, Ds, n, [&](int i, int j, double v) { SD[i * n + j] = v; });       // S D0s
+        wg_gemm_mfma<false, false>(n, n, n, SD, n, q.S, n, [&](int i, int j, double v) { Fr[i * n + j] = -v; });      // -(S D0s) S
+        if (bv.uhf) diagonalize_and_density<JM, false>(bv, q, jl, m, spin ? bv.Vprevb : bv.Vprev, spin ? bv.nbeta : bv.nalpha, 1.0);
+        else diagonalize_and_density<JM, false>(bv, q, jl, m);
+        __syncthreads();
+    }
+    if (tid == 0) {
+        p.istate[0] = ST_ITER; p.istate[1] = 0; p.istate[3] = 0;
+        p.diis_state[0] = 0; p.diis_state[1] = 0;
+        p.scal[0] = 0.0; p.scal[1] = 0.0; p.scal[2] = 0.0; p.scal[3] = 0.0; p.scal[4] = 0.0;
+    }
+}
+
 // slot (1-based) of the age-th oldest entry, age = 1..n_stored (diis_slot_of_age, mqc_diis.f90:89-103)
 __host__ __device__ inline int diis_slot_of_age(int newest, int n_stored, int max_vectors, int age)
 {
@@ -966,6 +1009,7 @@ size_t scf_lds_bytes(int n)
 }
 void launch_orthogonalizer_wide(const BatchView& bv, hipStream_t s);
 void launch_guess_wide(const BatchView& bv, int guess_kind, hipStream_t s);
+void launch_restart_wide(const BatchView& bv, const int* flags, hipStream_t s);
 void launch_scf_step_wide(const BatchView& bv, hipStream_t s);
 // batches of at most this many fragments take the 512-thread build (MQC_HIP_SCF_WIDE_MAX; 0 turns it off)
 static int scf_wide_max()
@@ -1009,6 +1053,15 @@ void MQC_SCF_PUBLIC(launch_guess)(const BatchView& bv, int guess_kind, hipStream
 #endif
     const size_t lds = scf_lds_bytes(bv.n);
     MQC_JACOBI_DISPATCH(guess_kernel, bv.n, bv.nfrag, lds, s, bv, guess_kind);
+}
+
+void MQC_SCF_PUBLIC(launch_restart)(const BatchView& bv, const int* flags, hipStream_t s)
+{
+#if MQC_SCF_NT == 256
+    if (bv.nfrag <= scf_wide_max()) return launch_restart_wide(bv, flags, s);
+#endif
+    const size_t lds = scf_lds_bytes(bv.n);
+    MQC_JACOBI_DISPATCH(restart_kernel, bv.n, bv.nfrag, lds, s, bv, flags);
 }
 
 static void apply_jacobi_env()

@@ -58,6 +58,7 @@ class EmbeddedJob:
     field_atoms: Sequence[int] = ()          # outside atoms that act as point charges (empty = none)
     field_charges: Optional[np.ndarray] = None   # their weights: Mulliken charge (far) or bare nuclear charge (near)
     h_extra: Optional[np.ndarray] = None     # (n, n): the near fragments' exact Coulomb operator, or None
+    initial_density: Optional[np.ndarray] = None   # (n, n): total density the SCF starts from (run_fmo2's restart), or None
 
 
 @dataclass
@@ -69,6 +70,18 @@ class EmbeddedResult:
     charges: Optional[np.ndarray] = None     # Mulliken, one per atom of the job
     u: Optional[np.ndarray] = None
     error: str = ""
+
+
+def block_diagonal(blocks: Sequence[np.ndarray]) -> np.ndarray:
+    """The densities of an n-mer's members side by side on the diagonal, members in order: the n-mer's starting density."""
+    n = sum(int(b.shape[0]) for b in blocks)
+    out = np.zeros((n, n))
+    at = 0
+    for b in blocks:
+        k = int(b.shape[0])
+        out[at:at + k, at:at + k] = b
+        at += k
+    return out
 
 
 Solver = Callable[[Sequence[EmbeddedJob]], List[EmbeddedResult]]
@@ -184,8 +197,10 @@ def hip_solver(system: FragmentedSystem, settings: ScfSettings) -> Solver:
                 g.h_extra = np.stack([jobs[k].h_extra for k in ks])
             groups.append(g); index.append(ks)
         extras_out: list = []
+        # jobs that bring a starting density send the pass through the restart entry; none: today's entry
+        d0 = [[jobs[k].initial_density for k in ks] for ks in index] if any(j.initial_density is not None for j in jobs) else None
         recs = run_hip_scf_groups(settings, groups, extras=("density", "embedding_matrix", "mulliken_charges"),
-                                  extras_out=extras_out)
+                                  extras_out=extras_out, initial_densities=d0)
         out = [EmbeddedResult() for _ in jobs]
         for ks, rec, ex in zip(index, recs, extras_out):
             for pos, k in enumerate(ks):
@@ -220,7 +235,7 @@ def run_fmo2(system: FragmentedSystem, settings: ScfSettings, expansion: str = "
              outer_tol: float = 1.0e-7, rank: int = 0, world: int = 1,
              allreduce: Optional[Callable[[np.ndarray], np.ndarray]] = None, solver: Optional[Solver] = None,
              esp: str = "ptc", resppc: float = 2.0, coulomb: Optional[Coulomb] = None, level: int = 2,
-             far_field: str = "mulliken", charges: Optional[Charges] = None) -> FmoRun:
+             far_field: str = "mulliken", charges: Optional[Charges] = None, restart: bool = False) -> FmoRun:
     """FMO2 ("fmo") or electrostatically embedded MBE2 ("mbe") of whole-molecule fragments; the field of the others is
     Mulliken point charges (`esp = "ptc"`) or, for fragments within `resppc`, bare nuclei plus the exact Coulomb
     operator of their electrons (`esp = "exact"`, the reference's FMO default).
@@ -231,7 +246,11 @@ def run_fmo2(system: FragmentedSystem, settings: ScfSettings, expansion: str = "
 
     `far_field = "chelpg"` takes the charges that stand for outside atoms from `charges` (all fragments of a pass with
     their densities in one call; default: the engine-backed `charges.hip_chelpg_charges`) instead of the SCF's Mulliken
-    charges; the exchange between ranks carries whatever that model produced."""
+    charges; the exchange between ranks carries whatever that model produced.
+
+    `restart`: every monomer of an outer pass starts its SCF from its own density of the previous pass (same geometry,
+    slightly different field) and every n-mer from the block-diagonal sum of its members' latest densities, in the n-mer's
+    basis order (members in order), instead of the settings' guess.  Same energies, fewer SCF iterations."""
     if expansion not in ("fmo", "mbe"):
         raise ValueError("expansion must be 'fmo' or 'mbe'")
     if world > 1 and allreduce is None:
@@ -312,6 +331,9 @@ def run_fmo2(system: FragmentedSystem, settings: ScfSettings, expansion: str = "
     def monomer_pass(bare: bool):
         nonlocal total_iters
         monomer_jobs = [EmbeddedJob(frags[i]) for i in mine] if (bare or esp == "none") else embedded_jobs([[i] for i in mine])
+        if restart:
+            for i, job in zip(mine, monomer_jobs):
+                job.initial_density = dens[i]          # None in the bare pass: nothing to start from yet
         res = solve(monomer_jobs)
         new_e = np.zeros(nfrag); new_i = np.zeros(nfrag); new_q = np.zeros(n_atoms)
         model_q: Dict[int, np.ndarray] = {}
@@ -375,6 +397,9 @@ def run_fmo2(system: FragmentedSystem, settings: ScfSettings, expansion: str = "
     my_terms = [t for k, t in enumerate(terms) if k % world == rank]
     nmer_jobs = ([EmbeddedJob(tuple(a for m in t for a in frags[m])) for t in my_terms] if esp == "none"
                  else embedded_jobs([list(t) for t in my_terms]))
+    if restart:
+        for members, job in zip(my_terms, nmer_jobs):
+            job.initial_density = block_diagonal([dens[m] for m in members])
     res = solve(nmer_jobs) if nmer_jobs else []
     value = np.zeros(len(terms)); resp = np.zeros(len(terms))
     index = {t: k for k, t in enumerate(terms)}

@@ -300,6 +300,7 @@ class MbeRun:
     owned: np.ndarray
     errors: List[str]
     gradient: Optional[np.ndarray] = None      # (n_atoms, 3) weighted sum of the owned fragments' gradients (zero-padded share)
+    densities: Optional[Dict[Tuple[int, ...], np.ndarray]] = None   # run_mbe with restart / initial_densities: converged total density per owned term
 
 
 def _group_layout(system: FragmentedSystem, term_list: Sequence[Tuple[int, ...]]):
@@ -354,12 +355,24 @@ def build_fragment_groups(system: FragmentedSystem, term_list: Sequence[Tuple[in
 def run_mbe(system: FragmentedSystem, settings: ScfSettings, level: int = 2,
             cutoffs: Optional[Dict[int, float]] = None, rank: int = 0, world: int = 1,
             terms: Optional[List[Tuple[int, ...]]] = None, want_gradient: bool = False,
-            costs: Optional[Sequence[float]] = None) -> MbeRun:
+            costs: Optional[Sequence[float]] = None, restart: bool = False,
+            initial_densities: Optional[Dict[Tuple[int, ...], np.ndarray]] = None) -> MbeRun:
     """`costs` (one per term, e.g. term_costs(...)): the static partition is longest-processing-time-first over them
-    instead of round-robin -- for lists whose terms of one order do not cost the same."""
+    instead of round-robin -- for lists whose terms of one order do not cost the same.
+
+    `restart`: the owned monomers run first, in one engine call, and every larger term starts from the block-diagonal sum
+    of its monomers' converged densities (members in order = the term's basis order) in a second call; a term with a
+    monomer this rank does not own starts from the settings' guess.  `initial_densities` maps terms to starting densities
+    of the caller's (the previous step of a trajectory: MbeRun.densities of that step); it wins over the monomer sum.
+    Either one sends the SCFs through the restart entry and makes the run return its converged densities.  Energies only:
+    gradients come from a run without them."""
     from .methods import run_hip_scf_groups
     terms = terms if terms is not None else generate_mbe_term_list(system, level, cutoffs)
     owned = partition_terms(len(terms), rank, world) if costs is None else partition_terms_lpt(costs, rank, world)
+    if restart or initial_densities is not None:
+        if want_gradient:
+            raise ValueError("run_mbe: starting densities and want_gradient do not combine")
+        return _run_mbe_restart(system, settings, terms, owned, restart, initial_densities or {})
     groups, positions = build_fragment_groups(system, [terms[i] for i in owned])
     owned_arr = np.asarray(owned)
     energies = np.zeros(len(terms))
@@ -390,6 +403,50 @@ def run_mbe(system: FragmentedSystem, settings: ScfSettings, level: int = 2,
             msg = bytes(rec["message"][k]).split(b"\0", 1)[0].decode(errors="replace")
             errors.append("term %s: %s" % (terms[tix[k]], msg))
     return MbeRun(terms, energies, iters, owned, errors, gradient_total)
+
+
+def _run_mbe_restart(system: FragmentedSystem, settings: ScfSettings, terms: List[Tuple[int, ...]], owned: np.ndarray,
+                     restart: bool, start: Dict[Tuple[int, ...], np.ndarray]) -> MbeRun:
+    """run_mbe through the restart entry: one engine call, or with `restart` two -- monomers, then everything larger."""
+    from .methods import run_hip_scf_groups
+    owned_list = [int(i) for i in owned]
+    phases = [[i for i in owned_list if len(terms[i]) == 1], [i for i in owned_list if len(terms[i]) > 1]] if restart else [owned_list]
+    energies = np.zeros(len(terms)); iters = np.zeros(len(terms), dtype=np.int64)
+    errors: List[str] = []
+    densities: Dict[Tuple[int, ...], np.ndarray] = {}
+
+    def start_of(term: Tuple[int, ...]):
+        d = start.get(tuple(term))
+        if d is not None or not restart or len(term) < 2 or any((m,) not in densities for m in term):
+            return d
+        blocks = [densities[(m,)] for m in term]
+        n = sum(b.shape[0] for b in blocks)
+        out = np.zeros((n, n))
+        at = 0
+        for b in blocks:
+            out[at:at + b.shape[0], at:at + b.shape[0]] = b
+            at += b.shape[0]
+        return out
+
+    for phase in phases:
+        if not phase:
+            continue
+        phase_arr = np.asarray(phase)
+        groups, positions = build_fragment_groups(system, [terms[i] for i in phase])
+        d0 = [[start_of(terms[i]) for i in phase_arr[pos]] for pos in positions]
+        extras_out: list = []
+        recs = run_hip_scf_groups(settings, groups, extras=("density",), extras_out=extras_out, initial_densities=d0)
+        for pos, rec, ex in zip(positions, recs, extras_out):
+            tix = phase_arr[pos]
+            ok = rec["has_error"] == 0
+            energies[tix[ok]] = rec["e_total"][ok]
+            iters[tix[ok]] = rec["iterations"][ok]
+            for k in np.nonzero(ok)[0]:
+                densities[tuple(terms[tix[k]])] = ex["density"][k]
+            for k in np.nonzero(~ok)[0]:
+                msg = bytes(rec["message"][k]).split(b"\0", 1)[0].decode(errors="replace")
+                errors.append("term %s: %s" % (terms[tix[k]], msg))
+    return MbeRun(terms, energies, iters, owned, errors, None, densities)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -7,7 +7,8 @@
   run_hip_scf         <- run_cuest_scf         (backends/cuest/backend/mqc_cuest_bridge.f90:32-39)
   hip_backend_available <- cuest_backend_available (:20-30)
   HFMethod.calc_energy  <- hf_calc_energy / hf_run (src/methods/mqc_method_hf.F90:113-217)
-  run_hip_scf_batch   <- the batch-submit entry the worker loop would use
+  run_hip_scf_batch   <- the batch-submit entry the worker loop would use; with
+                         initial_densities it goes through mqc_hip_scf_run_batch_restart (no counterpart)
   run_hip_embedded_gradients <- (no counterpart) gradients of fragments in point charges, on atoms and on the charges
                          (mqc_hip_scf_gradient_embedded_batch)
   run_hip_esp         <- (no counterpart) the potential of converged densities at arbitrary points (mqc_hip_esp_batch)
@@ -134,6 +135,9 @@ class CalculationResult:
     has_hessian: bool = False
     dipole_derivatives: Optional[np.ndarray] = None    # (3, 3 n_atoms) d mu / d R
     has_dipole_derivatives: bool = False
+    # filled by the restart path (run_hip_scf_batch / run_hip_scf with starting densities): what the next start needs
+    density: Optional[np.ndarray] = None               # (n_ao, n_ao) total density
+    spin_densities: Optional[np.ndarray] = None        # (2, n_ao, n_ao) alpha, beta: unrestricted runs only
 
 
 DEFAULT_DISPLACEMENT = 0.005         # Bohr, src/core/mqc_calculation_defaults.f90:13
@@ -241,9 +245,24 @@ def _fill(result: CalculationResult, r: capi.ScfResult, eps: Optional[np.ndarray
     return result
 
 
+def runs_unrestricted(settings: ScfSettings, multiplicity: int, nelec: int) -> bool:
+    """The engine's own decision (plan_batch): unrestricted iff forced, multiplicity != 1 or an odd electron count."""
+    return bool(settings.unrestricted) or int(multiplicity) != 1 or int(nelec) % 2 != 0
+
+
 def run_hip_scf(settings: ScfSettings, fragment: PhysicalFragment, result: Optional[CalculationResult] = None,
-                want_gradient: bool = False) -> CalculationResult:
-    """One fragment through the engine: the drop-in for run_cuest_scf."""
+                want_gradient: bool = False, initial_density: Optional[np.ndarray] = None) -> CalculationResult:
+    """One fragment through the engine: the drop-in for run_cuest_scf.  `initial_density` ((n_ao, n_ao) total density of
+    a restricted run, (2, n_ao, n_ao) alpha and beta of an unrestricted one) starts the SCF from it
+    (run_hip_scf_batch); the result then carries `density` and, unrestricted, `spin_densities`."""
+    if initial_density is not None:
+        if want_gradient:
+            raise ValueError("run_hip_scf: initial_density and want_gradient do not combine; converge first, then ask for the gradient")
+        r = run_hip_scf_batch(settings, [fragment], initial_densities=[initial_density])[0]
+        if result is None:
+            return r
+        result.__dict__.update(r.__dict__)
+        return result
     result = result if result is not None else CalculationResult()
     try:
         lib = capi.load_library()
@@ -335,7 +354,8 @@ class FragmentGroup:
 def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], want_gradient: bool = False,
                        gradients_out: Optional[list] = None, extras: Sequence[str] = (),
                        extras_out: Optional[list] = None, site_gradients_out: Optional[list] = None,
-                       status_out: Optional[list] = None) -> List[np.ndarray]:
+                       status_out: Optional[list] = None, initial_densities: Optional[Sequence] = None,
+                       spin_densities_out: Optional[list] = None) -> List[np.ndarray]:
     """All fragments of all groups in ONE mqc_hip_scf_run_batch call; returns, per group, a structured array
     viewing the engine's result records (fields of capi.ScfResult: e_total, iterations, has_error, message ...).
 
@@ -348,8 +368,21 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
 
     `site_gradients_out` (a list) sends the batch through mqc_hip_scf_gradient_embedded_batch instead: the gradient is
     forced on, and one (m, n_pc, 3) array per group (n_pc = 0 for a group without charges) is appended to it -- the
-    derivative of e_total with respect to the charges' positions.  `status_out` receives the call's status code."""
+    derivative of e_total with respect to the charges' positions.  `status_out` receives the call's status code.
+
+    `initial_densities` and `spin_densities_out` send the batch through mqc_hip_scf_run_batch_restart.
+    `initial_densities` holds one entry per group: None (the whole group starts from settings.guess) or m entries, each
+    None or that fragment's starting density -- (n_ao, n_ao), the total density, when the fragment runs restricted,
+    (2, n_ao, n_ao), alpha and beta, when it runs unrestricted (runs_unrestricted: forced, multiplicity != 1 or an odd
+    electron count).  Any finite density of the right size is legal: the engine projects it onto an SCF state of the new
+    geometry.  `spin_densities_out` (a list) receives one (m, 2, n_ao, n_ao) array per group, written for the fragments
+    that ran unrestricted (zeros elsewhere)."""
     embedded = site_gradients_out is not None
+    restart = initial_densities is not None or spin_densities_out is not None
+    if restart and embedded:
+        raise ValueError("starting densities and the embedded-gradient entry do not combine")
+    if initial_densities is not None and len(initial_densities) != len(groups):
+        raise ValueError("initial_densities must hold one entry per group")
     want_gradient = bool(want_gradient) or embedded
     sizes = [int(g.xyz.shape[0]) for g in groups]
     n = int(sum(sizes))
@@ -445,7 +478,41 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
             if extras_out is not None:
                 extras_out.append(got)
             keep.append(got)
-    if embedded:
+    if restart:
+        d0_ptr = np.zeros(n, dtype=np.uint64)
+        spin_ptr = np.zeros(n, dtype=np.uint64)
+        lo = 0
+        for gi, (g, m) in enumerate(zip(groups, sizes)):
+            z = np.ascontiguousarray(g.element_numbers, dtype=np.int32)
+            nao = _flat_basis_z(settings.basis_set, z).nao
+            entries = None if initial_densities is None else initial_densities[gi]
+            if entries is not None and m:
+                if len(entries) != m:
+                    raise ValueError("initial_densities[%d] must hold one entry per fragment of the group" % gi)
+                mult = np.broadcast_to(mols["multiplicity"][lo:lo + m], (m,))
+                nel = np.broadcast_to(mols["nelec"][lo:lo + m], (m,))
+                for k, d in enumerate(entries):
+                    if d is None:
+                        continue
+                    a = np.ascontiguousarray(d, dtype=np.float64)
+                    want = (2, nao, nao) if runs_unrestricted(settings, mult[k], nel[k]) else (nao, nao)
+                    if a.shape != want:
+                        raise ValueError("initial density of fragment %d of group %d has shape %s; this run needs %s"
+                                         % (k, gi, a.shape, want))
+                    keep.append(a)
+                    d0_ptr[lo + k] = a.ctypes.data
+            if spin_densities_out is not None:
+                sd = np.zeros((m, 2, nao, nao))
+                spin_densities_out.append(sd)
+                if m:
+                    spin_ptr[lo:lo + m] = sd.ctypes.data + np.arange(m, dtype=np.uint64) * np.uint64(2 * nao * nao * 8)
+            lo += m
+        rc = lib.mqc_hip_scf_run_batch_restart(ctx, n, mols.ctypes.data_as(C.POINTER(capi.Molecule)),
+                                               bass.ctypes.data_as(C.POINTER(capi.Basis)),
+                                               auxs.ctypes.data_as(C.POINTER(capi.Basis)) if df else None, C.byref(opts), res,
+                                               d0_ptr.ctypes.data_as(C.POINTER(capi.c_double_p)) if initial_densities is not None else None,
+                                               spin_ptr.ctypes.data_as(C.POINTER(capi.c_double_p)) if spin_densities_out is not None else None)
+    elif embedded:
         # one (m, n_pc, 3) array per group; entry i of the pointer array is fragment i's slice (0 = no charges)
         site_ptr = np.zeros(n, dtype=np.uint64)
         sites, lo = [], 0
@@ -540,9 +607,16 @@ def run_hip_esp(settings: ScfSettings, group: FragmentGroup, densities, points, 
     return out
 
 
-def run_hip_scf_batch(settings: ScfSettings, fragments: Sequence[PhysicalFragment]) -> List[CalculationResult]:
-    """Many independent fragments in one call (mqc_hip_scf_run_batch), results as CalculationResult objects."""
+def run_hip_scf_batch(settings: ScfSettings, fragments: Sequence[PhysicalFragment],
+                      initial_densities: Optional[Sequence] = None) -> List[CalculationResult]:
+    """Many independent fragments in one call (mqc_hip_scf_run_batch), results as CalculationResult objects.
+
+    `initial_densities` (one entry per fragment: None, or a starting density as run_hip_scf_groups describes) sends the
+    call through mqc_hip_scf_run_batch_restart; every result then carries its converged `density` and, where the
+    fragment ran unrestricted, its `spin_densities` -- what the next restart takes."""
     n = len(fragments)
+    if initial_densities is not None and len(initial_densities) != n:
+        raise ValueError("initial_densities must hold one entry per fragment")
     results = [CalculationResult() for _ in range(n)]
     if n == 0:
         return results
@@ -558,9 +632,22 @@ def run_hip_scf_batch(settings: ScfSettings, fragments: Sequence[PhysicalFragmen
                                     np.array([fragments[i].multiplicity for i in idx], dtype=np.int32),
                                     f0.ghost, np.array([fragments[i].nelec for i in idx], dtype=np.int32)))
         index.append(idx)
-    for idx, rec in zip(index, run_hip_scf_groups(settings, groups)):
-        for i, r in zip(idx, rec):
+    if initial_densities is None:
+        for idx, rec in zip(index, run_hip_scf_groups(settings, groups)):
+            for i, r in zip(idx, rec):
+                _fill_record(results[i], r)
+        return results
+    extras_out: list = []
+    spin_out: list = []
+    recs = run_hip_scf_groups(settings, groups, extras=("density",), extras_out=extras_out,
+                              initial_densities=[[initial_densities[i] for i in idx] for idx in index], spin_densities_out=spin_out)
+    for idx, rec, ex, sd in zip(index, recs, extras_out, spin_out):
+        for pos, (i, r) in enumerate(zip(idx, rec)):
             _fill_record(results[i], r)
+            if results[i].has_energy:
+                results[i].density = ex["density"][pos].copy()
+                if runs_unrestricted(settings, fragments[i].multiplicity, fragments[i].nelec):
+                    results[i].spin_densities = sd[pos].copy()
     return results
 
 
