@@ -1,0 +1,64 @@
+// driver.hpp -- what the batch driver (engine.cpp) and the stage-level entry points (stage_entries.cpp) share.
+// Declarations only; everything here is defined in engine.cpp.
+#pragma once
+#include "engine.hpp"
+
+namespace mqc {
+
+// the HIP error a stage left behind, as the call's failure
+int stage_check(const char* stage);
+
+// One pipeline slot: a stream with its own pools and events.  While the SCF loop of chunk k runs on
+// one slot, the integrals of chunk k+1 are formed on the other (compute-bound ERI kernels fill the
+// gaps the HBM-bound J/K stream and the per-iteration host round trip leave).
+struct Slot {
+    int id;
+    hipStream_t s;
+    DevicePool* pool[NPOOL];          // indexed by POOL_*
+    hipEvent_t e0, e1, e2, e3, q0, q1, s0, s1;
+    int* h_counter;
+};
+Slot make_slot(mqc_hip_context* ctx, int id, int* h_counter);
+// carve one chunk's arrays out of the slot's pools (carve_chunk) and upload the block table of a triangular tensor
+int carve_slot(mqc_hip_context* ctx, const Slot& sl, const BatchPlan& plan, const TopologyDev& td, int nfrag, BatchView& bv);
+int upload_topology(mqc_hip_context* ctx, const Topology& topo, TopologyDev& td, DevicePool* pool = nullptr, hipStream_t stream = nullptr);
+
+bool incore_supported(int n);
+// The decisions of a batch call of ntot fragments that do not wait for the grid: functional, spin, two-electron path,
+// Schwarz thresholds; then the refusals of validate_options
+int plan_batch(const mqc_hip_scf_options_t& o, const Topology& topo, int ntot, BatchPlan& p, std::string& msg);
+
+// Starting density of the superposed-atom guesses (one per topology: it does not depend on the geometry) and, for
+// the density-fitted exchange, its pseudo-orbitals v_i sqrt(n_i / 2) (density_pseudo_orbitals, mqc_libcint_rhf.f90:1413-1462)
+struct AtomicGuess {
+    std::vector<double> D0;      // [n*n] total density, block-diagonal over the atoms
+    std::vector<double> Cp;      // [n*n] row-major, nmodes columns used
+    int nmodes = 0;
+};
+
+// What the stages of one batch call share besides the plan: the inputs, ordered by compactness, the device topology
+// and grid, and the statistics, gathered locally (two lanes may run at once) and merged at the end
+struct Batch {
+    const Topology& topo;
+    const Topology* aux;
+    const mqc_hip_scf_options_t& opts;
+    const AtomicGuess* guess;
+    std::vector<const double*> xyz;
+    std::vector<mqc_hip_scf_result_t*> results;
+    std::vector<const mqc_hip_molecule_t*> mols;     // embedded groups only (point charges, h_extra)
+    std::vector<double*> pcgrad;                     // mqc_hip_scf_gradient_embedded_batch only: the callers' site gradients (or null)
+    // mqc_hip_scf_run_batch_restart only: the callers' starting densities (null entry: opts.guess) and where an
+    // unrestricted run's spin densities go (null entry: nowhere); empty when the call brought none
+    std::vector<const double*> d0;
+    std::vector<double*> spin_out;
+    TopologyDev td{}, tdx{};
+    GridDev grid;
+    Stats stats;
+};
+
+// radial cache of the quadrature: MQC_HIP_XC_RADIAL_CACHE=0 turns it off
+bool xc_radial_cache_on();
+// exchange-correlation: per-element grid templates and the per-topology point list
+int upload_grid(mqc_hip_context* ctx, Batch& b, DevicePool& pool, hipStream_t s);
+
+}  // namespace mqc

@@ -1,11 +1,12 @@
-// engine.cpp -- context, batch driver and the extern "C" entry points of libmqc_hip.so.
+// engine.cpp -- context, batch driver and the SCF extern "C" entry points of libmqc_hip.so (the stage-level entry
+// points are in stage_entries.cpp; driver.hpp declares what the two share).
 //
 // Host control flow of one batch (the device-resident SCF loop of
 // backends/cuest/backend/mqc_cuest_scf.f90:281-611, re-cut for whole batches):
 //   upload geometry -> int1e -> orthogonaliser -> ERI tensor -> guess ->
 //   repeat { J/K stream ; scf_step ; read ONE int (fragments still running) } -> fetch results
 // Only that one integer crosses the bus per iteration.
-#include "engine.hpp"
+#include "driver.hpp"
 #include "md_integrals.hpp"
 #include <algorithm>
 #include <array>
@@ -29,19 +30,13 @@ void int1e_reset_state();                                                 // ker
 void eri_schwarz_view(int slot, const double** q, double* thresh);        // kern_eri.hip
 void launch_jk_direct_incremental(const BatchView& bv, const Topology& topo, double thresh, bool only_active, hipStream_t s);   // kern_eri.hip
 static DevicePool g_grad_pool[2];
-// kern_esp.hip: potential of nfrag densities at their points (device arrays of one chunk); doubles of records per fragment
-void launch_esp(const TopologyDev& td, const Topology& topo, const double* boys_table, const double* c2s, int nfrag, const double* d_xyz,
-                const double* d_D, double* d_rec, const double* d_pts, const int* d_npts, int max_points, int include_nuclei, double* d_out,
-                hipStream_t s);
-size_t esp_record_doubles(const Topology& topo);
-static DevicePool g_esp_pool;
 // kern_grad_pc.hip: the point charges' part of an embedded fragment's gradient (atoms' part added into d_grad, the sites'
 // gradient into d_pcgrad [nfrag][npc][3]); doubles of records per fragment
 bool launch_pc_gradient(const BatchView& bv, const Topology& topo, const double* Dtot, double* d_grad, double* d_pcgrad, double* d_rec,
                         hipStream_t s, std::string& err);
 size_t gradpc_record_doubles(const Topology& topo);
 
-static int stage_check(const char* stage)
+int stage_check(const char* stage)
 {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MQC_HIP_ERR_DEVICE, std::string("HIP error after stage '") + stage + "': " + hipGetErrorString(e));
@@ -70,7 +65,7 @@ static size_t scratch_reservation_bytes(const mqc_hip_context* ctx)
     return (size_t)queues * SCRATCH_BOUND_PER_LANE * 64 * waves;
 }
 
-static int upload_topology(mqc_hip_context* ctx, const Topology& topo, TopologyDev& td, DevicePool* pool = nullptr, hipStream_t stream = nullptr)
+int upload_topology(mqc_hip_context* ctx, const Topology& topo, TopologyDev& td, DevicePool* pool, hipStream_t stream)
 {
     if (!pool) pool = &ctx->pool_topo;
     const int ns = (int)topo.shells.size();
@@ -163,18 +158,7 @@ static int upload_topology(mqc_hip_context* ctx, const Topology& topo, TopologyD
     return MQC_HIP_OK;
 }
 
-// One pipeline slot: a stream with its own pools and events.  While the SCF loop of chunk k runs on
-// one slot, the integrals of chunk k+1 are formed on the other (compute-bound ERI kernels fill the
-// gaps the HBM-bound J/K stream and the per-iteration host round trip leave).
-struct Slot {
-    int id;
-    hipStream_t s;
-    DevicePool* pool[NPOOL];          // indexed by POOL_*
-    hipEvent_t e0, e1, e2, e3, q0, q1, s0, s1;
-    int* h_counter;
-};
-
-static Slot make_slot(mqc_hip_context* ctx, int id, int* h_counter)
+Slot make_slot(mqc_hip_context* ctx, int id, int* h_counter)
 {
     if (id == 0)
         return {0, ctx->stream, {&ctx->pool_main, &ctx->pool_eri, &ctx->pool_misc, &ctx->pool_gridw, &ctx->pool_df},
@@ -183,8 +167,7 @@ static Slot make_slot(mqc_hip_context* ctx, int id, int* h_counter)
             ctx->evb0, ctx->evb1, ctx->evb2, ctx->evb3, ctx->evq2, ctx->evq3, ctx->evs[1][0], ctx->evs[1][1], h_counter};
 }
 
-// carve one chunk's arrays out of the slot's pools (carve_chunk) and upload the block table of a triangular tensor
-static int carve_slot(mqc_hip_context* ctx, const Slot& sl, const BatchPlan& plan, const TopologyDev& td, int nfrag, BatchView& bv)
+int carve_slot(mqc_hip_context* ctx, const Slot& sl, const BatchPlan& plan, const TopologyDev& td, int nfrag, BatchView& bv)
 {
     static const char* const what[NPOOL] = {"SCF matrices", "ERI tensor", "counters", "grid weights", "fitted tensor"};
     BatchView probe{};
@@ -205,7 +188,7 @@ static int carve_slot(mqc_hip_context* ctx, const Slot& sl, const BatchPlan& pla
     return MQC_HIP_OK;
 }
 
-static bool incore_supported(int n)
+bool incore_supported(int n)
 {
     // the J/K kernel stages whole packed rows through LDS: 3 row-sized buffers must fit 160 KB
     const size_t np = (size_t)n * (n + 1) / 2;
@@ -252,10 +235,8 @@ static int validate_options(const mqc_hip_scf_options_t& o, const Topology& topo
     return MQC_HIP_OK;
 }
 
-// The decisions of a batch call of ntot fragments that do not wait for the grid: functional, spin, two-electron path,
-// Schwarz thresholds; then the refusals of validate_options
 static bool runs_unrestricted(const mqc_hip_scf_options_t& o, int multiplicity, int nelec);
-static int plan_batch(const mqc_hip_scf_options_t& o, const Topology& topo, int ntot, BatchPlan& p, std::string& msg)
+int plan_batch(const mqc_hip_scf_options_t& o, const Topology& topo, int ntot, BatchPlan& p, std::string& msg)
 {
     p.n = topo.nao; p.npair = topo.npair; p.natoms = topo.natoms;
     if (!parse_functional(o.functional, p.xc, msg)) return MQC_HIP_ERR_UNSUPPORTED;
@@ -296,35 +277,8 @@ static int refuse(const std::vector<mqc_hip_scf_result_t*>& results, int code, c
     return fail(code, msg);
 }
 
-// Starting density of the superposed-atom guesses (one per topology: it does not depend on the geometry) and, for
-// the density-fitted exchange, its pseudo-orbitals v_i sqrt(n_i / 2) (density_pseudo_orbitals, mqc_libcint_rhf.f90:1413-1462)
-struct AtomicGuess {
-    std::vector<double> D0;      // [n*n] total density, block-diagonal over the atoms
-    std::vector<double> Cp;      // [n*n] row-major, nmodes columns used
-    int nmodes = 0;
-};
 static DevicePool g_guess_pool[2];
 static DevicePool g_restart_pool[2];     // per slot: which fragments of the chunk restart from a supplied density
-
-// What the stages of one batch call share besides the plan: the inputs, ordered by compactness, the device topology
-// and grid, and the statistics, gathered locally (two lanes may run at once) and merged at the end
-struct Batch {
-    const Topology& topo;
-    const Topology* aux;
-    const mqc_hip_scf_options_t& opts;
-    const AtomicGuess* guess;
-    std::vector<const double*> xyz;
-    std::vector<mqc_hip_scf_result_t*> results;
-    std::vector<const mqc_hip_molecule_t*> mols;     // embedded groups only (point charges, h_extra)
-    std::vector<double*> pcgrad;                     // mqc_hip_scf_gradient_embedded_batch only: the callers' site gradients (or null)
-    // mqc_hip_scf_run_batch_restart only: the callers' starting densities (null entry: opts.guess) and where an
-    // unrestricted run's spin densities go (null entry: nowhere); empty when the call brought none
-    std::vector<const double*> d0;
-    std::vector<double*> spin_out;
-    TopologyDev td{}, tdx{};
-    GridDev grid;
-    Stats stats;
-};
 
 struct Job {
     int start = 0, nf = 0;
@@ -333,15 +287,14 @@ struct Job {
     std::vector<int> restart;      // per fragment of the chunk: 1 = starts from its supplied density
 };
 
-// radial cache of the quadrature: MQC_HIP_XC_RADIAL_CACHE=0 turns it off
-static bool xc_radial_cache_on()
+bool xc_radial_cache_on()
 {
     static const bool on = [] { const char* e = std::getenv("MQC_HIP_XC_RADIAL_CACHE"); return !(e && e[0] == '0'); }();
     return on;
 }
 
 // ---- exchange-correlation: per-element grid templates and the per-topology point list
-static int upload_grid(mqc_hip_context* ctx, Batch& b, DevicePool& pool, hipStream_t s)
+int upload_grid(mqc_hip_context* ctx, Batch& b, DevicePool& pool, hipStream_t s)
 {
     const Topology& topo = b.topo;
     std::map<int, std::pair<int, int>> tmpl_of_z;     // Z -> (offset, count) in the packed template arrays
@@ -904,44 +857,56 @@ static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& j
     return MQC_HIP_OK;
 }
 
+// One topology group of a batch call, in the caller's order: what run_batch runs and where its status goes
+struct Work {
+    const std::vector<int64_t>* idx;
+    std::shared_ptr<Topology> topo, aux;
+    std::vector<const double*> xyz;
+    std::vector<const mqc_hip_molecule_t*> mol;
+    std::vector<mqc_hip_scf_result_t*> res;
+    std::vector<double*> pcg;            // mqc_hip_scf_gradient_embedded_batch only: the site gradients (or null), else empty
+    std::vector<const double*> d0;       // mqc_hip_scf_run_batch_restart only: starting densities ...
+    std::vector<double*> spin;           // ... and the spin densities' destinations; empty when the call brought none
+    std::shared_ptr<AtomicGuess> guess;
+    int rc = MQC_HIP_OK;
+    std::string msg;
+};
+
 // lane < 0: the batch owns both slots (chunks alternate, next chunk prepared ahead); lane 0/1: it runs on that
 // slot only, so that two topology groups can be driven by two host threads at once
-static int run_batch(mqc_hip_context* ctx, const Topology& topo, const Topology* aux, const std::vector<const double*>& xyz_in,
-                     const mqc_hip_scf_options_t& opts, const std::vector<mqc_hip_scf_result_t*>& results_in, int lane,
-                     const AtomicGuess* atomic_guess, const std::vector<const mqc_hip_molecule_t*>& mols_in,
-                     const std::vector<double*>* pcgrad_in = nullptr /* mqc_hip_scf_gradient_embedded_batch: the site gradients */,
-                     const std::vector<const double*>* d0_in = nullptr /* mqc_hip_scf_run_batch_restart: starting densities ... */,
-                     const std::vector<double*>* spin_in = nullptr /* ... and the spin densities' destinations */)
+static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_options_t& opts, int lane)
 {
+    const Topology& topo = *w.topo;
+    const Topology* aux = w.aux.get();
     const bool second = lane == 1;
     hipStream_t const lane_stream = second ? ctx->stream2 : ctx->stream;
     const double t_begin = now_s();
-    const int ntot = (int)xyz_in.size();
-    Batch b{topo, aux, opts, atomic_guess};
+    const int ntot = (int)w.xyz.size();
+    Batch b{topo, aux, opts, w.guess.get()};
     BatchPlan plan;
     // external point charges (FMO / EE-MBE embedding) and h_extra: the same in every fragment of the group (its key says so)
-    plan.npc = ntot > 0 ? mols_in[0]->n_point_charges : 0;
-    plan.hx = ntot > 0 && mols_in[0]->h_extra != nullptr;
+    plan.npc = ntot > 0 ? w.mol[0]->n_point_charges : 0;
+    plan.hx = ntot > 0 && w.mol[0]->h_extra != nullptr;
     const bool embedded = plan.npc > 0 || plan.hx;
     {
         // Order the batch by compactness (nuclear repulsion, most compact first).  Lanes of a wave are
         // consecutive fragments: with similar geometries side by side, the primitive-pair screening and
         // the Schwarz ballot drop the same work in every lane, so whole waves skip it.
         std::vector<std::pair<double, int>> key(ntot);
-        for (int i = 0; i < ntot; ++i) key[i] = {-nuclear_repulsion(topo, xyz_in[i]), i};
+        for (int i = 0; i < ntot; ++i) key[i] = {-nuclear_repulsion(topo, w.xyz[i]), i};
         std::stable_sort(key.begin(), key.end());
         for (auto& k : key) {
-            b.xyz.push_back(xyz_in[k.second]); b.results.push_back(results_in[k.second]);
-            if (embedded) b.mols.push_back(mols_in[k.second]);
-            if (pcgrad_in) b.pcgrad.push_back((*pcgrad_in)[k.second]);      // the same permutation as the results
-            if (d0_in) b.d0.push_back((*d0_in)[k.second]);
-            if (spin_in) b.spin_out.push_back((*spin_in)[k.second]);
+            b.xyz.push_back(w.xyz[k.second]); b.results.push_back(w.res[k.second]);
+            if (embedded) b.mols.push_back(w.mol[k.second]);
+            if (!w.pcg.empty()) b.pcgrad.push_back(w.pcg[k.second]);      // the same permutation as the results
+            if (!w.d0.empty()) b.d0.push_back(w.d0[k.second]);
+            if (!w.spin.empty()) b.spin_out.push_back(w.spin[k.second]);
         }
     }
     std::string msg;
     int rc = plan_batch(opts, topo, ntot, plan, msg);
     if (rc == MQC_HIP_OK && embedded && opts.want_gradient) {
-        if (!pcgrad_in) {
+        if (w.pcg.empty()) {
             msg = "analytic gradients of a fragment embedded in point charges or an extra one-electron operator are not returned by this entry "
                   "(the result record has no slot for the charges' own gradient): point charges go through mqc_hip_scf_gradient_embedded_batch";
             rc = MQC_HIP_ERR_UNSUPPORTED;
@@ -1329,13 +1294,17 @@ static void init_result(mqc_hip_scf_result_t* r)
     r->scf_status = MQC_HIP_SCF_NOT_RUN;
 }
 
-// the body of the batch entries; site_gradients != nullptr or embedded_entry: mqc_hip_scf_gradient_embedded_batch;
-// initial_density / spin_densities_out (either may be NULL): mqc_hip_scf_run_batch_restart
+struct BatchExtras {            // what the plain batch entry does not have
+    bool embedded_entry = false;
+    double* const* site_gradients = nullptr;        // mqc_hip_scf_gradient_embedded_batch
+    const double* const* initial_density = nullptr; // mqc_hip_scf_run_batch_restart (either may be NULL)
+    double* const* spin_densities_out = nullptr;
+};
+
+// the body of the batch entries
 static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,
                               const mqc_hip_basis_t* orbitals, const mqc_hip_basis_t* auxes,
-                              const mqc_hip_scf_options_t* opts, mqc_hip_scf_result_t* results, bool embedded_entry,
-                              double* const* site_gradients, const double* const* initial_density = nullptr,
-                              double* const* spin_densities_out = nullptr)
+                              const mqc_hip_scf_options_t* opts, mqc_hip_scf_result_t* results, const BatchExtras& extras)
 {
     if (!ctx) return fail(MQC_HIP_ERR_VALIDATION, "null context (call mqc_hip_context_get first)");
     if (nfrag < 0 || (nfrag > 0 && (!mols || !orbitals || !opts || !results)))
@@ -1374,19 +1343,6 @@ static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip
     // ---- per topology group: topology from the cache (or built now), then the batch.  With several groups
     // (monomers and dimers of an MBE list) two run at a time, each on its own slot: the small group's
     // latency-bound stages hide behind the large one.
-    struct Work {
-        const std::vector<int64_t>* idx;
-        std::shared_ptr<Topology> topo, aux;
-        std::vector<const double*> xyz;
-        std::vector<const mqc_hip_molecule_t*> mol;
-        std::vector<mqc_hip_scf_result_t*> res;
-        std::vector<double*> pcg;
-        std::vector<const double*> d0;
-        std::vector<double*> spin;
-        std::shared_ptr<AtomicGuess> guess;
-        int rc = MQC_HIP_OK;
-        std::string msg;
-    };
     std::vector<Work> work;
     auto cached_topology = [&](const std::string& key, const mqc_hip_molecule_t& mol, const mqc_hip_basis_t& bas, int max_l,
                                bool quartets, std::shared_ptr<Topology>& out, std::string& err) -> int {
@@ -1426,12 +1382,12 @@ static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip
         // supplied densities: their size follows from the run's spin treatment; one with a non-finite entry fails its own
         // fragment and nothing else
         std::vector<int64_t> run_idx;
-        bool any_d0 = false, all_d0 = initial_density != nullptr;
+        bool any_d0 = false, all_d0 = extras.initial_density != nullptr;
         {
             const size_t nn = (size_t)w.topo->nao * w.topo->nao;
             const size_t cnt = runs_unrestricted(*opts, w.topo->multiplicity, w.topo->nelec) ? 2 * nn : nn;
             for (auto i : idx) {
-                const double* d = initial_density ? initial_density[i] : nullptr;
+                const double* d = extras.initial_density ? extras.initial_density[i] : nullptr;
                 bool finite = true;
                 if (d) for (size_t k = 0; k < cnt && finite; ++k) finite = std::isfinite(d[k]);
                 if (!finite) {
@@ -1457,16 +1413,15 @@ static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip
         }
         for (auto i : run_idx) {
             w.xyz.push_back(mols[i].xyz); w.mol.push_back(&mols[i]); w.res.push_back(&results[i]);
-            if (embedded_entry) w.pcg.push_back(site_gradients ? site_gradients[i] : nullptr);
-            if (any_d0) w.d0.push_back(initial_density[i]);
-            if (spin_densities_out) w.spin.push_back(spin_densities_out[i]);
+            if (extras.embedded_entry) w.pcg.push_back(extras.site_gradients ? extras.site_gradients[i] : nullptr);
+            if (any_d0) w.d0.push_back(extras.initial_density[i]);
+            if (extras.spin_densities_out) w.spin.push_back(extras.spin_densities_out[i]);
         }
         work.push_back(std::move(w));
     }
     auto run_one = [&](Work& w, int lane) {
         (void)hipSetDevice(ctx->device);
-        w.rc = run_batch(ctx, *w.topo, w.aux.get(), w.xyz, *opts, w.res, lane, w.guess.get(), w.mol, embedded_entry ? &w.pcg : nullptr,
-                         w.d0.empty() ? nullptr : &w.d0, w.spin.empty() ? nullptr : &w.spin);
+        w.rc = run_batch(ctx, w, *opts, lane);
         if (w.rc != MQC_HIP_OK) w.msg = mqc_hip_last_error();      // the error text is thread-local
     };
     if (work.size() >= 2 && ctx->concurrent_groups) {
@@ -1502,7 +1457,7 @@ int mqc_hip_scf_run_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_mol
                           const mqc_hip_basis_t* orbitals, const mqc_hip_basis_t* auxes,
                           const mqc_hip_scf_options_t* opts, mqc_hip_scf_result_t* results)
 {
-    return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, opts, results, false, nullptr);
+    return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, opts, results, BatchExtras());
 }
 
 int mqc_hip_scf_run_batch_restart(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,
@@ -1510,7 +1465,10 @@ int mqc_hip_scf_run_batch_restart(mqc_hip_context* ctx, int64_t nfrag, const mqc
                                   const mqc_hip_scf_options_t* opts, mqc_hip_scf_result_t* results,
                                   const double* const* initial_density, double* const* spin_densities_out)
 {
-    return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, opts, results, false, nullptr, initial_density, spin_densities_out);
+    BatchExtras extras;
+    extras.initial_density = initial_density;
+    extras.spin_densities_out = spin_densities_out;
+    return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, opts, results, extras);
 }
 
 int mqc_hip_scf_gradient_embedded_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,
@@ -1525,459 +1483,16 @@ int mqc_hip_scf_gradient_embedded_batch(mqc_hip_context* ctx, int64_t nfrag, con
                 return fail(MQC_HIP_ERR_VALIDATION, "point_charge_gradients is NULL but fragment " + std::to_string(i) + " carries point charges");
     mqc_hip_scf_options_t o = *opts;
     o.want_gradient = 1;
-    return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, &o, results, true, point_charge_gradients);
+    BatchExtras extras;
+    extras.embedded_entry = true;
+    extras.site_gradients = point_charge_gradients;
+    return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, &o, results, extras);
 }
 
 int mqc_hip_scf_run(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* orbital,
                     const mqc_hip_basis_t* aux, const mqc_hip_scf_options_t* opts, mqc_hip_scf_result_t* result)
 {
     return mqc_hip_scf_run_batch(ctx, 1, mol, orbital, aux, opts, result);
-}
-
-// ---- stage-level entry points -----------------------------------------------------------
-struct StageBatch {
-    Topology topo;
-    TopologyDev td;
-    BatchView bv{};
-};
-
-// the plan of a stage-level call: closed shell, no exchange-correlation, the tensor layout of a batch of ntot
-static BatchPlan stage_plan(const Topology& topo, int two_e, int ntot)
-{
-    BatchPlan p;
-    p.n = topo.nao; p.npair = topo.npair; p.natoms = topo.natoms;
-    p.two_e = two_e;
-    plan_layout(p, ntot, (int)topo.shells.size(), topo.lmax, false);
-    return p;
-}
-
-static int stage_setup(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, bool with_eri, StageBatch& sb,
-                       int two_e = -1)
-{
-    if (!ctx || !mol || !bas) return fail(MQC_HIP_ERR_VALIDATION, "null argument");
-    HIP_CHECK_RET(hipSetDevice(ctx->device));
-    std::string err;
-    int rc = build_topology(*mol, *bas, sb.topo, err);
-    if (rc != MQC_HIP_OK) return fail(rc, err);
-    if (with_eri && !incore_supported(sb.topo.nao)) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large for the in-core ERI path");
-    rc = upload_topology(ctx, sb.topo, sb.td);
-    if (rc != MQC_HIP_OK) return rc;
-    if (two_e < 0) two_e = with_eri ? TWO_E_INCORE : TWO_E_NONE;
-    rc = carve_slot(ctx, make_slot(ctx, 0, nullptr), stage_plan(sb.topo, two_e, 1), sb.td, 1, sb.bv);
-    if (rc != MQC_HIP_OK) return rc;
-    sb.bv.nocc = std::max(1, sb.topo.nelec / 2); sb.bv.exx = 1.0;
-    HIP_CHECK_RET(hipMemcpy(sb.bv.xyz, mol->xyz, sizeof(double) * 3 * mol->n_atoms, hipMemcpyHostToDevice));
-    HIP_CHECK_RET(hipMemset(sb.bv.istate, 0, sizeof(int) * 4));
-    return MQC_HIP_OK;
-}
-
-int mqc_hip_int1e(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, double* S, double* T, double* V)
-{
-    StageBatch sb;
-    int rc = stage_setup(ctx, mol, bas, false, sb);
-    if (rc != MQC_HIP_OK) return rc;
-    launch_int1e(sb.bv, sb.topo, ctx->stream);
-    HIP_CHECK_RET(hipStreamSynchronize(ctx->stream));
-    HIP_CHECK_RET(hipGetLastError());
-    const size_t nn = (size_t)sb.topo.nao * sb.topo.nao;
-    if (S) HIP_CHECK_RET(hipMemcpy(S, sb.bv.S, sizeof(double) * nn, hipMemcpyDeviceToHost));
-    if (T) HIP_CHECK_RET(hipMemcpy(T, sb.bv.W, sizeof(double) * nn, hipMemcpyDeviceToHost));
-    if (V) HIP_CHECK_RET(hipMemcpy(V, sb.bv.W + nn, sizeof(double) * nn, hipMemcpyDeviceToHost));
-    return MQC_HIP_OK;
-}
-
-// the packed tensor of one fragment: 1/r12 (omega = 0) or erf(omega r12)/r12
-static int stage_eri_packed(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, double omega,
-                            double schwarz_tol, double* M)
-{
-    StageBatch sb;
-    int rc = stage_setup(ctx, mol, bas, true, sb);
-    if (rc != MQC_HIP_OK) return rc;
-    // stage-level check of the tensor: poison it first, so that an element no class list covers shows up as NaN
-    HIP_CHECK_RET(hipMemsetAsync(sb.bv.eri, 0xFF, sizeof(double) * (size_t)sb.topo.npair * sb.topo.npair, ctx->stream));
-    launch_eri(sb.bv, sb.topo, schwarz_tol, ctx->stream, nullptr, omega);
-    HIP_CHECK_RET(hipStreamSynchronize(ctx->stream));
-    HIP_CHECK_RET(hipGetLastError());
-    const size_t np = (size_t)sb.topo.npair;
-    HIP_CHECK_RET(hipMemcpy(M, sb.bv.eri, sizeof(double) * np * np, hipMemcpyDeviceToHost));
-    return MQC_HIP_OK;
-}
-
-int mqc_hip_eri_packed(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, double schwarz_tol, double* M)
-{
-    return stage_eri_packed(ctx, mol, bas, 0.0, schwarz_tol, M);
-}
-
-int mqc_hip_eri_packed_attenuated(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, double omega,
-                                  double schwarz_tol, double* M)
-{
-    if (!(omega > 0.0) || !std::isfinite(omega)) return fail(MQC_HIP_ERR_VALIDATION, "attenuated ERIs: omega must be positive and finite");
-    return stage_eri_packed(ctx, mol, bas, omega, schwarz_tol, M);
-}
-
-int mqc_hip_jk_incore(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, const double* D, double* J, double* K)
-{
-    StageBatch sb;
-    int rc = stage_setup(ctx, mol, bas, true, sb);
-    if (rc != MQC_HIP_OK) return rc;
-    const size_t nn = (size_t)sb.topo.nao * sb.topo.nao;
-    launch_eri(sb.bv, sb.topo, 0.0, ctx->stream);
-    HIP_CHECK_RET(hipMemcpyAsync(sb.bv.D, D, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));
-    launch_jk_incore(sb.bv, false, ctx->stream);
-    HIP_CHECK_RET(hipStreamSynchronize(ctx->stream));
-    HIP_CHECK_RET(hipGetLastError());
-    HIP_CHECK_RET(hipMemcpy(J, sb.bv.J, sizeof(double) * nn, hipMemcpyDeviceToHost));
-    HIP_CHECK_RET(hipMemcpy(K, sb.bv.K, sizeof(double) * nn, hipMemcpyDeviceToHost));
-    return MQC_HIP_OK;
-}
-
-// J and K of one fragment by the direct build: no tensor, the digest kernels over every unique quartet
-int mqc_hip_jk_direct(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, double schwarz_tol, double exx,
-                      const double* D, double* J, double* K)
-{
-    if (!D || !J || !K) return fail(MQC_HIP_ERR_VALIDATION, "null argument");
-    if (!(schwarz_tol >= 0.0) || !(exx >= 0.0) || !std::isfinite(schwarz_tol) || !std::isfinite(exx))
-        return fail(MQC_HIP_ERR_VALIDATION, "direct J/K: schwarz_tol and exx must be finite and not negative");
-    StageBatch sb;
-    int rc = stage_setup(ctx, mol, bas, false, sb, TWO_E_DIRECT);
-    if (rc != MQC_HIP_OK) return rc;
-    if (sb.topo.nao > 256) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large (n_ao <= 256)");
-    const size_t nn = (size_t)sb.topo.nao * sb.topo.nao;
-    sb.bv.exx = exx;
-    HIP_CHECK_RET(hipMemsetAsync(sb.bv.eri_count, 0, sizeof(unsigned long long), ctx->stream));
-    HIP_CHECK_RET(hipMemcpyAsync(sb.bv.D, D, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));
-    launch_direct_setup(sb.bv, sb.topo, ctx->stream);
-    launch_jk_direct(sb.bv, sb.topo, schwarz_tol, false, ctx->stream);
-    HIP_CHECK_RET(hipStreamSynchronize(ctx->stream));
-    HIP_CHECK_RET(hipGetLastError());
-    HIP_CHECK_RET(hipMemcpy(J, sb.bv.J, sizeof(double) * nn, hipMemcpyDeviceToHost));
-    HIP_CHECK_RET(hipMemcpy(K, sb.bv.K, sizeof(double) * nn, hipMemcpyDeviceToHost));
-    return MQC_HIP_OK;
-}
-
-int mqc_hip_coulomb_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols, const mqc_hip_basis_t* bas,
-                          int32_t n_source_atoms, const double* D, double* J)
-{
-    if (!ctx || nfrag < 0 || (nfrag > 0 && (!mols || !bas || !D || !J))) return fail(MQC_HIP_ERR_VALIDATION, "null argument");
-    if (nfrag == 0) return MQC_HIP_OK;
-    HIP_CHECK_RET(hipSetDevice(ctx->device));
-    for (int64_t i = 0; i < nfrag; ++i) {
-        if (!mols[i].atomic_numbers || !mols[i].xyz || mols[i].n_atoms != mols[0].n_atoms ||
-            std::memcmp(mols[i].atomic_numbers, mols[0].atomic_numbers, sizeof(int32_t) * mols[0].n_atoms) != 0 || mols[i].ghost != mols[0].ghost)
-            return fail(MQC_HIP_ERR_VALIDATION, "coulomb batch: every fragment must have the elements of the first (one topology per call)");
-    }
-    Topology topo;
-    std::string err;
-    int rc = build_topology(mols[0], *bas, topo, err);
-    if (rc != MQC_HIP_OK) return fail(rc, err);
-    if (n_source_atoms < 0 || n_source_atoms >= topo.natoms) return fail(MQC_HIP_ERR_VALIDATION, "coulomb batch: n_source_atoms must be within 0 .. n_atoms - 1");
-    const bool cross = n_source_atoms > 0;
-    if (cross) {
-        // keep the quartets that join a pair on the leading atoms with a pair on the source atoms (either side may be
-        // the bra: the class fixes the order); twin entries are dropped with the rest, the plain lists cover everything
-        const int first_src = topo.natoms - n_source_atoms;
-        auto on_src = [&](int sh) { return topo.shells[sh].atom >= first_src; };
-        for (auto& cl : topo.classes) {
-            std::vector<int> q, sets;
-            for (size_t e = 0; 4 * e + 3 < cl.quartets.size(); ++e) {
-                const int* s4 = &cl.quartets[4 * e];
-                const bool bra_src = on_src(s4[0]) && on_src(s4[1]), bra_lead = !on_src(s4[0]) && !on_src(s4[1]);
-                const bool ket_src = on_src(s4[2]) && on_src(s4[3]), ket_lead = !on_src(s4[2]) && !on_src(s4[3]);
-                if (!((bra_src && ket_lead) || (bra_lead && ket_src))) continue;
-                q.insert(q.end(), s4, s4 + 4);
-                if (e < cl.set_quartets.size()) sets.push_back(cl.set_quartets[e]);
-            }
-            cl.quartets.swap(q); cl.set_quartets.swap(sets);
-            cl.twin_entries.clear(); cl.rest.clear(); cl.set_twin.clear(); cl.set_rest.clear();
-        }
-        topo.key += "|cross" + std::to_string(n_source_atoms);
-    }
-    TopologyDev td;
-    rc = upload_topology(ctx, topo, td);
-    if (rc != MQC_HIP_OK) return rc;
-    const int n = topo.nao;
-    const size_t nn = (size_t)n * n;
-    // full mode: in-core (the packed tensor of every fragment of a chunk resident at once, chunks sized to the free HBM).
-    // cross mode: the direct digest over the filtered lists -- no tensor at all, the few (leading | source) quartets
-    // are contracted with the density as they are formed (Schwarz screening at 1e-12)
-    static const bool cross_incore = [] { const char* e = std::getenv("MQC_HIP_COULOMB_CROSS_INCORE"); return e && e[0] == '1'; }();
-    const bool direct = cross && !cross_incore;
-    if (!direct && !incore_supported(topo.nao)) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large for the in-core ERI path");
-    if (topo.nao > 256) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large (n_ao <= 256)");
-    const BatchPlan plan = stage_plan(topo, direct ? TWO_E_DIRECT : TWO_E_INCORE, (int)std::min<int64_t>(nfrag, 1 << 30));
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    free_b += ctx->pool_main.capacity() + ctx->pool_eri.capacity();
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nfrag, 16384), (int64_t)((double)free_b * 0.7 / (double)fragment_bytes(plan))));
-    const Slot sl0 = make_slot(ctx, 0, nullptr);
-    std::vector<double> hx;
-    for (int64_t start = 0; start < nfrag; start += chunk) {
-        const int nf = (int)std::min<int64_t>(chunk, nfrag - start);
-        BatchView bv{};
-        rc = carve_slot(ctx, sl0, plan, td, nf, bv);
-        if (rc != MQC_HIP_OK) return rc;
-        // only J is read back: the direct digest skips its exchange updates when exx = 0; the in-core kernels
-        // form K alongside J in the same pass over the tensor either way
-        bv.nocc = std::max(1, topo.nelec / 2); bv.exx = direct ? 0.0 : 1.0;
-        hx.resize((size_t)nf * topo.natoms * 3);
-        for (int f = 0; f < nf; ++f) std::memcpy(&hx[(size_t)f * topo.natoms * 3], mols[start + f].xyz, sizeof(double) * topo.natoms * 3);
-        HIP_CHECK_RET(hipMemcpyAsync(bv.xyz, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_CHECK_RET(hipMemsetAsync(bv.istate, 0, sizeof(int) * (size_t)nf * 4, ctx->stream));
-        HIP_CHECK_RET(hipMemsetAsync(bv.eri_count, 0, sizeof(unsigned long long), ctx->stream));
-        HIP_CHECK_RET(hipMemcpyAsync(bv.D, D + (size_t)start * nn, sizeof(double) * nn * nf, hipMemcpyHostToDevice, ctx->stream));
-        if (direct) {
-            launch_direct_setup(bv, topo, ctx->stream);
-            launch_jk_direct(bv, topo, 1.0e-12, false, ctx->stream);
-        } else {
-            // a restricted list leaves most of the tensor untouched: those blocks must read as zero
-            if (cross) HIP_CHECK_RET(hipMemsetAsync(bv.eri, 0, sizeof(double) * (size_t)nf * bv.eri_stride, ctx->stream));
-            launch_eri(bv, topo, 0.0, ctx->stream, hx.data());
-            launch_jk_incore(bv, false, ctx->stream);
-        }
-        HIP_CHECK_RET(hipStreamSynchronize(ctx->stream));
-        HIP_CHECK_RET(hipGetLastError());
-        HIP_CHECK_RET(hipMemcpy(J + (size_t)start * nn, bv.J, sizeof(double) * nn * nf, hipMemcpyDeviceToHost));
-    }
-    return MQC_HIP_OK;
-}
-
-// V(r) = sum_A Z_A/|r - R_A| - tr(D u_r) at the points of every fragment (kern_esp.hip).  Validation first (nothing is
-// written on a refusal), then chunks of fragments sized to the free HBM: geometry, densities and points up, the
-// primitive-pair records formed on the device, the point kernels, the potentials back.
-int mqc_hip_esp_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols, const mqc_hip_basis_t* bas, const double* D,
-                      int32_t max_points, const int32_t* n_points, const double* points, int32_t include_nuclei, double* esp)
-{
-    if (!ctx || nfrag < 0 || max_points < 0) return fail(MQC_HIP_ERR_VALIDATION, "esp batch: null context or negative count");
-    if (n_points)
-        for (int64_t i = 0; i < nfrag; ++i)
-            if (n_points[i] < 0 || n_points[i] > max_points)
-                return fail(MQC_HIP_ERR_VALIDATION, "esp batch: n_points[" + std::to_string(i) + "] = " + std::to_string(n_points[i]) +
-                                                        " is outside 0 .. max_points");
-    if (nfrag == 0 || max_points == 0) return MQC_HIP_OK;
-    if (!mols || !bas || !D || !points || !esp) return fail(MQC_HIP_ERR_VALIDATION, "null argument");
-    HIP_CHECK_RET(hipSetDevice(ctx->device));
-    const int na = mols[0].n_atoms;
-    for (int64_t i = 0; i < nfrag; ++i) {
-        if (!mols[i].atomic_numbers || !mols[i].xyz || mols[i].n_atoms != na ||
-            std::memcmp(mols[i].atomic_numbers, mols[0].atomic_numbers, sizeof(int32_t) * na) != 0 || mols[i].ghost != mols[0].ghost)
-            return fail(MQC_HIP_ERR_VALIDATION, "esp batch: every fragment must have the elements of the first (one topology per call)");
-        for (int k = 0; k < 3 * na; ++k)
-            if (!std::isfinite(mols[i].xyz[k])) return fail(MQC_HIP_ERR_VALIDATION, "esp batch: non-finite atomic coordinate in fragment " + std::to_string(i));
-    }
-    Topology topo;
-    std::string err;
-    int rc = build_topology(mols[0], *bas, topo, err, KERNEL_LMAX, false);
-    if (rc != MQC_HIP_OK) return fail(rc, err);
-    if (topo.nao > 256) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large (n_ao <= 256)");
-    const size_t mp = (size_t)max_points;
-    for (int64_t i = 0; i < nfrag; ++i) {
-        const int np = n_points ? n_points[i] : max_points;
-        const double* p = points + (size_t)i * 3 * mp;
-        for (int k = 0; k < 3 * np; ++k)
-            if (!std::isfinite(p[k])) return fail(MQC_HIP_ERR_VALIDATION, "esp batch: non-finite coordinate of point " + std::to_string(k / 3) + " of fragment " + std::to_string(i));
-        if (!include_nuclei) continue;
-        for (int a = 0; a < na; ++a) {
-            if (topo.zeff[a] == 0.0) continue;
-            const double* r = mols[i].xyz + 3 * a;
-            for (int k = 0; k < np; ++k) {
-                const double dx = p[3 * k] - r[0], dy = p[3 * k + 1] - r[1], dz = p[3 * k + 2] - r[2];
-                if (dx * dx + dy * dy + dz * dz < 1.0e-20)
-                    return fail(MQC_HIP_ERR_VALIDATION, "esp batch: point " + std::to_string(k) + " of fragment " + std::to_string(i) +
-                                                            " lies on nucleus " + std::to_string(a) + " (the nuclear potential diverges; include_nuclei = 0 gives the electronic part)");
-            }
-        }
-    }
-    TopologyDev td;
-    rc = upload_topology(ctx, topo, td);
-    if (rc != MQC_HIP_OK) return rc;
-    const size_t nn = (size_t)topo.nao * topo.nao, rec = esp_record_doubles(topo);
-    auto up = [](size_t doubles) { return (doubles + 31) & ~size_t(31); };     // every array starts on 256 bytes
-    const size_t per_frag = sizeof(double) * (up(3 * (size_t)na) + nn + rec + up(3 * mp) + up(mp) + 32) + 64;
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    free_b += g_esp_pool.capacity();
-    // MQC_HIP_ESP_CHUNK: a smaller cap on the fragments of one chunk (memory-tight hosts; the tests cross a chunk boundary with it)
-    int64_t cap = 16384;
-    if (const char* e = std::getenv("MQC_HIP_ESP_CHUNK")) cap = std::max(1, std::min(16384, std::atoi(e)));
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nfrag, cap), (int64_t)((double)free_b * 0.7 / (double)per_frag)));
-    std::vector<double> hx, hout;
-    std::vector<int> hn;
-    for (int64_t start = 0; start < nfrag; start += chunk) {
-        const int nf = (int)std::min<int64_t>(chunk, nfrag - start);
-        const size_t n_xyz = up((size_t)nf * 3 * na), n_D = up((size_t)nf * nn), n_rec = (size_t)nf * rec, n_pts = up((size_t)nf * 3 * mp),
-                     n_out = up((size_t)nf * mp);
-        double* base = (double*)g_esp_pool.ensure(sizeof(double) * (n_xyz + n_D + n_rec + n_pts + n_out) + sizeof(int) * ((size_t)nf + 64));
-        if (!base) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (esp batch)");
-        double *d_xyz = base, *d_D = d_xyz + n_xyz, *d_rec = d_D + n_D, *d_pts = d_rec + n_rec, *d_out = d_pts + n_pts;
-        int* d_np = (int*)(d_out + n_out);
-        hx.resize((size_t)nf * 3 * na); hn.resize(nf);
-        for (int f = 0; f < nf; ++f) {
-            std::memcpy(&hx[(size_t)f * 3 * na], mols[start + f].xyz, sizeof(double) * 3 * na);
-            hn[f] = n_points ? n_points[start + f] : max_points;
-        }
-        HIP_CHECK_RET(hipMemcpyAsync(d_xyz, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_CHECK_RET(hipMemcpyAsync(d_np, hn.data(), sizeof(int) * hn.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_CHECK_RET(hipMemcpyAsync(d_D, D + (size_t)start * nn, sizeof(double) * nn * nf, hipMemcpyHostToDevice, ctx->stream));
-        // a fragment's points beyond its count are not touched on the host: each fragment's live part goes up on its own
-        const bool full = std::all_of(hn.begin(), hn.end(), [&](int v) { return v == max_points; });
-        if (full) HIP_CHECK_RET(hipMemcpyAsync(d_pts, points + (size_t)start * 3 * mp, sizeof(double) * 3 * mp * nf, hipMemcpyHostToDevice, ctx->stream));
-        for (int f = 0; f < nf && !full; ++f)
-            if (hn[f] > 0)
-                HIP_CHECK_RET(hipMemcpyAsync(d_pts + (size_t)f * 3 * mp, points + (size_t)(start + f) * 3 * mp, sizeof(double) * 3 * hn[f],
-                                             hipMemcpyHostToDevice, ctx->stream));
-        launch_esp(td, topo, ctx->d_boys, ctx->d_c2s, nf, d_xyz, d_D, d_rec, d_pts, d_np, max_points, include_nuclei ? 1 : 0, d_out, ctx->stream);
-        HIP_CHECK_RET(hipStreamSynchronize(ctx->stream));
-        HIP_CHECK_RET(hipGetLastError());
-        hout.resize((size_t)nf * mp);
-        HIP_CHECK_RET(hipMemcpy(hout.data(), d_out, sizeof(double) * hout.size(), hipMemcpyDeviceToHost));
-        for (int f = 0; f < nf; ++f) std::memcpy(esp + (size_t)(start + f) * mp, &hout[(size_t)f * mp], sizeof(double) * hn[f]);
-    }
-    return MQC_HIP_OK;
-}
-
-// The quadrature stage of an SCF iteration on given densities (include/mqc_hip.h).  Nothing here is private to the
-// call: plan_batch and plan_layout decide what an SCF batch of nfrag fragments with this functional would get, carve_slot
-// lays the chunk out, and the grid, the weights, the radial cache and launch_xc are the driver's own (prepare, scf_loop).
-int mqc_hip_xc_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols, const mqc_hip_basis_t* bas, const char* functional,
-                     int32_t grid_level, int32_t unrestricted, const double* D, double* e_xc, double* n_electrons, double* V_xc)
-{
-    if (!ctx || !mols || !bas || !functional || !D || !e_xc || !n_electrons || !V_xc) return fail(MQC_HIP_ERR_VALIDATION, "xc batch: null argument");
-    if (nfrag < 1) return fail(MQC_HIP_ERR_VALIDATION, "xc batch: n_fragments must be at least 1");
-    HIP_CHECK_RET(hipSetDevice(ctx->device));
-    for (int64_t i = 0; i < nfrag; ++i) {
-        if (!mols[i].atomic_numbers || !mols[i].xyz || mols[i].n_atoms <= 0 || mols[i].n_atoms != mols[0].n_atoms ||
-            std::memcmp(mols[i].atomic_numbers, mols[0].atomic_numbers, sizeof(int32_t) * mols[0].n_atoms) != 0 || mols[i].ghost != mols[0].ghost)
-            return fail(MQC_HIP_ERR_VALIDATION, "xc batch: every fragment must have the elements of the first (one topology per call)");
-    }
-    mqc_hip_scf_options_t opts;
-    mqc_hip_default_options(&opts);
-    if (std::strlen(functional) >= sizeof(opts.functional)) return fail(MQC_HIP_ERR_UNSUPPORTED, "xc batch: functional name too long");
-    std::snprintf(opts.functional, sizeof(opts.functional), "%s", functional);
-    opts.grid_level = grid_level;
-    opts.unrestricted = unrestricted ? 1 : 0;
-    Topology topo;
-    std::string msg;
-    int rc = build_topology(mols[0], *bas, topo, msg, KERNEL_LMAX, false);
-    if (rc != MQC_HIP_OK) return fail(rc, msg);
-    const int ntot = (int)std::min<int64_t>(nfrag, 1 << 30);
-    BatchPlan plan;
-    if ((rc = plan_batch(opts, topo, ntot, plan, msg)) != MQC_HIP_OK) return fail(rc, msg);
-    if (plan.xc.ncomp == 0) return fail(MQC_HIP_ERR_VALIDATION, "xc batch: the functional has no grid part (Hartree-Fock)");
-    if (plan.uhf && !unrestricted) return fail(MQC_HIP_ERR_VALIDATION, "xc batch: an open-shell fragment takes spin densities (unrestricted != 0)");
-    Batch b{topo, nullptr, opts, nullptr};
-    if ((rc = upload_topology(ctx, topo, b.td)) != MQC_HIP_OK) return rc;
-    if ((rc = upload_grid(ctx, b, ctx->pool_grid, ctx->stream)) != MQC_HIP_OK) return rc;
-    plan.npts = b.grid.npts;
-    plan_layout(plan, ntot, (int)topo.shells.size(), topo.lmax, xc_radial_cache_on());
-
-    const int n = topo.nao, nspin = plan.uhf ? 2 : 1;
-    const size_t nn = (size_t)n * n;
-    constexpr size_t GUARD = 4096;         // bytes compared on either side of the accumulator
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    free_b += ctx->pool_main.capacity() + ctx->pool_eri.capacity() + ctx->pool_gridw.capacity();
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nfrag, 16384), (int64_t)((double)free_b * 0.7 / (double)fragment_bytes(plan))));
-    const Slot sl0 = make_slot(ctx, 0, nullptr);
-    hipStream_t s = ctx->stream;
-    std::vector<double> hx, acc, scal;
-    std::vector<unsigned char> before(2 * GUARD), after(2 * GUARD);
-    for (int64_t start = 0; start < nfrag; start += chunk) {
-        const int nf = (int)std::min<int64_t>(chunk, nfrag - start);
-        {
-            // room behind the last array of the quadrature's pool, so that the guard band exists where nothing follows V_xc
-            BatchView probe{};
-            const ChunkBytes need = carve_chunk(plan, nf, nullptr, probe);
-            if (!sl0.pool[POOL_GRIDW]->ensure(need.pool[POOL_GRIDW] + GUARD + 256)) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (grid weights)");
-        }
-        BatchView bv{};
-        bv.nalpha = plan.nalpha; bv.nbeta = plan.nbeta; bv.nocc = plan.nocc;
-        bv.exx = plan.rsh ? 1.0 : plan.xc.exx; bv.e_tol = opts.energy_tol; bv.d_tol = opts.density_tol;
-        bv.max_iter = opts.max_iter; bv.diis_size = opts.diis_size;
-        bv.xc = plan.xc; bv.grid = b.grid;
-        if ((rc = carve_slot(ctx, sl0, plan, b.td, nf, bv)) != MQC_HIP_OK) return rc;
-        hx.resize((size_t)nf * topo.natoms * 3);
-        for (int f = 0; f < nf; ++f) std::memcpy(&hx[(size_t)f * topo.natoms * 3], mols[start + f].xyz, sizeof(double) * topo.natoms * 3);
-        HIP_CHECK_RET(hipMemcpyAsync(bv.xyz, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, s));
-        HIP_CHECK_RET(hipMemsetAsync(bv.istate, 0, sizeof(int) * (size_t)nf * 4, s));
-        if (plan.uhf) {
-            for (int f = 0; f < nf; ++f) {
-                const double* d = D + (size_t)(start + f) * 2 * nn;
-                HIP_CHECK_RET(hipMemcpyAsync(bv.D + (size_t)f * nn, d, sizeof(double) * nn, hipMemcpyHostToDevice, s));
-                HIP_CHECK_RET(hipMemcpyAsync(bv.Db + (size_t)f * nn, d + nn, sizeof(double) * nn, hipMemcpyHostToDevice, s));
-            }
-        } else HIP_CHECK_RET(hipMemcpyAsync(bv.D, D + (size_t)start * nn, sizeof(double) * nn * nf, hipMemcpyHostToDevice, s));
-        launch_becke_weights(bv, s);
-        if (bv.grid.rad) launch_xc_radial_cache(bv, s);
-        if ((rc = stage_check("grid weights")) != MQC_HIP_OK) return rc;
-        // Poison.  launch_xc zeroes the accumulator itself, so a tile no workgroup owns reads as zero, not NaN, and the
-        // comparison with the reference finds it; what the poison of the array cannot show is a write OUTSIDE it.  The
-        // bytes on either side -- the end of the Becke weights in front, the radial cache behind or (where the plan has
-        // none) poisoned spare room of the pool -- do not change in a quadrature launch: they are compared across it.
-        const size_t vx_bytes = sizeof(double) * (size_t)nf * nn * nspin;
-        unsigned char* lo = (unsigned char*)bv.Vxc - GUARD;
-        unsigned char* hi = (unsigned char*)bv.Vxc + vx_bytes;
-        if ((unsigned char*)bv.grid.weights > lo) return fail(MQC_HIP_ERR_DEVICE, "xc batch: the grid is smaller than the guard band");
-        HIP_CHECK_RET(hipMemsetAsync(bv.Vxc, 0xFF, vx_bytes, s));
-        if (!bv.grid.rad) HIP_CHECK_RET(hipMemsetAsync(hi, 0xFF, GUARD, s));
-        HIP_CHECK_RET(hipMemcpyAsync(before.data(), lo, GUARD, hipMemcpyDeviceToHost, s));
-        HIP_CHECK_RET(hipMemcpyAsync(before.data() + GUARD, hi, GUARD, hipMemcpyDeviceToHost, s));
-        launch_xc(bv, false, s);
-        HIP_CHECK_RET(hipMemcpyAsync(after.data(), lo, GUARD, hipMemcpyDeviceToHost, s));
-        HIP_CHECK_RET(hipMemcpyAsync(after.data() + GUARD, hi, GUARD, hipMemcpyDeviceToHost, s));
-        acc.resize((size_t)nf * nn * nspin); scal.resize((size_t)nf * 8);
-        HIP_CHECK_RET(hipMemcpyAsync(acc.data(), bv.Vxc, vx_bytes, hipMemcpyDeviceToHost, s));
-        HIP_CHECK_RET(hipMemcpyAsync(scal.data(), bv.scal, sizeof(double) * scal.size(), hipMemcpyDeviceToHost, s));
-        HIP_CHECK_RET(hipStreamSynchronize(s));
-        if ((rc = stage_check("exchange-correlation quadrature")) != MQC_HIP_OK) return rc;
-        if (std::memcmp(before.data(), after.data(), 2 * GUARD) != 0)
-            return fail(MQC_HIP_ERR_DEVICE, "xc batch: the quadrature wrote outside the V_xc accumulator");
-        // V_xc = A + A^T (scf_step's Fock assembly); the beta accumulators follow the alpha ones of the whole chunk
-        for (int f = 0; f < nf; ++f) {
-            e_xc[start + f] = scal[8 * (size_t)f + 5];
-            n_electrons[start + f] = scal[8 * (size_t)f + 6];
-            for (int sp = 0; sp < nspin; ++sp) {
-                const double* a = acc.data() + ((size_t)sp * nf + f) * nn;
-                double* v = V_xc + ((size_t)(start + f) * nspin + sp) * nn;
-                for (int i = 0; i < n; ++i)
-                    for (int j = 0; j < n; ++j) v[(size_t)i * n + j] = a[(size_t)i * n + j] + a[(size_t)j * n + i];
-            }
-        }
-    }
-    return MQC_HIP_OK;
-}
-
-int mqc_hip_syev(mqc_hip_context* ctx, int32_t n, const double* A, double* w, double* V)
-{
-    if (!ctx || !A || !w || !V || n <= 0) return fail(MQC_HIP_ERR_VALIDATION, "bad arguments");
-    if (n > 256) return fail(MQC_HIP_ERR_UNSUPPORTED, "matrix too large for the Jacobi solver (n <= 256)");
-    HIP_CHECK_RET(hipSetDevice(ctx->device));
-    const size_t nn = (size_t)n * n;
-    double* d = (double*)ctx->pool_main.ensure(sizeof(double) * (2 * nn + n) + 1024);
-    if (!d) return fail(MQC_HIP_ERR_DEVICE, "out of device memory");
-    HIP_CHECK_RET(hipMemcpy(d, A, sizeof(double) * nn, hipMemcpyHostToDevice));
-    launch_syev(n, d, d + 2 * nn, d + nn, ctx->stream);
-    HIP_CHECK_RET(hipStreamSynchronize(ctx->stream));
-    HIP_CHECK_RET(hipGetLastError());
-    HIP_CHECK_RET(hipMemcpy(w, d + 2 * nn, sizeof(double) * n, hipMemcpyDeviceToHost));
-    HIP_CHECK_RET(hipMemcpy(V, d + nn, sizeof(double) * nn, hipMemcpyDeviceToHost));
-    return MQC_HIP_OK;
-}
-
-int mqc_hip_diis_coefficients(mqc_hip_context* ctx, int32_t n_stored, const double* overlap, double* coefficients, int32_t* ok)
-{
-    if (!ctx || !overlap || !coefficients || !ok) return fail(MQC_HIP_ERR_VALIDATION, "bad arguments");
-    if (n_stored < 1 || n_stored > DIIS_MAX) return fail(MQC_HIP_ERR_VALIDATION, "n_stored must be within 1..8");
-    HIP_CHECK_RET(hipSetDevice(ctx->device));
-    double* d = (double*)ctx->pool_misc.ensure(4096);
-    if (!d) return fail(MQC_HIP_ERR_DEVICE, "out of device memory");
-    HIP_CHECK_RET(hipMemcpy(d + 32, overlap, sizeof(double) * n_stored * n_stored, hipMemcpyHostToDevice));
-    launch_diis_coeff(n_stored, d + 32, d + 128, (int*)d, ctx->stream);
-    HIP_CHECK_RET(hipStreamSynchronize(ctx->stream));
-    HIP_CHECK_RET(hipMemcpy(coefficients, d + 128, sizeof(double) * n_stored, hipMemcpyDeviceToHost));
-    int okv = 0;
-    HIP_CHECK_RET(hipMemcpy(&okv, d, sizeof(int), hipMemcpyDeviceToHost));
-    *ok = okv;
-    return MQC_HIP_OK;
 }
 
 }  // extern "C"

@@ -344,6 +344,8 @@ void plan_layout(BatchPlan& p, int ntot, int nshell, int lmax, bool rad_cache);
 ChunkBytes carve_chunk(const BatchPlan& p, int nfrag, char* const* bases, BatchView& bv, std::vector<CarvedArray>* record = nullptr);
 // bytes per fragment that bound every chunk: carve_chunk(p, nf) <= nf x this (+ the direct path's own J/K accumulators)
 size_t fragment_bytes(const BatchPlan& p);
+// fragments per chunk of a batched stage entry: what fits 70 % of free_bytes, at most nfrag and cap, at least one
+int64_t stage_chunk_fragments(size_t free_bytes, size_t per_fragment_bytes, int64_t nfrag, int64_t cap = 16384);
 // host-side pieces (basis_norm.cpp, boys_table.cpp, batch.cpp)
 void set_error(const std::string& msg);
 int fail(int code, const std::string& msg);

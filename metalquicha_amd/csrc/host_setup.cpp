@@ -483,6 +483,11 @@ size_t fragment_bytes(const BatchPlan& p)
     return carve_chunk(p, 1, nullptr, probe).total() + (p.two_e == TWO_E_DIRECT ? sizeof(double) * 2 * (size_t)p.n * p.n : 0);
 }
 
+int64_t stage_chunk_fragments(size_t free_bytes, size_t per_fragment_bytes, int64_t nfrag, int64_t cap)
+{
+    return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nfrag, cap), (int64_t)((double)free_bytes * 0.7 / (double)per_fragment_bytes)));
+}
+
 double nuclear_repulsion(const Topology& topo, const double* xyz)
 {
     double e = 0.0;

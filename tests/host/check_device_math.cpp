@@ -257,6 +257,12 @@ int hostcheck_carve(const int* spec, int nfrag, unsigned long long* pool_bytes, 
     return 0;
 }
 
+// the chunk size of the batched stage entries (mqc_hip_coulomb_batch, _esp_batch, _xc_batch)
+long long hostcheck_stage_chunk(unsigned long long free_bytes, unsigned long long per_fragment, long long nfrag, long long cap)
+{
+    return stage_chunk_fragments((size_t)free_bytes, (size_t)per_fragment, nfrag, cap);
+}
+
 void hostcheck_boys(int L, double T, double* F)
 {
     ensure_tables();

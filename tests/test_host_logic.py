@@ -227,6 +227,22 @@ def test_every_chunk_takes_the_tensor_layout_of_its_batch(hostcheck):
     assert _carve(hostcheck, 64, DIMER_DZ, two_e="direct", ntot=120)[2:4] == (0, 0)
 
 
+@pytest.mark.parametrize("free,per,nfrag,cap,expected", [
+    (1000, 100, 50, 16384, 7), (0, 100, 50, 16384, 1), (1 << 40, 1 << 20, 3, 16384, 3), (1 << 50, 1 << 10, 20000, 16384, 16384),
+    (1 << 40, 1 << 20, 9, 2, 2), (int(288e9), None, 100000, 16384, None)])
+def test_stage_chunk_size_is_the_budget_formula(hostcheck, free, per, nfrag, cap, expected):
+    """The batched stage entries (coulomb, esp, xc) size their chunks with stage_chunk_fragments: what fits 70 % of the
+    free bytes, at most the batch and the cap, at least one fragment.  per = None: a cc-pVDZ water dimer's own
+    fragment_bytes on a 288 GB card."""
+    if per is None:
+        per = _carve(hostcheck, 1, DIMER_DZ)[1]
+    hostcheck.hostcheck_stage_chunk.restype = ctypes.c_longlong
+    got = hostcheck.hostcheck_stage_chunk(ctypes.c_ulonglong(free), ctypes.c_ulonglong(per), ctypes.c_longlong(nfrag), ctypes.c_longlong(cap))
+    want = max(1, min(nfrag, cap, int(free * 0.7 / per)))      # IEEE doubles on both sides: equality is exact
+    assert got == want
+    assert expected is None or got == expected
+
+
 # ---- MBE assembly ----------------------------------------------------------------------------
 def test_mbe_term_list_and_coefficients():
     system = mbe.water_cluster(2)
