@@ -214,7 +214,13 @@ struct EriListCache {
     int nap = 0;
 };
 constexpr int ERI_CACHE_WAYS = 4;
-constexpr int ERI_SIDE_MAX = 7;        // task-list launches of different classes are independent: round-robin.
+constexpr int ERI_SIDE_MAX = 7;
+// Batches with a share plan and at least this many fragments put the task launches and the copy of the shared blocks on one
+// stream (launch_eri).  Same box, builds alternating, ms per evaluation before -> after: 2016 dimers (the benchmark, five
+// runs each) 90.1-91.6 -> 87.0-89.1; one rank's share of a 4-way split (520 fragments) 27.5, 28.1 -> 29.4, 30.8; of an
+// 8-way split (260 fragments) 18.4, 18.7 -> 18.9, 18.7.  Below the full batch the task launches ARE the critical path and
+// want all the streams, so the switch sits between 520 and 2016.  MQC_HIP_ERI_TASK_STREAM_MIN overrides.
+constexpr int ERI_TASK_STREAM_MIN_FRAGMENTS = 1024;
 // Side streams in use: 3 with the HIP runtime's default of four hardware queues per process, 7 when the process runs
 // with GPU_MAX_HW_QUEUES >= 8 (more streams than hardware queues only serialise); MQC_HIP_ERI_STREAMS overrides.
 static int eri_side_streams()
@@ -582,43 +588,63 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
     EriListCache* cc = eri_lists(bv, topo, s, host_xyz);
     const int* d = (const int*)cc->pool.ensure(0);
 
-    // ---- launches: dense lists on the caller's stream; the task-list launches of shared entries (few, long
-    // threads: one wave per entry and distinct geometry) on a side stream so that they fill gaps instead of
-    // serialising; both join before the copy kernel
-    // The class launches are spread over the caller's stream and the side streams: small batches give every launch
-    // only a handful of long-running waves, and even a full batch has a tail per launch; with the launches placed
-    // longest-first their critical paths overlap instead of adding up.
+    // ---- launches.  The class launches are spread over the caller's stream and the side streams: small batches give
+    // every launch only a handful of long-running waves, and even a full batch has a tail per launch; with the launches
+    // placed longest-first their critical paths overlap instead of adding up.
     // (measured with the longest-first assignment below: 2016 dimers 127.3 -> 124 ms, 1008: 75.3 -> 70.8, 504: 55.0 ->
     // 49.5, so every batch is spread; MQC_HIP_ERI_SPREAD_MAX=n keeps batches above n fragments on one stream)
+    //
+    // Batches with a share plan: the task-list launches of the shared entries (few, long threads: one lane per entry
+    // and distinct geometry) ALL go on one side stream, heaviest first, with eri_broadcast_kernel right behind them on
+    // that stream; the dense launches go on the caller's stream and the other side streams only, so no dense launch
+    // ever waits behind a task launch and the copy runs next to the dense work instead of after the join.  The task
+    // stream is side[0].  The one-electron chain of the chunk sits on side[2] (see load[3] below), so the tasks and the
+    // chain share a stream only when MQC_HIP_ERI_STREAMS leaves a single side stream; with two or more, side[0] is the
+    // stream with the least summed cost (nothing but the tasks), and side[2] keeps its reservation for the dense
+    // placement.  What makes the overlap correct:
+    //   * the zero fill completes before ANY class launch starts: the caller's stream has joined the fill (join[] of
+    //     launch_eri_bounds, or the fill sits on the caller's stream itself) before the fork event below is recorded,
+    //     and every side stream waits for that event;
+    //   * a shared element is written only by a task launch (in the representative fragment) or by the copy (in the
+    //     others), never by a dense launch: an entry is dense exactly when plan.shared_row of its atom set is -1, and
+    //     pp_row sends an element to the copy exactly when the row of the same atom set is >= 0;
+    //   * the copy reads only shared elements of representatives, i.e. only what the task launches ahead of it on its
+    //     own stream wrote.
+    // A range-separated hybrid calls launch_eri twice (eri, then eri_lr): the caller's stream joins every side stream
+    // at the end of a call and the next call's fork event is recorded behind that join, so the second call's tasks and
+    // copy start after the whole first call and work on the second tensor only (the view is passed by value).
+    // MQC_HIP_ERI_TASK_STREAM_MIN=n: batches of fewer than n fragments keep the earlier placement (task launches
+    // round-robin over all side streams, the copy on the caller's stream after the join).
     static const int spread_max = [] { const char* e = std::getenv("MQC_HIP_ERI_SPREAD_MAX"); return e ? std::atoi(e) : (1 << 30); }();
+    static const int task_stream_min = [] { const char* e = std::getenv("MQC_HIP_ERI_TASK_STREAM_MIN"); return e ? std::atoi(e) : ERI_TASK_STREAM_MIN_FRAGMENTS; }();
     const bool spread = bv.nfrag <= spread_max;
     const bool forked = cc->shared || spread;
+    const bool task_stream = cc->shared && bv.nfrag >= task_stream_min;      // !plan.on: exactly the earlier path
     if (forked) {
         (void)hipEventRecord(st.fork, s);
         for (int k = 0; k < ERI_SIDE_STREAMS; ++k) (void)hipStreamWaitEvent(st.side[k], st.fork, 0);
     }
     int rr = 0;
-    // spread mode: longest-processing-time-first assignment of the class launches to the 1 + ERI_SIDE_STREAMS
-    // streams.  A small-batch launch lasts as long as its heaviest thread: primitive quartets of the first (deepest)
-    // entry x work per primitive quartet x passes.
+    // A small-batch launch lasts as long as its heaviest thread: primitive quartets of the first (deepest) entry x work
+    // per primitive quartet x passes.
+    auto entry_cost = [&](const EriLaunch& L, const int* e) {
+        const auto& cl = topo.classes[L.cls];
+        double prims = 1.0;
+        for (int q = 0; q < 4; ++q) prims *= topo.shells[e[q] & 0xffff].nprim;
+        const int nc = ncart(cl.la) * ncart(cl.lb) * ncart(cl.lc) * ncart(cl.ld);
+        const int passes = eri_uses_passes(cl.la, cl.lb, cl.lc, cl.ld)
+                               ? (nsph(cl.lc) * nsph(cl.ld) + eri_pass_chunk(cl.la, cl.lb, cl.lc, cl.ld) - 1) / eri_pass_chunk(cl.la, cl.lb, cl.lc, cl.ld)
+                               : 1;
+        return prims * (nc + 8.0 * nherm(cl.la + cl.lb + cl.lc + cl.ld)) * passes * (L.twin ? 1.5 : 1.0);
+    };
+    // spread mode: longest-processing-time-first assignment of the dense launches to the caller's stream and the side
+    // streams (all of them, or all but the task stream).
     std::vector<int> lane_of(cc->launches.size(), 0), issue_order;
     if (spread) {
         std::vector<std::pair<double, int>> cost(cc->launches.size());
         for (size_t k = 0; k < cc->launches.size(); ++k) {
             const EriLaunch& L = cc->launches[k];
-            const auto& cl = topo.classes[L.cls];
-            double c = 0.0;
-            if (L.dense_n > 0) {
-                const int* e = cc->host.data() + L.dense_off;
-                double prims = 1.0;
-                for (int q = 0; q < 4; ++q) prims *= topo.shells[e[q] & 0xffff].nprim;
-                const int nc = ncart(cl.la) * ncart(cl.lb) * ncart(cl.lc) * ncart(cl.ld);
-                const int passes = eri_uses_passes(cl.la, cl.lb, cl.lc, cl.ld)
-                                       ? (nsph(cl.lc) * nsph(cl.ld) + eri_pass_chunk(cl.la, cl.lb, cl.lc, cl.ld) - 1) / eri_pass_chunk(cl.la, cl.lb, cl.lc, cl.ld)
-                                       : 1;
-                c = prims * (nc + 8.0 * nherm(cl.la + cl.lb + cl.lc + cl.ld)) * passes * (L.twin ? 1.5 : 1.0);
-            }
-            cost[k] = {c, (int)k};
+            cost[k] = {L.dense_n > 0 ? entry_cost(L, cc->host.data() + L.dense_off) : 0.0, (int)k};
         }
         std::sort(cost.begin(), cost.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
         for (auto& ck : cost) issue_order.push_back(ck.second);
@@ -629,10 +655,25 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
         if (ERI_SIDE_STREAMS >= 3 && !cost.empty()) load[3] = 1.5 * cost.front().first;
         for (auto& ck : cost) {
             int best = 0;
-            for (int q = 1; q <= ERI_SIDE_STREAMS; ++q) if (load[q] < load[best]) best = q;
+            for (int q = 1; q <= ERI_SIDE_STREAMS; ++q) {
+                if (task_stream && q == 1) continue;          // side[0]: the tasks and their copy
+                if (load[q] < load[best]) best = q;
+            }
             load[best] += ck.first;
             lane_of[ck.second] = best;
         }
+    }
+    // the task launches in the order they go on the task stream: heaviest first, by the same cost expression applied
+    // to the shared list's first entry
+    std::vector<int> task_order;
+    if (task_stream) {
+        std::vector<std::pair<double, int>> tc;
+        for (size_t k = 0; k < cc->launches.size(); ++k) {
+            const EriLaunch& L = cc->launches[k];
+            if (L.sh_n > 0 && L.ntasks > 0) tc.push_back({entry_cost(L, cc->host.data() + L.sh_off), (int)k});
+        }
+        std::stable_sort(tc.begin(), tc.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
+        for (auto& t : tc) task_order.push_back(t.second);
     }
     int li = 0;
     auto dense_stream = [&]() { if (!spread) return s; const int k = lane_of[li]; return k == 0 ? s : st.side[k - 1]; };
@@ -641,28 +682,32 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
     // default 7: (dd|dp) and (dd|dd); MQC_HIP_ERI_GENERAL=k moves the border (4 = every pass class, 99 = f shells only)
     static const int gen_from = [] { const char* e = std::getenv("MQC_HIP_ERI_GENERAL"); return e ? std::atoi(e) : 7; }();
     auto to_general = [&](const Topology::ClassList& c) { return class_is_general(c.la, c.lb, c.lc, c.ld, gen_from); };
+    bool do_dense = true, do_tasks = true;                // which half of a launch entry an issue() call puts out
+    auto task_s = [&]() { return task_stream ? st.side[0] : st.side[rr++ % ERI_SIDE_STREAMS]; };
 #define ERI_CASE(a, b, c, d_)                                                                                         \
     if (!general && cl.la == a && cl.lb == b && cl.lc == c && cl.ld == d_) {                                          \
         if (att) {                                                                                                    \
-            launch_eri_class<a, b, c, d_, true>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream()); \
-            launch_eri_class<a, b, c, d_, true>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, st.side[rr++ % ERI_SIDE_STREAMS]); \
+            if (do_dense) launch_eri_class<a, b, c, d_, true>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream()); \
+            if (do_tasks) launch_eri_class<a, b, c, d_, true>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, task_s()); \
         } else {                                                                                                      \
-        launch_eri_class<a, b, c, d_>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream());         \
-        launch_eri_class<a, b, c, d_>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, st.side[rr++ % ERI_SIDE_STREAMS]); \
+            if (do_dense) launch_eri_class<a, b, c, d_>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream()); \
+            if (do_tasks) launch_eri_class<a, b, c, d_>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, task_s()); \
         }                                                                                                             \
     }
 #define TWIN_CASE(a, b, c, d_)                                                                                        \
     if (cl.la == a && cl.lb == b && cl.lc == c && cl.ld == d_) {                                                      \
-        if (twin_wave && (a) <= 1 && (b) == 0 && (c) == 0 && (d_) == 0)                                               \
+        if (!do_dense) {}                                                                                             \
+        else if (twin_wave && (a) <= 1 && (b) == 0 && (c) == 0 && (d_) == 0)                                          \
             launch_twin_wave(a, d + L.dense_off, L.dense_n, dense_stream());                                          \
         else if (att)                                                                                                 \
             launch_eri_twin_class<a, b, c, d_, true>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream()); \
         else                                                                                                          \
-        launch_eri_twin_class<a, b, c, d_>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream());    \
-        if (att)                                                                                                      \
-            launch_eri_twin_class<a, b, c, d_, true>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, st.side[rr++ % ERI_SIDE_STREAMS]); \
+            launch_eri_twin_class<a, b, c, d_>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream()); \
+        if (!do_tasks) {}                                                                                             \
+        else if (att)                                                                                                 \
+            launch_eri_twin_class<a, b, c, d_, true>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, task_s()); \
         else                                                                                                          \
-        launch_eri_twin_class<a, b, c, d_>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, st.side[rr++ % ERI_SIDE_STREAMS]); \
+            launch_eri_twin_class<a, b, c, d_>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, task_s()); \
     }
     // small batches: the twin (ss|ss) and (ps|ss) entries one wave per (entry, fragment) (eri_twin_wave_kernel)
     static const int twin_wave_max = [] { const char* e = std::getenv("MQC_HIP_TWIN_WAVE_MAX"); return e ? std::atoi(e) : ERI_TWIN_WAVE_MAX_FRAGMENTS; }();
@@ -673,19 +718,14 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
         else if (la == 0) launch_eri_twin_wave_class<0, 0, 0, 0>(bv, list, nq, Q, thresh, st_);
         else launch_eri_twin_wave_class<1, 0, 0, 0>(bv, list, nq, Q, thresh, st_);
     };
-    // in spread mode the launches are issued heaviest first (stream order = issue order)
-    std::vector<int> order(cc->launches.size());
-    for (size_t k = 0; k < order.size(); ++k) order[k] = (int)k;
-    if (spread) order = issue_order;
-    for (size_t oi = 0; oi < order.size(); ++oi) {
-        li = order[oi];
+    auto issue = [&]() {            // launch entry li: its dense half, its task half, or both (do_dense / do_tasks)
         const EriLaunch& L = cc->launches[li];
         const auto& cl = topo.classes[L.cls];
         const bool general = to_general(cl);
         if (L.twin) {
             TWIN_CASE(0, 0, 0, 0) TWIN_CASE(1, 0, 0, 0) TWIN_CASE(1, 0, 1, 0) TWIN_CASE(1, 1, 0, 0)
             TWIN_CASE(1, 1, 1, 0) TWIN_CASE(2, 0, 0, 0) TWIN_CASE(2, 0, 1, 0) TWIN_CASE(2, 1, 0, 0)
-            continue;
+            return;
         }
         ERI_CASE(0, 0, 0, 0)
         ERI_CASE(1, 0, 0, 0) ERI_CASE(1, 0, 1, 0)
@@ -696,9 +736,30 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
         ERI_CASE(2, 2, 2, 2)
         if (general) {
             // a class with an f shell (or a d-heavy class routed here): the wave-cooperative LDS kernel
-            launch_eri_general(bv, cl.la, cl.lb, cl.lc, cl.ld, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream(), att);
-            launch_eri_general(bv, cl.la, cl.lb, cl.lc, cl.ld, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, st.side[rr++ % ERI_SIDE_STREAMS], att);
+            if (do_dense) launch_eri_general(bv, cl.la, cl.lb, cl.lc, cl.ld, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream(), att);
+            if (do_tasks) launch_eri_general(bv, cl.la, cl.lb, cl.lc, cl.ld, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, task_s(), att);
         }
+    };
+    auto copy_shared = [&](hipStream_t cs) {
+        hipLaunchKernelGGL(eri_broadcast_kernel, dim3((unsigned)np, (unsigned)bv.nfrag), dim3(256), 0, cs, bv,
+                           d + cc->pair_off, d + cc->pp_off, cc->nap, (const unsigned char*)(d + cc->any_off), d + cc->rep_off);
+    };
+    // in spread mode the launches are issued heaviest first (stream order = issue order)
+    std::vector<int> order(cc->launches.size());
+    for (size_t k = 0; k < order.size(); ++k) order[k] = (int)k;
+    if (spread) order = issue_order;
+    if (task_stream) {
+        // dense and task launches alternate in issue order, each heaviest first on its own streams; the copy follows the
+        // last task launch at once, ahead of the dense launches still to be issued
+        const size_t nt = task_order.size();
+        for (size_t oi = 0; oi < order.size() || oi < nt; ++oi) {
+            if (oi < order.size()) { li = order[oi]; do_dense = true; do_tasks = false; issue(); }
+            if (oi < nt) { li = task_order[oi]; do_dense = false; do_tasks = true; issue(); }
+            if (oi + 1 == nt) copy_shared(st.side[0]);
+        }
+        if (nt == 0) copy_shared(st.side[0]);
+    } else {
+        for (size_t oi = 0; oi < order.size(); ++oi) { li = order[oi]; issue(); }
     }
 #undef ERI_CASE
 #undef TWIN_CASE
@@ -708,10 +769,7 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
             (void)hipStreamWaitEvent(s, st.join[k], 0);
         }
     }
-    if (cc->shared) {
-        hipLaunchKernelGGL(eri_broadcast_kernel, dim3((unsigned)np, (unsigned)bv.nfrag), dim3(256), 0, s, bv,
-                           d + cc->pair_off, d + cc->pp_off, cc->nap, (const unsigned char*)(d + cc->any_off), d + cc->rep_off);
-    }
+    if (cc->shared && !task_stream) copy_shared(s);
 }
 
 
