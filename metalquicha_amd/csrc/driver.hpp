@@ -2,6 +2,8 @@
 // Declarations only; everything here is defined in engine.cpp.
 #pragma once
 #include "engine.hpp"
+#include <condition_variable>
+#include <mutex>
 
 namespace mqc {
 
@@ -36,6 +38,17 @@ struct AtomicGuess {
     int nmodes = 0;
 };
 
+// A batch call that defers its small topology groups (scf_run_batch_impl): the largest group's batch opens the gate
+// once its first chunk's integrals are done, the other groups' batches wait at it before they enqueue anything.  Host
+// side only: a wait packet in a hardware queue would hold up the large group's own streams that share that queue.
+struct GroupGate {
+    std::mutex m;
+    std::condition_variable cv;
+    bool is_open = false;
+    void open() { { std::lock_guard<std::mutex> lock(m); is_open = true; } cv.notify_all(); }
+    void wait() { std::unique_lock<std::mutex> lock(m); cv.wait(lock, [this] { return is_open; }); }
+};
+
 // What the stages of one batch call share besides the plan: the inputs, ordered by compactness, the device topology
 // and grid, and the statistics, gathered locally (two lanes may run at once) and merged at the end
 struct Batch {
@@ -54,11 +67,18 @@ struct Batch {
     TopologyDev td{}, tdx{};
     GridDev grid;
     Stats stats;
+    GroupGate* gate = nullptr;                       // opened when the first chunk's integral stage has been joined (scf_loop)
+    int chain_side = 2;                              // side stream of the one-electron chain (prepare)
 };
 
 // radial cache of the quadrature: MQC_HIP_XC_RADIAL_CACHE=0 turns it off
 bool xc_radial_cache_on();
 // exchange-correlation: per-element grid templates and the per-topology point list
 int upload_grid(mqc_hip_context* ctx, Batch& b, DevicePool& pool, hipStream_t s);
+
+
+// The integral stage of `slot` uses its first `count` side streams only, and charges the one-electron chain of the
+// chunk (prepare) to side stream `chain_side` (kern_eri.hip).  Set between calls of the stage, never inside one.
+void eri_limit_side_streams(int slot, int count, int chain_side);
 
 }  // namespace mqc

@@ -433,7 +433,7 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
     // The one-electron stage, the orthogonaliser and the starting guess need the geometry (S, H) only and are
     // latency-bound (six class launches; one workgroup per fragment, Jacobi sweeps): they run on a side stream next
     // to the compute-bound two-electron stage, which does not wait for them (0.7 ms of a single-fragment call)
-    hipStream_t so = ctx->side[sl.id & 1][2];
+    hipStream_t so = ctx->side[sl.id & 1][b.chain_side];
     HIP_CHECK_RET(hipEventRecord(ctx->evo[sl.id & 1][0], s));             // uploads and resets above are in
     HIP_CHECK_RET(hipStreamWaitEvent(so, ctx->evo[sl.id & 1][0], 0));
     launch_int1e(bv, topo, so);
@@ -531,6 +531,7 @@ static int scf_loop(const BatchPlan& plan, Batch& b, const Slot& sl, Job& job)
     const double t3 = now_s();
     HIP_CHECK_RET(hipStreamSynchronize(s));
     if ((rc = stage_check("integrals")) != MQC_HIP_OK) return rc;
+    if (b.gate) b.gate->open();         // deferred small groups start now: from here on this batch uses one stream
     {
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, sl.q0, sl.q1);
@@ -583,7 +584,10 @@ static int scf_loop(const BatchPlan& plan, Batch& b, const Slot& sl, Job& job)
             // the triangular kernel skips rows the Schwarz bounds prove zero and reports the chunks it did read
             if (bv.eri_tri && bv.jk_loaded && tri_doubles_per_fragment < 0.0) {
                 std::vector<int> ld(nf);
-                if (hipMemcpy(ld.data(), bv.jk_loaded, sizeof(int) * (size_t)nf, hipMemcpyDeviceToHost) == hipSuccess) {
+                // on this batch's own stream (it was joined a few lines up): a copy on the null stream waits for every blocking
+                // stream of the process, the other lane's included -- for its whole integral stage when that has just begun
+                if (hipMemcpyAsync(ld.data(), bv.jk_loaded, sizeof(int) * (size_t)nf, hipMemcpyDeviceToHost, s) == hipSuccess &&
+                    hipStreamSynchronize(s) == hipSuccess) {
                     double sum = 0.0;
                     for (int v : ld) sum += v;
                     tri_doubles_per_fragment = 128.0 * sum / (double)nf;
@@ -868,6 +872,9 @@ struct Work {
     std::vector<const double*> d0;       // mqc_hip_scf_run_batch_restart only: starting densities ...
     std::vector<double*> spin;           // ... and the spin densities' destinations; empty when the call brought none
     std::shared_ptr<AtomicGuess> guess;
+    // deferred small groups (scf_run_batch_impl): the largest group's batch opens the gate, the others wait at it
+    GroupGate* opens = nullptr;
+    GroupGate* waits = nullptr;
     int rc = MQC_HIP_OK;
     std::string msg;
 };
@@ -883,6 +890,10 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
     const double t_begin = now_s();
     const int ntot = (int)w.xyz.size();
     Batch b{topo, aux, opts, w.guess.get()};
+    b.gate = w.opens;
+    if (w.waits && second) b.chain_side = 1;         // deferred on lane 1: its third side stream stays idle (scf_run_batch_impl)
+    // whichever way this batch ends (refusal, error return, no chunk that reaches scf_loop), the waiting groups go on
+    struct GateOpener { GroupGate* g; ~GateOpener() { if (g) g->open(); } } const opener{w.opens};
     BatchPlan plan;
     // external point charges (FMO / EE-MBE embedding) and h_extra: the same in every fragment of the group (its key says so)
     plan.npc = ntot > 0 ? w.mol[0]->n_point_charges : 0;
@@ -920,6 +931,7 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
             if (!b.mols[k]->point_charge_xyz || !b.mols[k]->point_charges) { msg = "point charges announced but their arrays are NULL"; rc = MQC_HIP_ERR_VALIDATION; }
     if (rc == MQC_HIP_OK && plan.two_e == TWO_E_DF && !aux) { msg = "density fitting needs an auxiliary basis"; rc = MQC_HIP_ERR_VALIDATION; }
     if (rc != MQC_HIP_OK) return refuse(b.results, rc, msg);
+    if (w.waits) w.waits->wait();       // nothing of a deferred group is enqueued before the large group's integrals are done
     rc = upload_topology(ctx, topo, b.td, second ? &ctx->pool_topo2 : &ctx->pool_topo, lane_stream);
     if (rc != MQC_HIP_OK) return rc;
     if (plan.two_e == TWO_E_DF) {
@@ -1427,7 +1439,33 @@ static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip
     if (work.size() >= 2 && ctx->concurrent_groups) {
         // largest group first on lane 0; the others queue up on lane 1, then lane 0 helps with what is left
         std::sort(work.begin(), work.end(), [](const Work& a, const Work& b) { return a.xyz.size() > b.xyz.size(); });
-        std::atomic<size_t> next{0};
+        // A large group's integral stage wants all four hardware queues: its streams alias pairwise onto the queues of
+        // the other lane's streams, and behind the small groups' latency-bound launches (0.1-2.6 ms each) they started
+        // 2.6-12 ms late ((H2O)64 MBE-2: 2016 dimers behind 64 monomers, profiles/r04_b_..._task_stream.txt).  So when
+        // the largest group has at least DEFER_MIN fragments and every other group holds at most one eighth of its
+        // stored integrals (fragments x n_ao^4: a monomer group as numerous as its dimers still is 1/16 of them), the
+        // other groups wait -- on the host -- until the large group's first chunk has joined its integral stage; they
+        // then run next to its SCF loop, which uses one stream.  MQC_HIP_DEFER_SMALL_GROUPS_MIN overrides the border;
+        // 0: never defer.  The border is ERI_TASK_STREAM_MIN_FRAGMENTS' (kern_eri.hip).
+        static const long defer_min = [] { const char* e = std::getenv("MQC_HIP_DEFER_SMALL_GROUPS_MIN"); return e ? std::atol(e) : 1024L; }();
+        auto weight = [](const Work& x) { const double n = (double)x.topo->nao; return (double)x.xyz.size() * n * n * n * n; };
+        bool defer = defer_min > 0 && (long)work[0].xyz.size() >= defer_min;
+        for (size_t k = 1; k < work.size() && defer; ++k) defer = 8.0 * weight(work[k]) <= weight(work[0]);
+        // The deferred groups then run next to the large group's SCF loop, which is one stream on one hardware queue;
+        // lane 1's third side stream shares that queue, and a kernel of the loop waits behind whatever sits there (2.3 ms
+        // of the first iteration behind the monomers' one-electron chain and class launches, profiles/r05_e_...).  So a
+        // deferring call keeps lane 1 to its other streams, the one-electron chain on the second side stream.
+        GroupGate gate;
+        if (defer) {
+            work[0].opens = &gate;
+            for (size_t k = 1; k < work.size(); ++k) work[k].waits = &gate;
+            eri_limit_side_streams(1, 2, 1);
+            // MQC_HIP_DEFER_SMALL_GROUPS_TRACE=1: one line per deferring call (the tests read it)
+            static const bool trace = [] { const char* e = std::getenv("MQC_HIP_DEFER_SMALL_GROUPS_TRACE"); return e && e[0] == '1'; }();
+            if (trace) std::fprintf(stderr, "mqc_hip: %zu small groups deferred behind a group of %zu fragments\n", work.size() - 1, work[0].xyz.size());
+        }
+        // a deferring call hands the large group to lane 0 itself: lane 1's thread may come first to the counter
+        std::atomic<size_t> next{defer ? 1u : 0u};
         auto worker = [&](int lane) {
             for (;;) {
                 const size_t k = next.fetch_add(1);
@@ -1436,8 +1474,10 @@ static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip
             }
         };
         std::thread t1(worker, 1);
+        if (defer) run_one(work[0], 0);
         worker(0);
         t1.join();
+        if (defer) eri_limit_side_streams(1, 1 << 20, 2);
     } else {
         for (auto& w : work) run_one(w, -1);
     }

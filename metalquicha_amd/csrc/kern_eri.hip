@@ -1,6 +1,7 @@
 // kern_eri.hip -- dispatcher of the four-centre ERI formation (kernels: eri_kernels.hpp,
 // instantiated per class group in kern_eri_inst.hip).
 #include "eri_kernels.hpp"
+#include "driver.hpp"
 #include <array>
 #include <cstring>
 #include <map>
@@ -255,6 +256,8 @@ struct EriSlotState {
     DevicePool qpool, pairs;
     hipStream_t side[ERI_SIDE_MAX] = {};
     hipEvent_t fork = nullptr, join[ERI_SIDE_MAX] = {};
+    // eri_limit_side_streams: side streams this slot may use, and the one that carries the one-electron chain
+    int limit = ERI_SIDE_MAX, chain = 2;
 };
 }  // namespace
 
@@ -308,6 +311,15 @@ static EriSlotState& eri_slot_state(int slot)
     return st;
 }
 
+// A lane whose batches run next to another lane's SCF loop keeps off the hardware queue of that loop's stream: it uses
+// its first `count` side streams only and its one-electron chain sits on side stream `chain_side` (engine.cpp)
+void eri_limit_side_streams(int slot, int count, int chain_side)
+{
+    EriSlotState& st = eri_slot_state(slot);
+    st.limit = count < 1 ? 1 : (count > ERI_SIDE_MAX ? ERI_SIDE_MAX : count);
+    st.chain = chain_side;
+}
+
 // Screened build, part 1: Schwarz bounds of every shell pair and the zero fill of the tensor, put on the side
 // streams as soon as the geometry is on the device (call it right after the upload, before the one-electron
 // stage): the six class kernels are latency-bound -- (dd|dd) alone is 6 k threads for 4.7 ms -- and run next to
@@ -315,6 +327,7 @@ static EriSlotState& eri_slot_state(int slot)
 void launch_eri_bounds(const BatchView& bv, const Topology& topo, double schwarz_tol, hipStream_t s)
 {
     EriSlotState& st = eri_slot_state(bv.slot);
+    const int nside = std::min(eri_side_streams(), st.limit);
     st.bounds_pending = false;
     if (!(schwarz_tol > 0.0)) return;
     const size_t np = (size_t)bv.npair;
@@ -340,15 +353,15 @@ void launch_eri_bounds(const BatchView& bv, const Topology& topo, double schwarz
         if (same) { st.same_atom.push_back(A); st.same_atom.push_back(B); }
     }
     (void)hipEventRecord(st.fork, s);
-    for (int k = 0; k < ERI_SIDE_STREAMS; ++k) (void)hipStreamWaitEvent(st.side[k], st.fork, 0);
+    for (int k = 0; k < nside; ++k) (void)hipStreamWaitEvent(st.side[k], st.fork, 0);
     size_t off = 0;
     int rr = 0;
     double* Q = st.Q;
     // the zero fill first, on the last stream, which it keeps to itself when there are streams to spare: with the
     // one-centre bounds out of the way it is the longest item here (12 GB for 2016 dimers, 2.8 ms), the class kernels wait
     // for it, and a bound launch queued behind it made them wait for both
-    if (bv.eri) (void)hipMemsetAsync(bv.eri, 0, sizeof(double) * bv.eri_stride * bv.nfrag, st.side[ERI_SIDE_STREAMS - 1]);
-    const int nb_streams = (bv.eri && ERI_SIDE_STREAMS >= 4) ? ERI_SIDE_STREAMS - 1 : ERI_SIDE_STREAMS;
+    if (bv.eri) (void)hipMemsetAsync(bv.eri, 0, sizeof(double) * bv.eri_stride * bv.nfrag, st.side[nside - 1]);
+    const int nb_streams = (bv.eri && nside >= 4) ? nside - 1 : nside;
     // most expensive class first
 #define SCHWARZ_CASE(a, b)                                                                                                      \
     launch_schwarz_class<a, b>(bv, st.bucket[a][b].data(), (int)st.bucket[a][b].size() / 2, d_pairs + off, Q, st.side[rr++ % nb_streams]); \
@@ -402,7 +415,7 @@ void launch_eri_bounds(const BatchView& bv, const Topology& topo, double schwarz
             launch_schwarz_general(bv, a, b, d_pairs + off, (int)bk.size() / 2, Q, ss);
             off += bk.size();
         }
-    for (int k = 0; k < ERI_SIDE_STREAMS; ++k) (void)hipEventRecord(st.join[k], st.side[k]);
+    for (int k = 0; k < nside; ++k) (void)hipEventRecord(st.join[k], st.side[k]);
     st.bounds_pending = true;
 }
 
@@ -555,6 +568,7 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
     BatchView bv = bv_in;
     bv.omega2 = att ? omega * omega : 0.0;
     EriSlotState& st = eri_slot_state(bv.slot);
+    const int nside = std::min(eri_side_streams(), st.limit);
     const size_t np = (size_t)bv.npair;
     // The class lists cover every element of the pair matrix, so the unscreened build overwrites the whole
     // tensor and needs no zero fill (22 GB for the (H2O)64 dimers); a screened build leaves skipped blocks at zero.
@@ -562,7 +576,7 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
     double thresh = 0.0;
     if (schwarz_tol > 0.0) {
         if (!st.bounds_pending || st.bounds_tol != schwarz_tol) launch_eri_bounds(bv, topo, schwarz_tol, s);
-        for (int k = 0; k < ERI_SIDE_STREAMS; ++k) (void)hipStreamWaitEvent(s, st.join[k], 0);
+        for (int k = 0; k < nside; ++k) (void)hipStreamWaitEvent(s, st.join[k], 0);
         st.bounds_pending = false;
         Q = st.Q;
         thresh = schwarz_tol;
@@ -622,7 +636,7 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
     const bool task_stream = cc->shared && bv.nfrag >= task_stream_min;      // !plan.on: exactly the earlier path
     if (forked) {
         (void)hipEventRecord(st.fork, s);
-        for (int k = 0; k < ERI_SIDE_STREAMS; ++k) (void)hipStreamWaitEvent(st.side[k], st.fork, 0);
+        for (int k = 0; k < nside; ++k) (void)hipStreamWaitEvent(st.side[k], st.fork, 0);
     }
     int rr = 0;
     // A small-batch launch lasts as long as its heaviest thread: primitive quartets of the first (deepest) entry x work
@@ -649,13 +663,13 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
         std::sort(cost.begin(), cost.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
         for (auto& ck : cost) issue_order.push_back(ck.second);
         double load[ERI_SIDE_MAX + 1] = {};
-        // side stream 2 carries the one-electron chain of this chunk (int1e classes, orthogonaliser, guess: engine.cpp) ahead of
+        // side stream 2 (st.chain) carries the one-electron chain of this chunk (int1e classes, orthogonaliser, guess: engine.cpp) ahead of
         // anything queued here -- 1.9 ms for a single fragment, as much as the heaviest class launch: in a batch of one,
         // three class launches placed on it waited for the guess and the whole stage with them (1.3 of 3.2 ms)
-        if (ERI_SIDE_STREAMS >= 3 && !cost.empty()) load[3] = 1.5 * cost.front().first;
+        if (st.chain < nside && !cost.empty()) load[st.chain + 1] = 1.5 * cost.front().first;
         for (auto& ck : cost) {
             int best = 0;
-            for (int q = 1; q <= ERI_SIDE_STREAMS; ++q) {
+            for (int q = 1; q <= nside; ++q) {
                 if (task_stream && q == 1) continue;          // side[0]: the tasks and their copy
                 if (load[q] < load[best]) best = q;
             }
@@ -683,7 +697,7 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
     static const int gen_from = [] { const char* e = std::getenv("MQC_HIP_ERI_GENERAL"); return e ? std::atoi(e) : 7; }();
     auto to_general = [&](const Topology::ClassList& c) { return class_is_general(c.la, c.lb, c.lc, c.ld, gen_from); };
     bool do_dense = true, do_tasks = true;                // which half of a launch entry an issue() call puts out
-    auto task_s = [&]() { return task_stream ? st.side[0] : st.side[rr++ % ERI_SIDE_STREAMS]; };
+    auto task_s = [&]() { return task_stream ? st.side[0] : st.side[rr++ % nside]; };
 #define ERI_CASE(a, b, c, d_)                                                                                         \
     if (!general && cl.la == a && cl.lb == b && cl.lc == c && cl.ld == d_) {                                          \
         if (att) {                                                                                                    \
@@ -764,7 +778,7 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
 #undef ERI_CASE
 #undef TWIN_CASE
     if (forked) {
-        for (int k = 0; k < ERI_SIDE_STREAMS; ++k) {
+        for (int k = 0; k < nside; ++k) {
             (void)hipEventRecord(st.join[k], st.side[k]);
             (void)hipStreamWaitEvent(s, st.join[k], 0);
         }
