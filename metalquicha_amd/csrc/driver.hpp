@@ -80,5 +80,8 @@ int upload_grid(mqc_hip_context* ctx, Batch& b, DevicePool& pool, hipStream_t s)
 // The integral stage of `slot` uses its first `count` side streams only, and charges the one-electron chain of the
 // chunk (prepare) to side stream `chain_side` (kern_eri.hip).  Set between calls of the stage, never inside one.
 void eri_limit_side_streams(int slot, int count, int chain_side);
+// Whether the host may wait inside the integral stage of `slot` until its launches are handed out (the dispatcher of
+// launch_eri, kern_eri.hip): true unless the host has another chunk's SCF loop to run meanwhile.  Default: true.
+void eri_host_may_wait(int slot, bool yes);
 
 }  // namespace mqc

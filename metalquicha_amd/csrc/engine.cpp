@@ -989,6 +989,10 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
         return r;
     };
     const int njobs = (int)jobs.size();
+    // chunks that alternate between the slots: prepare(k + 1) has to return before finish(k) can start, so the integral
+    // stage must not keep the host; a single chunk and a lane go from prepare straight into finish, which blocks anyway
+    const bool alternating = lane < 0 && njobs > 1;
+    if (alternating) { eri_host_may_wait(0, false); eri_host_may_wait(1, false); }
     if (lane >= 0) {
         // one slot only: chunks strictly one after the other
         Slot& sl = slots[lane & 1];
@@ -1002,6 +1006,7 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
             if (rc == MQC_HIP_OK) rc = finish(slots[k & 1], jobs[k]);
         }
     }
+    if (alternating) { eri_host_may_wait(0, true); eri_host_may_wait(1, true); }
     if (rc != MQC_HIP_OK) {
         // drain the streams before the error return hands the pools back
         if (lane != 1) (void)hipStreamSynchronize(ctx->stream);

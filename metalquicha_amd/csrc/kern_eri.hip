@@ -2,12 +2,15 @@
 // instantiated per class group in kern_eri_inst.hip).
 #include "eri_kernels.hpp"
 #include "driver.hpp"
+#include "eri_dispatch.hpp"
 #include <array>
+#include <chrono>
 #include <cstring>
 #include <map>
 #include <unordered_map>
 #include <functional>
 #include <string>
+#include <thread>
 
 namespace mqc {
 
@@ -258,6 +261,12 @@ struct EriSlotState {
     hipEvent_t fork = nullptr, join[ERI_SIDE_MAX] = {};
     // eri_limit_side_streams: side streams this slot may use, and the one that carries the one-electron chain
     int limit = ERI_SIDE_MAX, chain = 2;
+    // the dispatcher of launch_eri: false while the driver alternates chunks between the two slots, where the host has
+    // the other slot's SCF loop to run and must not wait in this one's integral stage (eri_host_may_wait)
+    bool host_may_wait = true;
+    // its events, created at the first dispatching call, timing disabled.  Per stream (0: the caller's, k + 1: side[k])
+    // one behind each launch in flight, and one behind what the stream carried before the stage; one behind the copy
+    hipEvent_t disp_done[ERI_SIDE_MAX + 1][eri_dispatch::MAX_DEPTH] = {}, disp_before[ERI_SIDE_MAX + 1] = {}, disp_copy = nullptr;
 };
 }  // namespace
 
@@ -292,6 +301,13 @@ void eri_reset_state()
             st.side[k] = nullptr;
             g_preset_side[sl][k] = nullptr;
         }
+        for (int q = 0; q <= ERI_SIDE_MAX; ++q) {
+            for (auto& e : st.disp_done[q]) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+            if (st.disp_before[q]) (void)hipEventDestroy(st.disp_before[q]);
+            st.disp_before[q] = nullptr;
+        }
+        if (st.disp_copy) (void)hipEventDestroy(st.disp_copy);
+        st.disp_copy = nullptr;
         for (auto& c : st.cache) { c.valid = false; c.key = 0; c.host.clear(); c.launches.clear(); }
         st.bounds_pending = false; st.Q = nullptr; st.next = 0; st.q1_key.clear(); st.q1_vals = nullptr;
     }
@@ -318,6 +334,14 @@ void eri_limit_side_streams(int slot, int count, int chain_side)
     EriSlotState& st = eri_slot_state(slot);
     st.limit = count < 1 ? 1 : (count > ERI_SIDE_MAX ? ERI_SIDE_MAX : count);
     st.chain = chain_side;
+}
+
+// Whether the host may wait inside the slot's integral stage (launch_eri's dispatcher polls the streams for the whole
+// dense phase): yes when nothing else waits for the host until the stage ends -- a single chunk, a lane, a stage-level
+// entry -- and no while chunks alternate between the slots.  Set between calls of the stage, never inside one.
+void eri_host_may_wait(int slot, bool yes)
+{
+    eri_slot_state(slot).host_may_wait = yes;
 }
 
 // Screened build, part 1: Schwarz bounds of every shell pair and the zero fill of the tensor, put on the side
@@ -634,6 +658,43 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
     const bool spread = bv.nfrag <= spread_max;
     const bool forked = cc->shared || spread;
     const bool task_stream = cc->shared && bv.nfrag >= task_stream_min;      // !plan.on: exactly the earlier path
+    // The dispatcher: large spread batches whose host has nothing else to do until the stage ends (host_may_wait) do
+    // not place their dense launches ahead of time.  The host hands them out, heaviest first, as the streams drain: an
+    // event behind every launch, hipEventQuery polls with a short sleep in between, and the rule of eri_dispatch.hpp --
+    // the stream with the fewest launches in flight, at most `depth` per stream.  Every stream of the slot takes part.
+    // A stream that carries other work when the stage starts counts as full until one event behind that work is
+    // complete: on the chain stream and after an earlier launch_eri call that is disp_before[], recorded below ahead
+    // of the fork wait; on the task stream it is disp_copy, recorded behind the copy, so dense launches queue behind
+    // the copy once it is done (safe by the three points above: the copy reads what the task launches wrote and writes
+    // elements no dense launch writes).  No cost model decides a placement; entry_cost only orders the launches, as it
+    // does for the static placement (ordered by a summed cost of all entries, or with the launches of few threads
+    // between those of many, the stage was 0.4-0.8 ms slower, profiles/r06_e).
+    // MQC_HIP_ERI_DISPATCH_MIN=n: from n fragments on (default: the task stream's border, 1024; 0: every spread batch;
+    // negative: never).  MQC_HIP_ERI_DISPATCH_DEPTH: launches in flight per stream (default 2; at depth 1 a stream idles
+    // for one host reaction after every launch and nothing is gained).  Below the border launches last 0.05-0.3 ms, a
+    // poll costs as much as a launch, and the static placement below runs unchanged.  The gain is small because the
+    // launches share the card -- a launch lasts as long as its neighbours let it, the stage as long as the summed work
+    // (DESIGN 10.2): 2016 dimers, same box, builds alternating, five runs each, ms per evaluation median / min / max
+    // 86.19 / 85.91 / 86.32 -> 85.21 / 84.71 / 85.79, stage clock 29.05 -> 28.09 ms (profiles/r06_a).
+    static const int dispatch_min = [] { const char* e = std::getenv("MQC_HIP_ERI_DISPATCH_MIN"); return e ? std::atoi(e) : ERI_TASK_STREAM_MIN_FRAGMENTS; }();
+    static const int dispatch_depth = [] {
+        const char* e = std::getenv("MQC_HIP_ERI_DISPATCH_DEPTH");
+        const int v = e ? std::atoi(e) : 2;
+        return v < 1 ? 1 : (v > eri_dispatch::MAX_DEPTH ? eri_dispatch::MAX_DEPTH : v);
+    }();
+    // MQC_HIP_ERI_DISPATCH_TRACE=1: one line per dispatching call (the tests read it)
+    static const bool dispatch_trace = [] { const char* e = std::getenv("MQC_HIP_ERI_DISPATCH_TRACE"); return e && e[0] == '1'; }();
+    bool dynamic = spread && st.host_may_wait && dispatch_min >= 0 && bv.nfrag >= dispatch_min && hipPeekAtLastError() == hipSuccess;
+    if (dynamic) {
+        auto make = [&](hipEvent_t& e) { if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { e = nullptr; dynamic = false; } };
+        for (int q = 0; q <= nside; ++q) {
+            for (int j = 0; j < dispatch_depth; ++j) make(st.disp_done[q][j]);
+            make(st.disp_before[q]);
+        }
+        make(st.disp_copy);
+        // what each side stream carries from before this call, ahead of the fork wait
+        for (int k = 0; k < nside && dynamic; ++k) dynamic = hipEventRecord(st.disp_before[k + 1], st.side[k]) == hipSuccess;
+    }
     if (forked) {
         (void)hipEventRecord(st.fork, s);
         for (int k = 0; k < nside; ++k) (void)hipStreamWaitEvent(st.side[k], st.fork, 0);
@@ -652,7 +713,8 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
         return prims * (nc + 8.0 * nherm(cl.la + cl.lb + cl.lc + cl.ld)) * passes * (L.twin ? 1.5 : 1.0);
     };
     // spread mode: longest-processing-time-first assignment of the dense launches to the caller's stream and the side
-    // streams (all of them, or all but the task stream).
+    // streams (all of them, or all but the task stream).  With the dispatcher on this is the issue order, and the
+    // placement of whatever is left should a poll fail.
     std::vector<int> lane_of(cc->launches.size(), 0), issue_order;
     if (spread) {
         std::vector<std::pair<double, int>> cost(cc->launches.size());
@@ -690,7 +752,8 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
         for (auto& t : tc) task_order.push_back(t.second);
     }
     int li = 0;
-    auto dense_stream = [&]() { if (!spread) return s; const int k = lane_of[li]; return k == 0 ? s : st.side[k - 1]; };
+    int placed_on = -1;                                   // the dispatcher's choice for the launch being issued
+    auto dense_stream = [&]() { if (!spread) return s; const int k = placed_on >= 0 ? placed_on : lane_of[li]; return k == 0 ? s : st.side[k - 1]; };
     // MQC_HIP_ERI_GENERAL=k: classes whose total angular momentum is >= k AND that would take the pass kernels go
     // through the wave-cooperative LDS kernel instead (no scratch, one wave per quartet and fragment); default: off
     // default 7: (dd|dp) and (dd|dd); MQC_HIP_ERI_GENERAL=k moves the border (4 = every pass class, 99 = f shells only)
@@ -762,7 +825,75 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
     std::vector<int> order(cc->launches.size());
     for (size_t k = 0; k < order.size(); ++k) order[k] = (int)k;
     if (spread) order = issue_order;
-    if (task_stream) {
+    if (dynamic) {
+        eri_dispatch::Book book(nside + 1, dispatch_depth);
+        auto stream_of = [&](int q) { return q == 0 ? s : st.side[q - 1]; };
+        for (int q = 1; q <= nside; ++q) book.block(q);
+        const size_t nt = task_order.size();
+        size_t ti = 0;
+        bool copy_issued = false;
+        int ndense = 0, nplaced = 0;
+        long waits = 0;
+        // hipEventQuery answers hipErrorNotReady while work is pending and leaves it as the thread's last error, which
+        // stage_check would report: a not-ready poll is consumed here.  Any other answer stays and ends the dispatching.
+        auto complete = [&](hipEvent_t e) {
+            const hipError_t r = hipEventQuery(e);
+            if (r == hipSuccess) return true;
+            if (r == hipErrorNotReady) (void)hipGetLastError();
+            else dynamic = false;
+            return false;
+        };
+        auto poll = [&]() {
+            for (int q = 0; q <= nside && dynamic; ++q) {
+                if (book.blocked[q]) {
+                    const bool tasks_here = task_stream && q == 1;
+                    if (tasks_here && !copy_issued) continue;
+                    if (complete(tasks_here ? st.disp_copy : st.disp_before[q])) book.unblock(q);
+                    continue;
+                }
+                while (dynamic && book.outstanding[q] > 0 && complete(st.disp_done[q][book.oldest_slot(q)])) book.pop(q);
+            }
+        };
+        // the task launches and the copy: as without the dispatcher, one after each of the first dense launches, the
+        // copy right behind the last of them -- and all that are left before the host waits for the first time
+        auto next_task = [&]() {
+            if (ti < nt) { li = task_order[ti++]; placed_on = -1; do_dense = false; do_tasks = true; issue(); }
+            if (task_stream && ti == nt && !copy_issued) {
+                copy_shared(st.side[0]);
+                if (hipEventRecord(st.disp_copy, st.side[0]) != hipSuccess) dynamic = false;
+                copy_issued = true;
+            }
+        };
+        if (task_stream && nt == 0) next_task();
+        for (size_t oi = 0; oi < order.size(); ++oi) {
+            const bool has_dense = cc->launches[order[oi]].dense_n > 0;
+            ndense += has_dense ? 1 : 0;
+            int q = -1;
+            while (dynamic && has_dense) {
+                if (hipPeekAtLastError() != hipSuccess) { dynamic = false; break; }      // a launch failed: stage_check's
+                poll();
+                if (!dynamic || (q = book.pick()) >= 0) break;
+                if (task_stream && !copy_issued) { next_task(); continue; }
+                ++waits;
+                std::this_thread::sleep_for(std::chrono::microseconds(20));
+            }
+            if (!dynamic) q = -1;
+            // without the task stream an entry's task launch goes out with its dense half, round-robin over the side streams
+            li = order[oi]; placed_on = q; do_dense = true; do_tasks = !task_stream;
+            issue();
+            if (q >= 0) {
+                const int slot = book.push(q);
+                if (hipEventRecord(st.disp_done[q][slot], stream_of(q)) != hipSuccess) dynamic = false;
+                ++nplaced;
+            }
+            placed_on = -1;
+            if (task_stream) next_task();
+        }
+        while (task_stream && !copy_issued) next_task();
+        if (dispatch_trace)
+            std::fprintf(stderr, "mqc_hip: eri dispatch: %d of %d dense launches placed over %d streams, depth %d, %ld waits\n", nplaced, ndense,
+                         nside + 1, dispatch_depth, waits);
+    } else if (task_stream) {
         // dense and task launches alternate in issue order, each heaviest first on its own streams; the copy follows the
         // last task launch at once, ahead of the dense launches still to be issued
         const size_t nt = task_order.size();
