@@ -25,7 +25,7 @@ done
 [ kern_scf.hip -nt kern_scf_wide.hip ] && touch kern_scf_wide.hip
 for f in kern_int1e.hip kern_eri.hip kern_eri_general.hip kern_grad.hip kern_grad_pc.hip kern_esp.hip kern_fock.hip kern_scf.hip kern_scf_wide.hip kern_xc.hip kern_df.hip host_setup.cpp grid_host.cpp engine.cpp stage_entries.cpp; do
   o=_obj/${f%.*}.o
-  if stale "$o" "$f" || { [ "$f" = kern_eri.hip ] && [ eri_dispatch.hpp -nt "$o" ]; }; then run hipcc $FLAGS -x hip -c "$f" -o "$o"; fi
+  if stale "$o" "$f" || { [ "$f" = kern_eri.hip ] && { [ eri_dispatch.hpp -nt "$o" ] || [ eri_plan.hpp -nt "$o" ]; }; }; then run hipcc $FLAGS -x hip -c "$f" -o "$o"; fi
 done
 for p in "${pids[@]}"; do wait $p; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT _obj/*.o

@@ -3,6 +3,7 @@
 #include "eri_kernels.hpp"
 #include "driver.hpp"
 #include "eri_dispatch.hpp"
+#include "eri_plan.hpp"
 #include <array>
 #include <chrono>
 #include <cstring>
@@ -30,20 +31,26 @@ static bool class_is_general(int la, int lb, int lc, int ld, int gen_from)
     return eri_uses_passes(la, lb, lc, ld) && la + lb + lc + ld >= gen_from;
 }
 
+// The 21 classes with their own register kernels (s, p, d shells, la >= lb, lc >= ld, bra >= ket), and the 8 of them
+// that also have a twin kernel: listed once, for the declarations and for the dispatch ladders below.
+#define ERI_CLASSES(X)                                                                            \
+    X(0, 0, 0, 0) X(1, 0, 0, 0) X(1, 0, 1, 0) X(1, 1, 0, 0) X(1, 1, 1, 0) X(1, 1, 1, 1)           \
+    X(2, 0, 0, 0) X(2, 0, 1, 0) X(2, 0, 1, 1) X(2, 0, 2, 0)                                       \
+    X(2, 1, 0, 0) X(2, 1, 1, 0) X(2, 1, 1, 1) X(2, 1, 2, 0) X(2, 1, 2, 1)                         \
+    X(2, 2, 0, 0) X(2, 2, 1, 0) X(2, 2, 1, 1) X(2, 2, 2, 0) X(2, 2, 2, 1) X(2, 2, 2, 2)
+#define ERI_TWIN_CLASSES(X)                                                                       \
+    X(0, 0, 0, 0) X(1, 0, 0, 0) X(1, 0, 1, 0) X(1, 1, 0, 0) X(1, 1, 1, 0) X(2, 0, 0, 0) X(2, 0, 1, 0) X(2, 1, 0, 0)
+
 #define ERI_DECL(a, b, c, d) \
     extern template void launch_eri_class<a, b, c, d>(const BatchView&, const int*, int, const int*, int, const double*, double, hipStream_t); \
     extern template void launch_eri_class<a, b, c, d, true>(const BatchView&, const int*, int, const int*, int, const double*, double, hipStream_t);
 #define SCHWARZ_DECL(a, b) \
     extern template void launch_schwarz_class<a, b>(const BatchView&, const int*, int, int*, double*, hipStream_t);
-ERI_DECL(0, 0, 0, 0) ERI_DECL(1, 0, 0, 0) ERI_DECL(1, 0, 1, 0) ERI_DECL(1, 1, 0, 0) ERI_DECL(1, 1, 1, 0) ERI_DECL(1, 1, 1, 1)
-ERI_DECL(2, 0, 0, 0) ERI_DECL(2, 0, 1, 0) ERI_DECL(2, 0, 1, 1) ERI_DECL(2, 0, 2, 0)
-ERI_DECL(2, 1, 0, 0) ERI_DECL(2, 1, 1, 0) ERI_DECL(2, 1, 1, 1) ERI_DECL(2, 1, 2, 0) ERI_DECL(2, 1, 2, 1)
-ERI_DECL(2, 2, 0, 0) ERI_DECL(2, 2, 1, 0) ERI_DECL(2, 2, 1, 1) ERI_DECL(2, 2, 2, 0) ERI_DECL(2, 2, 2, 1) ERI_DECL(2, 2, 2, 2)
+ERI_CLASSES(ERI_DECL)
 #define TWIN_DECL(a, b, c, d) \
     extern template void launch_eri_twin_class<a, b, c, d>(const BatchView&, const int*, int, const int*, int, const double*, double, hipStream_t); \
     extern template void launch_eri_twin_class<a, b, c, d, true>(const BatchView&, const int*, int, const int*, int, const double*, double, hipStream_t);
-TWIN_DECL(0, 0, 0, 0) TWIN_DECL(1, 0, 0, 0) TWIN_DECL(1, 0, 1, 0) TWIN_DECL(1, 1, 0, 0)
-TWIN_DECL(1, 1, 1, 0) TWIN_DECL(2, 0, 0, 0) TWIN_DECL(2, 0, 1, 0) TWIN_DECL(2, 1, 0, 0)
+ERI_TWIN_CLASSES(TWIN_DECL)
 #define TWINW_DECL(a, b, c, d) \
     extern template void launch_eri_twin_wave_class<a, b, c, d>(const BatchView&, const int*, int, const double*, double, hipStream_t); \
     extern template void launch_eri_twin_wave_class<a, b, c, d, true>(const BatchView&, const int*, int, const double*, double, hipStream_t);
@@ -52,10 +59,7 @@ SCHWARZ_DECL(0, 0) SCHWARZ_DECL(1, 0) SCHWARZ_DECL(1, 1) SCHWARZ_DECL(2, 0) SCHW
 
 #define DIG_DECL(a, b, c, d) \
     extern template void launch_eri_digest_class<a, b, c, d>(const BatchView&, const int*, int, const double*, const double*, double, double*, double*, int, hipStream_t);
-DIG_DECL(0, 0, 0, 0) DIG_DECL(1, 0, 0, 0) DIG_DECL(1, 0, 1, 0) DIG_DECL(1, 1, 0, 0) DIG_DECL(1, 1, 1, 0) DIG_DECL(1, 1, 1, 1)
-DIG_DECL(2, 0, 0, 0) DIG_DECL(2, 0, 1, 0) DIG_DECL(2, 0, 1, 1) DIG_DECL(2, 0, 2, 0)
-DIG_DECL(2, 1, 0, 0) DIG_DECL(2, 1, 1, 0) DIG_DECL(2, 1, 1, 1) DIG_DECL(2, 1, 2, 0) DIG_DECL(2, 1, 2, 1)
-DIG_DECL(2, 2, 0, 0) DIG_DECL(2, 2, 1, 0) DIG_DECL(2, 2, 1, 1) DIG_DECL(2, 2, 2, 0) DIG_DECL(2, 2, 2, 1) DIG_DECL(2, 2, 2, 2)
+ERI_CLASSES(DIG_DECL)
 
 // MQC_HIP_NO_TWIN_BLOCKS=1 forces the segmented treatment everywhere (A/B measurements, tests)
 static bool twin_blocks_disabled()
@@ -201,6 +205,10 @@ static void plan_sharing(const Topology& topo, const double* host_xyz, int nfrag
 
 namespace {
 struct EriLaunch { int cls; bool twin; size_t dense_off; int dense_n; size_t sh_off; int sh_n; size_t task_off; int ntasks; };
+// One half of a launch entry: its dense list (every fragment), or its shared list with the tasks (one representative
+// fragment per distinct geometry)
+enum class Half { dense, tasks };
+struct HalfList { const int* list; int n; const int* tasks; int ntasks; };
 // Everything one launch_eri call uploads, kept per (topology, geometry set): an MBE driver that re-evaluates
 // the same fragments (geometry optimisation steps aside, every SCF restart does) skips planning and upload.
 struct EriListCache {
@@ -236,7 +244,6 @@ static int eri_side_streams()
     }();
     return n;
 }
-#define ERI_SIDE_STREAMS eri_side_streams()
 // Three, not more: ROCm maps streams onto 4 hardware queues in creation order, and a lane's main stream plus its
 // three side streams (created back to back in mqc_hip_context_get) then sit on four different queues; a fourth
 // side stream shares the main stream's queue and its kernels wait behind the orthogonaliser.
@@ -282,7 +289,7 @@ static hipStream_t g_preset_side[2][ERI_SIDE_MAX] = {};
 // side streams created by the context right after the lane's main stream (hardware-queue placement, see above)
 void eri_set_side_streams(int slot, const hipStream_t* streams, int count)
 {
-    for (int k = 0; k < ERI_SIDE_STREAMS && k < count; ++k) g_preset_side[slot & 1][k] = streams[k];
+    for (int k = 0; k < eri_side_streams() && k < count; ++k) g_preset_side[slot & 1][k] = streams[k];
 }
 
 static EriSlotState g_eri_state_slot[2];
@@ -318,7 +325,7 @@ static EriSlotState& eri_slot_state(int slot)
     EriSlotState& st = g_eri_state_slot[slot & 1];
     if (!st.fork) {
         (void)hipEventCreateWithFlags(&st.fork, hipEventDisableTiming);
-        for (int k = 0; k < ERI_SIDE_STREAMS; ++k) {
+        for (int k = 0; k < eri_side_streams(); ++k) {
             if (g_preset_side[slot & 1][k]) st.side[k] = g_preset_side[slot & 1][k];
             else (void)hipStreamCreateWithFlags(&st.side[k], hipStreamNonBlocking);
             (void)hipEventCreateWithFlags(&st.join[k], hipEventDisableTiming);
@@ -581,6 +588,58 @@ __global__ void schwarz_save_kernel(const double* __restrict__ Q, double* __rest
     dst[B * ns + A] = Q[A * ns + B];
 }
 
+// The cost that orders the launches (eri_plan::entry_cost), for the list of L that starts with quartet e
+static double launch_cost(const Topology& topo, const EriLaunch& L, const int* e)
+{
+    const auto& cl = topo.classes[L.cls];
+    int nprim[4];
+    for (int q = 0; q < 4; ++q) nprim[q] = topo.shells[e[q] & 0xffff].nprim;
+    const int l[4] = {cl.la, cl.lb, cl.lc, cl.ld};
+    const int chunk = eri_pass_chunk(cl.la, cl.lb, cl.lc, cl.ld);
+    const int passes = eri_uses_passes(cl.la, cl.lb, cl.lc, cl.ld) ? (nsph(cl.lc) * nsph(cl.ld) + chunk - 1) / chunk : 1;
+    return eri_plan::entry_cost(nprim, l, passes, L.twin);
+}
+
+// the class ladder, plain or erf-attenuated.  twin_wave: the twin (ss|ss) and (ps|ss) entries one wave per (entry,
+// fragment) (eri_twin_wave_kernel); general: the wave-cooperative LDS kernel (a class with an f shell, or a d-heavy
+// class routed there)
+#define TWINW_CASE(a, b, c, d) \
+    if (cl.la == a && cl.lb == b && cl.lc == c && cl.ld == d) return launch_eri_twin_wave_class<a, b, c, d, ATT>(bv, h.list, h.n, Q, thresh, stream);
+#define TWIN_CASE(a, b, c, d) \
+    if (cl.la == a && cl.lb == b && cl.lc == c && cl.ld == d) return launch_eri_twin_class<a, b, c, d, ATT>(bv, h.list, h.n, h.tasks, h.ntasks, Q, thresh, stream);
+#define ERI_CASE(a, b, c, d) \
+    if (cl.la == a && cl.lb == b && cl.lc == c && cl.ld == d) return launch_eri_class<a, b, c, d, ATT>(bv, h.list, h.n, h.tasks, h.ntasks, Q, thresh, stream);
+template <bool ATT>
+static void launch_half(const BatchView& bv, const Topology::ClassList& cl, bool twin, bool twin_wave, bool general, const HalfList& h,
+                        const double* Q, double thresh, hipStream_t stream)
+{
+    if (twin) {
+        if (twin_wave) { TWINW_CASE(0, 0, 0, 0) TWINW_CASE(1, 0, 0, 0) }
+        ERI_TWIN_CLASSES(TWIN_CASE)
+        return;
+    }
+    if (general) launch_eri_general(bv, cl.la, cl.lb, cl.lc, cl.ld, h.list, h.n, h.tasks, h.ntasks, Q, thresh, stream, ATT);
+    else { ERI_CLASSES(ERI_CASE) }
+}
+
+// Launches one half of entry L (lists at d) on `stream`
+static void launch_entry(const BatchView& bv, const Topology& topo, const EriLaunch& L, const int* d, const double* Q, double thresh, bool att,
+                         Half which, hipStream_t stream)
+{
+    // MQC_HIP_ERI_GENERAL=k: classes whose total angular momentum is >= k AND that would take the pass kernels go
+    // through the wave-cooperative LDS kernel instead (no scratch, one wave per quartet and fragment);
+    // default 7: (dd|dp) and (dd|dd); k moves the border (4 = every pass class, 99 = f shells only)
+    static const int gen_from = [] { const char* e = std::getenv("MQC_HIP_ERI_GENERAL"); return e ? std::atoi(e) : 7; }();
+    // small batches only, and only the dense half
+    static const int twin_wave_max = [] { const char* e = std::getenv("MQC_HIP_TWIN_WAVE_MAX"); return e ? std::atoi(e) : ERI_TWIN_WAVE_MAX_FRAGMENTS; }();
+    const auto& cl = topo.classes[L.cls];
+    const HalfList h = which == Half::dense ? HalfList{d + L.dense_off, L.dense_n, nullptr, 0} : HalfList{d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks};
+    const bool twin_wave = which == Half::dense && bv.nfrag <= twin_wave_max;
+    const bool general = class_is_general(cl.la, cl.lb, cl.lc, cl.ld, gen_from);
+    if (att) launch_half<true>(bv, cl, L.twin, twin_wave, general, h, Q, thresh, stream);
+    else launch_half<false>(bv, cl, L.twin, twin_wave, general, h, Q, thresh, stream);
+}
+
 void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol, hipStream_t s, const double* host_xyz, double omega)
 {
     // erf(omega r)/r: the ATT instantiations of every route below, omega^2 carried in this call's copy of the view.
@@ -628,18 +687,17 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
 
     // ---- launches.  The class launches are spread over the caller's stream and the side streams: small batches give
     // every launch only a handful of long-running waves, and even a full batch has a tail per launch; with the launches
-    // placed longest-first their critical paths overlap instead of adding up.
-    // (measured with the longest-first assignment below: 2016 dimers 127.3 -> 124 ms, 1008: 75.3 -> 70.8, 504: 55.0 ->
-    // 49.5, so every batch is spread; MQC_HIP_ERI_SPREAD_MAX=n keeps batches above n fragments on one stream)
-    //
-    // Batches with a share plan: the task-list launches of the shared entries (few, long threads: one lane per entry
-    // and distinct geometry) ALL go on one side stream, heaviest first, with eri_broadcast_kernel right behind them on
-    // that stream; the dense launches go on the caller's stream and the other side streams only, so no dense launch
-    // ever waits behind a task launch and the copy runs next to the dense work instead of after the join.  The task
-    // stream is side[0].  The one-electron chain of the chunk sits on side[2] (see load[3] below), so the tasks and the
-    // chain share a stream only when MQC_HIP_ERI_STREAMS leaves a single side stream; with two or more, side[0] is the
-    // stream with the least summed cost (nothing but the tasks), and side[2] keeps its reservation for the dense
-    // placement.  What makes the overlap correct:
+    // placed longest-first their critical paths overlap instead of adding up (2016 dimers 127.3 -> 124 ms, 1008: 75.3 ->
+    // 70.8, 504: 55.0 -> 49.5, so every batch is spread; MQC_HIP_ERI_SPREAD_MAX=n keeps batches above n fragments on
+    // one stream).  Order and static placement are planned ahead (eri_plan.hpp) and issued by one walk over two queues:
+    //   dense queue: the entries, heaviest dense half first, each on its lane of the plan or, with the dispatcher, on
+    //                the stream eri_dispatch::Book names;
+    //   side queue:  batches with a share plan from MQC_HIP_ERI_TASK_STREAM_MIN fragments on put the task-list launches
+    //                (few, long threads: one lane per entry and distinct geometry) on side[0], heaviest first, and
+    //                eri_broadcast_kernel right behind the last of them; no dense launch is planned there.
+    // After each dense item one side item goes out, the rest of the side queue at the end.  Smaller batches have no
+    // side queue: an entry's task half goes out with its dense half, round-robin over the side streams, and the copy
+    // on the caller's stream after the join.  What makes the overlap correct:
     //   * the zero fill completes before ANY class launch starts: the caller's stream has joined the fill (join[] of
     //     launch_eri_bounds, or the fill sits on the caller's stream itself) before the fork event below is recorded,
     //     and every side stream waits for that event;
@@ -651,31 +709,28 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
     // A range-separated hybrid calls launch_eri twice (eri, then eri_lr): the caller's stream joins every side stream
     // at the end of a call and the next call's fork event is recorded behind that join, so the second call's tasks and
     // copy start after the whole first call and work on the second tensor only (the view is passed by value).
-    // MQC_HIP_ERI_TASK_STREAM_MIN=n: batches of fewer than n fragments keep the earlier placement (task launches
-    // round-robin over all side streams, the copy on the caller's stream after the join).
     static const int spread_max = [] { const char* e = std::getenv("MQC_HIP_ERI_SPREAD_MAX"); return e ? std::atoi(e) : (1 << 30); }();
     static const int task_stream_min = [] { const char* e = std::getenv("MQC_HIP_ERI_TASK_STREAM_MIN"); return e ? std::atoi(e) : ERI_TASK_STREAM_MIN_FRAGMENTS; }();
     const bool spread = bv.nfrag <= spread_max;
     const bool forked = cc->shared || spread;
     const bool task_stream = cc->shared && bv.nfrag >= task_stream_min;      // !plan.on: exactly the earlier path
-    // The dispatcher: large spread batches whose host has nothing else to do until the stage ends (host_may_wait) do
-    // not place their dense launches ahead of time.  The host hands them out, heaviest first, as the streams drain: an
-    // event behind every launch, hipEventQuery polls with a short sleep in between, and the rule of eri_dispatch.hpp --
-    // the stream with the fewest launches in flight, at most `depth` per stream.  Every stream of the slot takes part.
-    // A stream that carries other work when the stage starts counts as full until one event behind that work is
-    // complete: on the chain stream and after an earlier launch_eri call that is disp_before[], recorded below ahead
-    // of the fork wait; on the task stream it is disp_copy, recorded behind the copy, so dense launches queue behind
-    // the copy once it is done (safe by the three points above: the copy reads what the task launches wrote and writes
-    // elements no dense launch writes).  No cost model decides a placement; entry_cost only orders the launches, as it
-    // does for the static placement (ordered by a summed cost of all entries, or with the launches of few threads
-    // between those of many, the stage was 0.4-0.8 ms slower, profiles/r06_e).
+    // The dispatcher: large spread batches whose host has nothing else to do until the stage ends (host_may_wait) take
+    // the lane of a dense launch from the book instead of the plan: an event behind every launch, hipEventQuery polls
+    // with a short sleep in between, and the rule of eri_dispatch.hpp -- the stream with the fewest launches in flight,
+    // at most `depth` per stream.  While it waits for a stream the side queue goes out ahead of its turn.  A stream that
+    // carries other work when the stage starts counts as full until one event behind that work is complete: on the
+    // chain stream and after an earlier launch_eri call that is disp_before[], recorded below ahead of the fork wait; on
+    // the task stream it is disp_copy, recorded behind the copy, so dense launches queue behind the copy once it is done
+    // (safe by the three points above).  No cost model decides a placement; the cost only orders the launches (ordered
+    // by a summed cost of all entries, or with the launches of few threads between those of many, the stage was 0.4-0.8
+    // ms slower, profiles/r06_e).  Should a poll or an event record fail, the launches left take their planned lanes.
     // MQC_HIP_ERI_DISPATCH_MIN=n: from n fragments on (default: the task stream's border, 1024; 0: every spread batch;
     // negative: never).  MQC_HIP_ERI_DISPATCH_DEPTH: launches in flight per stream (default 2; at depth 1 a stream idles
-    // for one host reaction after every launch and nothing is gained).  Below the border launches last 0.05-0.3 ms, a
-    // poll costs as much as a launch, and the static placement below runs unchanged.  The gain is small because the
-    // launches share the card -- a launch lasts as long as its neighbours let it, the stage as long as the summed work
-    // (DESIGN 10.2): 2016 dimers, same box, builds alternating, five runs each, ms per evaluation median / min / max
-    // 86.19 / 85.91 / 86.32 -> 85.21 / 84.71 / 85.79, stage clock 29.05 -> 28.09 ms (profiles/r06_a).
+    // for one host reaction after every launch and nothing is gained).  Below the border launches last 0.05-0.3 ms and a
+    // poll costs as much as a launch.  The gain is small because the launches share the card -- a launch lasts as long
+    // as its neighbours let it, the stage as long as the summed work: 2016 dimers, same box, builds
+    // alternating, five runs each, ms per evaluation median / min / max 86.19 / 85.91 / 86.32 -> 85.21 / 84.71 / 85.79,
+    // stage clock 29.05 -> 28.09 ms (profiles/r06_a).
     static const int dispatch_min = [] { const char* e = std::getenv("MQC_HIP_ERI_DISPATCH_MIN"); return e ? std::atoi(e) : ERI_TASK_STREAM_MIN_FRAGMENTS; }();
     static const int dispatch_depth = [] {
         const char* e = std::getenv("MQC_HIP_ERI_DISPATCH_DEPTH");
@@ -699,215 +754,81 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
         (void)hipEventRecord(st.fork, s);
         for (int k = 0; k < nside; ++k) (void)hipStreamWaitEvent(st.side[k], st.fork, 0);
     }
-    int rr = 0;
-    // A small-batch launch lasts as long as its heaviest thread: primitive quartets of the first (deepest) entry x work
-    // per primitive quartet x passes.
-    auto entry_cost = [&](const EriLaunch& L, const int* e) {
-        const auto& cl = topo.classes[L.cls];
-        double prims = 1.0;
-        for (int q = 0; q < 4; ++q) prims *= topo.shells[e[q] & 0xffff].nprim;
-        const int nc = ncart(cl.la) * ncart(cl.lb) * ncart(cl.lc) * ncart(cl.ld);
-        const int passes = eri_uses_passes(cl.la, cl.lb, cl.lc, cl.ld)
-                               ? (nsph(cl.lc) * nsph(cl.ld) + eri_pass_chunk(cl.la, cl.lb, cl.lc, cl.ld) - 1) / eri_pass_chunk(cl.la, cl.lb, cl.lc, cl.ld)
-                               : 1;
-        return prims * (nc + 8.0 * nherm(cl.la + cl.lb + cl.lc + cl.ld)) * passes * (L.twin ? 1.5 : 1.0);
-    };
-    // spread mode: longest-processing-time-first assignment of the dense launches to the caller's stream and the side
-    // streams (all of them, or all but the task stream).  With the dispatcher on this is the issue order, and the
-    // placement of whatever is left should a poll fail.
-    std::vector<int> lane_of(cc->launches.size(), 0), issue_order;
-    if (spread) {
-        std::vector<std::pair<double, int>> cost(cc->launches.size());
-        for (size_t k = 0; k < cc->launches.size(); ++k) {
-            const EriLaunch& L = cc->launches[k];
-            cost[k] = {L.dense_n > 0 ? entry_cost(L, cc->host.data() + L.dense_off) : 0.0, (int)k};
-        }
-        std::sort(cost.begin(), cost.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-        for (auto& ck : cost) issue_order.push_back(ck.second);
-        double load[ERI_SIDE_MAX + 1] = {};
-        // side stream 2 (st.chain) carries the one-electron chain of this chunk (int1e classes, orthogonaliser, guess: engine.cpp) ahead of
-        // anything queued here -- 1.9 ms for a single fragment, as much as the heaviest class launch: in a batch of one,
-        // three class launches placed on it waited for the guess and the whole stage with them (1.3 of 3.2 ms)
-        if (st.chain < nside && !cost.empty()) load[st.chain + 1] = 1.5 * cost.front().first;
-        for (auto& ck : cost) {
-            int best = 0;
-            for (int q = 1; q <= nside; ++q) {
-                if (task_stream && q == 1) continue;          // side[0]: the tasks and their copy
-                if (load[q] < load[best]) best = q;
-            }
-            load[best] += ck.first;
-            lane_of[ck.second] = best;
-        }
+    // side stream 2 (st.chain) carries the one-electron chain of this chunk (int1e classes, orthogonaliser, guess:
+    // engine.cpp) -- 1.9 ms for a single fragment, as much as the heaviest class launch: in a batch of one, three class
+    // launches placed on it waited for the guess and the whole stage with them (1.3 of 3.2 ms); hence its head start
+    // in the plan.  The tasks and the chain share a stream only when MQC_HIP_ERI_STREAMS leaves a single side stream.
+    std::vector<eri_plan::Entry> entries(cc->launches.size());
+    for (size_t k = 0; k < entries.size(); ++k) {
+        const EriLaunch& L = cc->launches[k];
+        if (L.dense_n > 0) entries[k].dense_cost = launch_cost(topo, L, cc->host.data() + L.dense_off);
+        entries[k].has_tasks = L.sh_n > 0 && L.ntasks > 0;
+        if (entries[k].has_tasks) entries[k].task_cost = launch_cost(topo, L, cc->host.data() + L.sh_off);
     }
-    // the task launches in the order they go on the task stream: heaviest first, by the same cost expression applied
-    // to the shared list's first entry
-    std::vector<int> task_order;
-    if (task_stream) {
-        std::vector<std::pair<double, int>> tc;
-        for (size_t k = 0; k < cc->launches.size(); ++k) {
-            const EriLaunch& L = cc->launches[k];
-            if (L.sh_n > 0 && L.ntasks > 0) tc.push_back({entry_cost(L, cc->host.data() + L.sh_off), (int)k});
-        }
-        std::stable_sort(tc.begin(), tc.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-        for (auto& t : tc) task_order.push_back(t.second);
-    }
-    int li = 0;
-    int placed_on = -1;                                   // the dispatcher's choice for the launch being issued
-    auto dense_stream = [&]() { if (!spread) return s; const int k = placed_on >= 0 ? placed_on : lane_of[li]; return k == 0 ? s : st.side[k - 1]; };
-    // MQC_HIP_ERI_GENERAL=k: classes whose total angular momentum is >= k AND that would take the pass kernels go
-    // through the wave-cooperative LDS kernel instead (no scratch, one wave per quartet and fragment); default: off
-    // default 7: (dd|dp) and (dd|dd); MQC_HIP_ERI_GENERAL=k moves the border (4 = every pass class, 99 = f shells only)
-    static const int gen_from = [] { const char* e = std::getenv("MQC_HIP_ERI_GENERAL"); return e ? std::atoi(e) : 7; }();
-    auto to_general = [&](const Topology::ClassList& c) { return class_is_general(c.la, c.lb, c.lc, c.ld, gen_from); };
-    bool do_dense = true, do_tasks = true;                // which half of a launch entry an issue() call puts out
-    auto task_s = [&]() { return task_stream ? st.side[0] : st.side[rr++ % nside]; };
-#define ERI_CASE(a, b, c, d_)                                                                                         \
-    if (!general && cl.la == a && cl.lb == b && cl.lc == c && cl.ld == d_) {                                          \
-        if (att) {                                                                                                    \
-            if (do_dense) launch_eri_class<a, b, c, d_, true>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream()); \
-            if (do_tasks) launch_eri_class<a, b, c, d_, true>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, task_s()); \
-        } else {                                                                                                      \
-            if (do_dense) launch_eri_class<a, b, c, d_>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream()); \
-            if (do_tasks) launch_eri_class<a, b, c, d_>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, task_s()); \
-        }                                                                                                             \
-    }
-#define TWIN_CASE(a, b, c, d_)                                                                                        \
-    if (cl.la == a && cl.lb == b && cl.lc == c && cl.ld == d_) {                                                      \
-        if (!do_dense) {}                                                                                             \
-        else if (twin_wave && (a) <= 1 && (b) == 0 && (c) == 0 && (d_) == 0)                                          \
-            launch_twin_wave(a, d + L.dense_off, L.dense_n, dense_stream());                                          \
-        else if (att)                                                                                                 \
-            launch_eri_twin_class<a, b, c, d_, true>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream()); \
-        else                                                                                                          \
-            launch_eri_twin_class<a, b, c, d_>(bv, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream()); \
-        if (!do_tasks) {}                                                                                             \
-        else if (att)                                                                                                 \
-            launch_eri_twin_class<a, b, c, d_, true>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, task_s()); \
-        else                                                                                                          \
-            launch_eri_twin_class<a, b, c, d_>(bv, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, task_s()); \
-    }
-    // small batches: the twin (ss|ss) and (ps|ss) entries one wave per (entry, fragment) (eri_twin_wave_kernel)
-    static const int twin_wave_max = [] { const char* e = std::getenv("MQC_HIP_TWIN_WAVE_MAX"); return e ? std::atoi(e) : ERI_TWIN_WAVE_MAX_FRAGMENTS; }();
-    const bool twin_wave = bv.nfrag <= twin_wave_max;
-    auto launch_twin_wave = [&](int la, const int* list, int nq, hipStream_t st_) {
-        if (att && la == 0) launch_eri_twin_wave_class<0, 0, 0, 0, true>(bv, list, nq, Q, thresh, st_);
-        else if (att) launch_eri_twin_wave_class<1, 0, 0, 0, true>(bv, list, nq, Q, thresh, st_);
-        else if (la == 0) launch_eri_twin_wave_class<0, 0, 0, 0>(bv, list, nq, Q, thresh, st_);
-        else launch_eri_twin_wave_class<1, 0, 0, 0>(bv, list, nq, Q, thresh, st_);
-    };
-    auto issue = [&]() {            // launch entry li: its dense half, its task half, or both (do_dense / do_tasks)
-        const EriLaunch& L = cc->launches[li];
-        const auto& cl = topo.classes[L.cls];
-        const bool general = to_general(cl);
-        if (L.twin) {
-            TWIN_CASE(0, 0, 0, 0) TWIN_CASE(1, 0, 0, 0) TWIN_CASE(1, 0, 1, 0) TWIN_CASE(1, 1, 0, 0)
-            TWIN_CASE(1, 1, 1, 0) TWIN_CASE(2, 0, 0, 0) TWIN_CASE(2, 0, 1, 0) TWIN_CASE(2, 1, 0, 0)
-            return;
-        }
-        ERI_CASE(0, 0, 0, 0)
-        ERI_CASE(1, 0, 0, 0) ERI_CASE(1, 0, 1, 0)
-        ERI_CASE(1, 1, 0, 0) ERI_CASE(1, 1, 1, 0) ERI_CASE(1, 1, 1, 1)
-        ERI_CASE(2, 0, 0, 0) ERI_CASE(2, 0, 1, 0) ERI_CASE(2, 0, 1, 1) ERI_CASE(2, 0, 2, 0)
-        ERI_CASE(2, 1, 0, 0) ERI_CASE(2, 1, 1, 0) ERI_CASE(2, 1, 1, 1) ERI_CASE(2, 1, 2, 0) ERI_CASE(2, 1, 2, 1)
-        ERI_CASE(2, 2, 0, 0) ERI_CASE(2, 2, 1, 0) ERI_CASE(2, 2, 1, 1) ERI_CASE(2, 2, 2, 0) ERI_CASE(2, 2, 2, 1)
-        ERI_CASE(2, 2, 2, 2)
-        if (general) {
-            // a class with an f shell (or a d-heavy class routed here): the wave-cooperative LDS kernel
-            if (do_dense) launch_eri_general(bv, cl.la, cl.lb, cl.lc, cl.ld, d + L.dense_off, L.dense_n, nullptr, 0, Q, thresh, dense_stream(), att);
-            if (do_tasks) launch_eri_general(bv, cl.la, cl.lb, cl.lc, cl.ld, d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks, Q, thresh, task_s(), att);
-        }
-    };
+    const eri_plan::Plan plan = eri_plan::plan(entries, nside, st.chain, spread, task_stream);
+    auto stream_of = [&](int lane) { return lane == 0 ? s : st.side[lane - 1]; };
     auto copy_shared = [&](hipStream_t cs) {
         hipLaunchKernelGGL(eri_broadcast_kernel, dim3((unsigned)np, (unsigned)bv.nfrag), dim3(256), 0, cs, bv,
                            d + cc->pair_off, d + cc->pp_off, cc->nap, (const unsigned char*)(d + cc->any_off), d + cc->rep_off);
     };
-    // in spread mode the launches are issued heaviest first (stream order = issue order)
-    std::vector<int> order(cc->launches.size());
-    for (size_t k = 0; k < order.size(); ++k) order[k] = (int)k;
-    if (spread) order = issue_order;
-    if (dynamic) {
-        eri_dispatch::Book book(nside + 1, dispatch_depth);
-        auto stream_of = [&](int q) { return q == 0 ? s : st.side[q - 1]; };
-        for (int q = 1; q <= nside; ++q) book.block(q);
-        const size_t nt = task_order.size();
-        size_t ti = 0;
-        bool copy_issued = false;
-        int ndense = 0, nplaced = 0;
-        long waits = 0;
-        // hipEventQuery answers hipErrorNotReady while work is pending and leaves it as the thread's last error, which
-        // stage_check would report: a not-ready poll is consumed here.  Any other answer stays and ends the dispatching.
-        auto complete = [&](hipEvent_t e) {
-            const hipError_t r = hipEventQuery(e);
-            if (r == hipSuccess) return true;
-            if (r == hipErrorNotReady) (void)hipGetLastError();
-            else dynamic = false;
-            return false;
-        };
-        auto poll = [&]() {
-            for (int q = 0; q <= nside && dynamic; ++q) {
-                if (book.blocked[q]) {
-                    const bool tasks_here = task_stream && q == 1;
-                    if (tasks_here && !copy_issued) continue;
-                    if (complete(tasks_here ? st.disp_copy : st.disp_before[q])) book.unblock(q);
-                    continue;
-                }
-                while (dynamic && book.outstanding[q] > 0 && complete(st.disp_done[q][book.oldest_slot(q)])) book.pop(q);
+    const bool dispatching = dynamic;
+    eri_dispatch::Book book(nside + 1, dispatch_depth);
+    for (int q = 1; q <= nside; ++q) book.block(q);
+    bool copy_issued = false;
+    int rr = 0, ndense = 0, nplaced = 0;
+    long waits = 0;
+    // hipEventQuery answers hipErrorNotReady while work is pending and leaves it as the thread's last error, which
+    // stage_check would report: a not-ready poll is consumed here.  Any other answer stays and ends the dispatching.
+    auto complete = [&](hipEvent_t e) {
+        const hipError_t r = hipEventQuery(e);
+        if (r == hipSuccess) return true;
+        if (r == hipErrorNotReady) (void)hipGetLastError();
+        else dynamic = false;
+        return false;
+    };
+    auto poll = [&]() {
+        for (int q = 0; q <= nside && dynamic; ++q) {
+            if (book.blocked[q]) {
+                const bool tasks_here = task_stream && q == 1;
+                if (tasks_here && !copy_issued) continue;
+                if (complete(tasks_here ? st.disp_copy : st.disp_before[q])) book.unblock(q);
+                continue;
             }
-        };
-        // the task launches and the copy: as without the dispatcher, one after each of the first dense launches, the
-        // copy right behind the last of them -- and all that are left before the host waits for the first time
-        auto next_task = [&]() {
-            if (ti < nt) { li = task_order[ti++]; placed_on = -1; do_dense = false; do_tasks = true; issue(); }
-            if (task_stream && ti == nt && !copy_issued) {
-                copy_shared(st.side[0]);
-                if (hipEventRecord(st.disp_copy, st.side[0]) != hipSuccess) dynamic = false;
-                copy_issued = true;
-            }
-        };
-        if (task_stream && nt == 0) next_task();
-        for (size_t oi = 0; oi < order.size(); ++oi) {
-            const bool has_dense = cc->launches[order[oi]].dense_n > 0;
-            ndense += has_dense ? 1 : 0;
-            int q = -1;
-            while (dynamic && has_dense) {
-                if (hipPeekAtLastError() != hipSuccess) { dynamic = false; break; }      // a launch failed: stage_check's
-                poll();
-                if (!dynamic || (q = book.pick()) >= 0) break;
-                if (task_stream && !copy_issued) { next_task(); continue; }
-                ++waits;
-                std::this_thread::sleep_for(std::chrono::microseconds(20));
-            }
-            if (!dynamic) q = -1;
-            // without the task stream an entry's task launch goes out with its dense half, round-robin over the side streams
-            li = order[oi]; placed_on = q; do_dense = true; do_tasks = !task_stream;
-            issue();
-            if (q >= 0) {
-                const int slot = book.push(q);
-                if (hipEventRecord(st.disp_done[q][slot], stream_of(q)) != hipSuccess) dynamic = false;
-                ++nplaced;
-            }
-            placed_on = -1;
-            if (task_stream) next_task();
+            while (dynamic && book.outstanding[q] > 0 && complete(st.disp_done[q][book.oldest_slot(q)])) book.pop(q);
         }
-        while (task_stream && !copy_issued) next_task();
-        if (dispatch_trace)
-            std::fprintf(stderr, "mqc_hip: eri dispatch: %d of %d dense launches placed over %d streams, depth %d, %ld waits\n", nplaced, ndense,
-                         nside + 1, dispatch_depth, waits);
-    } else if (task_stream) {
-        // dense and task launches alternate in issue order, each heaviest first on its own streams; the copy follows the
-        // last task launch at once, ahead of the dense launches still to be issued
-        const size_t nt = task_order.size();
-        for (size_t oi = 0; oi < order.size() || oi < nt; ++oi) {
-            if (oi < order.size()) { li = order[oi]; do_dense = true; do_tasks = false; issue(); }
-            if (oi < nt) { li = task_order[oi]; do_dense = false; do_tasks = true; issue(); }
-            if (oi + 1 == nt) copy_shared(st.side[0]);
+    };
+    // the lane source: the plan, or the book while the dispatcher is on and the entry has a dense half
+    auto place = [&](int k) -> eri_plan::Placement {
+        if (!dynamic || cc->launches[k].dense_n == 0) return {plan.lane[k], false};
+        if (hipPeekAtLastError() != hipSuccess) dynamic = false;      // a launch failed: stage_check's
+        else poll();
+        if (!dynamic) return {plan.lane[k], false};
+        return {book.pick(), true};
+    };
+    auto idle = [&]() { ++waits; std::this_thread::sleep_for(std::chrono::microseconds(20)); };
+    auto emit = [&](const eri_plan::Item& it) {
+        if (it.kind == eri_plan::COPY) {
+            copy_shared(stream_of(it.lane));
+            if (dispatching && hipEventRecord(st.disp_copy, stream_of(it.lane)) != hipSuccess) dynamic = false;
+            copy_issued = true;
+            return;
         }
-        if (nt == 0) copy_shared(st.side[0]);
-    } else {
-        for (size_t oi = 0; oi < order.size(); ++oi) { li = order[oi]; issue(); }
-    }
-#undef ERI_CASE
-#undef TWIN_CASE
+        const EriLaunch& L = cc->launches[it.entry];
+        if (it.kind == eri_plan::TASKS) { launch_entry(bv, topo, L, d, Q, thresh, att, Half::tasks, stream_of(it.lane)); return; }
+        ndense += L.dense_n > 0 ? 1 : 0;
+        launch_entry(bv, topo, L, d, Q, thresh, att, Half::dense, stream_of(it.lane));
+        // rr advances once per entry, whether or not it has tasks
+        if (it.kind == eri_plan::DENSE_WITH_TASKS) launch_entry(bv, topo, L, d, Q, thresh, att, Half::tasks, st.side[rr++ % nside]);
+        if (it.dispatched) {
+            const int slot = book.push(it.lane);
+            if (hipEventRecord(st.disp_done[it.lane][slot], stream_of(it.lane)) != hipSuccess) dynamic = false;
+            ++nplaced;
+        }
+    };
+    eri_plan::walk(plan, task_stream, dispatching, place, idle, emit);
+    if (dispatching && dispatch_trace)
+        std::fprintf(stderr, "mqc_hip: eri dispatch: %d of %d dense launches placed over %d streams, depth %d, %ld waits\n", nplaced, ndense,
+                     nside + 1, dispatch_depth, waits);
     if (forked) {
         for (int k = 0; k < nside; ++k) {
             (void)hipEventRecord(st.join[k], st.side[k]);
@@ -1027,13 +948,7 @@ void launch_jk_direct(const BatchView& bv, const Topology& topo, double thresh, 
         // and the f classes: LDS kernel
         const bool general = cl.la > CLASS_LMAX || ncart(cl.la) * ncart(cl.lb) * ncart(cl.lc) * ncart(cl.ld) > ERI_UNROLL_LIMIT;
         if (general) launch_digest_general(bv, cl.la, cl.lb, cl.lc, cl.ld, d_list + off, (int)cl.quartets.size() / 4, Q, Dmax, thresh, Jt, Kt, oa, s);
-        DIG_CASE(0, 0, 0, 0)
-        DIG_CASE(1, 0, 0, 0) DIG_CASE(1, 0, 1, 0)
-        DIG_CASE(1, 1, 0, 0) DIG_CASE(1, 1, 1, 0) DIG_CASE(1, 1, 1, 1)
-        DIG_CASE(2, 0, 0, 0) DIG_CASE(2, 0, 1, 0) DIG_CASE(2, 0, 1, 1) DIG_CASE(2, 0, 2, 0)
-        DIG_CASE(2, 1, 0, 0) DIG_CASE(2, 1, 1, 0) DIG_CASE(2, 1, 1, 1) DIG_CASE(2, 1, 2, 0) DIG_CASE(2, 1, 2, 1)
-        DIG_CASE(2, 2, 0, 0) DIG_CASE(2, 2, 1, 0) DIG_CASE(2, 2, 1, 1) DIG_CASE(2, 2, 2, 0) DIG_CASE(2, 2, 2, 1)
-        DIG_CASE(2, 2, 2, 2)
+        ERI_CLASSES(DIG_CASE)
         off += cl.quartets.size();
     }
     hipLaunchKernelGGL(symmetrise_jk_kernel, dim3((n * n + 255) / 256, bv.nfrag), dim3(256), 0, s, bv, Jt, Kt);

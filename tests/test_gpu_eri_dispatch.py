@@ -111,6 +111,40 @@ def test_dispatched_batch_matches_static_unshared(case, depth, probe_dir):
     check_batch(cc.SPD, frags, Jd, sample, "dispatched %s" % case)
 
 
+UNSPREAD = {"MQC_HIP_ERI_SPREAD_MAX": "0", "MQC_HIP_ERI_DISPATCH_TRACE": "1"}
+ONE_SIDE_STREAM = {**DISPATCH, "MQC_HIP_ERI_STREAMS": "1"}
+
+
+@pytest.mark.parametrize("name, env", [("unspread", UNSPREAD), ("one_side_stream", ONE_SIDE_STREAM)])
+def test_shared_batch_on_the_narrow_paths(name, env, probe_dir):
+    """repeat:2 (16 fragments, the smallest batch that gets a share plan) on the two paths no other test takes: shared
+    blocks without spread (every dense launch on the caller's stream, task launches round-robin over the side streams,
+    the copy after the join), and a single side stream with the task stream and the dispatcher on, where the task
+    stream and the chain stream are one and the dispatcher has two streams.  Every fragment's J against the child
+    without sharing and without the dispatcher, bound UNSHARED_BOUND; the oracle on oracle_sample's fragments."""
+    case = "repeat:2"
+    frags = batch_of(case)
+    m = len(frags)
+    assert m == batch_size(2) == 16
+    Ju = reference(case, probe_dir)
+    Jn, traces = coulomb_in_child(case, str(probe_dir / (name + ".npy")), env)
+    print("%s: dispatcher (placed, dense launches, streams, depth, waits): %s" % (name, traces))
+    if name == "unspread":
+        assert traces == [], "the dispatcher ran on an unspread batch"
+    else:
+        assert len(traces) == 1, "one launch_eri call, one dispatching call expected"
+        placed, dense, streams, _depth, _waits = traces[0]
+        assert placed == dense, "dynamic placement ended early: a poll failed"
+        assert streams == 2
+    assert Jn.shape == Ju.shape == (m, 40, 40) and not np.any(np.isnan(Jn))
+    per_fragment = np.max(np.abs(Jn - Ju), axis=(1, 2))
+    assert per_fragment.shape == (m,)                  # no fragment left uncompared
+    worst = int(np.argmax(per_fragment))
+    print("%s, %d fragments, against static unshared: worst |dJ| %.3e (fragment %d), bound %.3e" % (name, m, per_fragment[worst], worst, UNSHARED_BOUND))
+    assert per_fragment[worst] <= UNSHARED_BOUND, (name, worst, per_fragment[worst])
+    check_batch(cc.SPD, frags, Jn, oracle_sample(2), "%s %s" % (name, case))
+
+
 _RSH_CHILD = r"""
 import sys
 import numpy as np
