@@ -99,7 +99,7 @@ module mqc_hip_c
    public :: mqc_hip_backend_available, mqc_hip_context_get, mqc_hip_finalize, mqc_hip_last_error, &
              mqc_hip_abi_version, mqc_hip_default_options, mqc_hip_scf_run, mqc_hip_scf_run_batch, &
              mqc_hip_coulomb_batch, mqc_hip_esp_batch, mqc_hip_scf_gradient_embedded_batch, &
-             mqc_hip_scf_run_batch_restart
+             mqc_hip_scf_run_batch_restart, mqc_hip_rimp2_batch
 
    interface
       function mqc_hip_backend_available() bind(C, name="mqc_hip_backend_available") result(r)
@@ -185,6 +185,26 @@ module mqc_hip_c
          type(mqc_hip_scf_result_t), intent(inout) :: res(*)
          type(c_ptr), value :: initial_density
          type(c_ptr), value :: spin_densities_out
+         integer(c_int) :: r
+      end function
+      !! mqc_hip_scf_run_batch of a density-fitted closed-shell Hartree-Fock run followed, per converged fragment, by its
+      !! RI-MP2 correlation energy: e_os(i), e_ss(i) (opposite-spin and same-spin parts, E_corr = e_os + e_ss) and
+      !! mp2_done(i) = 1; fragments whose SCF failed get zeros.  frozen_core /= 0 freezes the atoms' core orbitals.
+      function mqc_hip_rimp2_batch(ctx, n, mols, orbitals, auxes, opts, res, frozen_core, e_os, e_ss, mp2_done) &
+         bind(C, name="mqc_hip_rimp2_batch") result(r)
+         import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double, mqc_hip_molecule_t, mqc_hip_basis_t, mqc_hip_scf_options_t, &
+            mqc_hip_scf_result_t
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: n
+         type(mqc_hip_molecule_t), intent(in) :: mols(*)
+         type(mqc_hip_basis_t), intent(in) :: orbitals(*)
+         type(c_ptr), value :: auxes
+         type(mqc_hip_scf_options_t), intent(in) :: opts
+         type(mqc_hip_scf_result_t), intent(inout) :: res(*)
+         integer(c_int32_t), value :: frozen_core
+         real(c_double), intent(inout) :: e_os(*)
+         real(c_double), intent(inout) :: e_ss(*)
+         integer(c_int32_t), intent(inout) :: mp2_done(*)
          integer(c_int) :: r
       end function
       !! J[D] for many fragments of one topology; n_source_atoms > 0: only the (leading | source) block (local_coulomb)

@@ -301,6 +301,28 @@ int mqc_hip_scf_run_batch_restart(mqc_hip_context *ctx, int64_t n_fragments, con
                                   const double *const *initial_density /* NULL, or [n_fragments]; entry i NULL or -> density */,
                                   double *const *spin_densities_out /* NULL, or [n_fragments]; entry i NULL or -> [2][n_ao*n_ao] */);
 
+/* RI-MP2 correlation energies on top of a density-fitted closed-shell Hartree-Fock batch.  The SCF part IS
+ * mqc_hip_scf_run_batch -- grouping by topology, chunking under MQC_HIP_HBM_BUDGET_GB, deferred groups, per-fragment
+ * failures in results[i], results[i].e_total the SCF energy -- and after the SCF loop of a chunk, while its fitted
+ * tensor B^P_(mu nu), orbitals and orbital energies are still on the device, the stage of kern_mp2.hip forms
+ *     (ia|jb) = sum_P B^P_ia B^P_jb,   e_os = sum (ia|jb)^2 / D,   e_ss = sum (ia|jb) [(ia|jb) - (ib|ja)] / D,
+ *     D = e_i + e_j - e_a - e_b,       E_corr = e_os + e_ss        (SCS-MP2: 6/5 e_os + 1/3 e_ss)
+ * over the active occupied (i, j) and the virtual (a, b) orbitals of every fragment whose SCF converged:
+ *     mp2_done[i] = 1 and e_os[i], e_ss[i] written;  every other fragment gets mp2_done[i] = 0, e_os[i] = e_ss[i] = 0.
+ * frozen_core != 0 freezes, per atom, 0 orbitals for Z <= 2, 1 for Z = 3-10, 5 for Z = 11-18, 9 for Z = 19-36 (ghost
+ * atoms none): the lowest orbitals of the fragment stay out of the sums.  Point charges and h_extra are legal: the
+ * orbitals carry the field.
+ * MQC_HIP_ERR_UNSUPPORTED (the refused fragments run no SCF): no density fitting (RI-MP2 uses the fitted tensor of a
+ * density-fitted SCF), a functional (double hybrids are not built), an unrestricted run (opts->unrestricted, multiplicity
+ * != 1, an odd electron count), want_gradient.  MQC_HIP_ERR_VALIDATION: a NULL output array, a frozen core that leaves no
+ * active occupied orbital.  Whatever the density-fitted SCF refuses (n_ao > 140, g shells) keeps its own refusal.
+ * (Added without an ABI bump: no struct changed.) */
+int mqc_hip_rimp2_batch(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip_molecule_t *mols,
+                        const mqc_hip_basis_t *orbitals, const mqc_hip_basis_t *auxes,
+                        const mqc_hip_scf_options_t *opts, mqc_hip_scf_result_t *results,
+                        int32_t frozen_core,
+                        double *e_os /* [n] */, double *e_ss /* [n] */, int32_t *mp2_done /* [n] */);
+
 int mqc_hip_syev(mqc_hip_context *ctx, int32_t n, const double *A, double *w, double *V);
 /* DIIS coefficients from an age-ordered overlap matrix, the device routine's algorithm
  * (diis_coefficients/solve_diis, src/methods/mqc_diis.f90:164-273) */

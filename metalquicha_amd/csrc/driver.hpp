@@ -64,6 +64,11 @@ struct Batch {
     // unrestricted run's spin densities go (null entry: nowhere); empty when the call brought none
     std::vector<const double*> d0;
     std::vector<double*> spin_out;
+    // mqc_hip_rimp2_batch only (mp2_frozen >= 0: the frozen orbitals of this topology): where each fragment's
+    // opposite-spin and same-spin correlation energies and its done flag go
+    int mp2_frozen = -1;
+    std::vector<double*> mp2_os, mp2_ss;
+    std::vector<int32_t*> mp2_done;
     TopologyDev td{}, tdx{};
     GridDev grid;
     Stats stats;

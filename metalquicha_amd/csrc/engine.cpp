@@ -35,6 +35,10 @@ static DevicePool g_grad_pool[2];
 bool launch_pc_gradient(const BatchView& bv, const Topology& topo, const double* Dtot, double* d_grad, double* d_pcgrad, double* d_rec,
                         hipStream_t s, std::string& err);
 size_t gradpc_record_doubles(const Topology& topo);
+// kern_mp2.hip: RI-MP2 pair energies of a converged density-fitted chunk, [nfrag][2] = e_os, e_ss copied to h_out on s
+// (the caller joins the stream); device bytes per fragment of the stage
+bool launch_rimp2(const BatchView& bv, int n_frozen, double* h_out, hipStream_t s, std::string& err);
+size_t rimp2_fragment_bytes(int n, int nocc, int naux, int n_frozen);
 
 int stage_check(const char* stage)
 {
@@ -694,7 +698,7 @@ static void embedding_and_mulliken(const Topology& topo, const double* D, const 
 
 // what a chunk's results are made of, read back once after its SCF loop
 struct ChunkOut {
-    std::vector<double> scal, eps, epsb, dip, grad, pcgrad;
+    std::vector<double> scal, eps, epsb, dip, grad, pcgrad, mp2;
     std::vector<double> D, U, S;      // total density, embedding operator, overlap: only where a caller reads them
     std::vector<double> Da, Db;       // spin densities of an unrestricted chunk, where a caller asked for them
     std::vector<int> ist;
@@ -762,6 +766,12 @@ static int write_result(const BatchPlan& plan, Batch& b, const Job& job, const C
     else if (!std::isfinite(r->e_total)) fill_error(r, "SCF produced a non-finite energy");
     else if (!conv && !b.opts.allow_crap_scf)
         fill_error(r, "SCF did not converge in " + std::to_string(r->iterations) + " iterations");
+    if (b.mp2_frozen >= 0 && conv && !r->has_error) {
+        // the correlation energy belongs to converged orbitals only; everything else keeps the entry's zeros
+        *b.mp2_os[job.start + f] = o.mp2[2 * f];
+        *b.mp2_ss[job.start + f] = o.mp2[2 * f + 1];
+        *b.mp2_done[job.start + f] = 1;
+    }
     b.stats.scf_iterations_total += r->iterations;
     return MQC_HIP_OK;
 }
@@ -811,6 +821,14 @@ static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& j
         }
         o.grad.resize((size_t)nf * topo.natoms * 3);
         HIP_CHECK_RET(hipMemcpyAsync(o.grad.data(), d_grad, sizeof(double) * o.grad.size(), hipMemcpyDeviceToHost, s));
+    }
+    // ---- RI-MP2 (mqc_hip_rimp2_batch): the fitted tensor, the orbitals and their energies of this chunk are still in place
+    if (b.mp2_frozen >= 0) {
+        o.mp2.assign((size_t)nf * 2, 0.0);
+        std::string merr;
+        if (!launch_rimp2(bv, b.mp2_frozen, o.mp2.data(), s, merr)) return fail(MQC_HIP_ERR_DEVICE, merr);
+        int mrc = stage_check("RI-MP2");
+        if (mrc != MQC_HIP_OK) return mrc;
     }
     launch_dipole(bv, topo, s);
     if (plan.uhf) {
@@ -871,6 +889,9 @@ struct Work {
     std::vector<double*> pcg;            // mqc_hip_scf_gradient_embedded_batch only: the site gradients (or null), else empty
     std::vector<const double*> d0;       // mqc_hip_scf_run_batch_restart only: starting densities ...
     std::vector<double*> spin;           // ... and the spin densities' destinations; empty when the call brought none
+    int mp2_frozen = -1;                 // mqc_hip_rimp2_batch only: frozen orbitals of the topology (>= 0) ...
+    std::vector<double*> mp2_os, mp2_ss; // ... and where the fragments' components and done flags go
+    std::vector<int32_t*> mp2_done;
     std::shared_ptr<AtomicGuess> guess;
     // deferred small groups (scf_run_batch_impl): the largest group's batch opens the gate, the others wait at it
     GroupGate* opens = nullptr;
@@ -912,7 +933,9 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
             if (!w.pcg.empty()) b.pcgrad.push_back(w.pcg[k.second]);      // the same permutation as the results
             if (!w.d0.empty()) b.d0.push_back(w.d0[k.second]);
             if (!w.spin.empty()) b.spin_out.push_back(w.spin[k.second]);
+            if (w.mp2_frozen >= 0) { b.mp2_os.push_back(w.mp2_os[k.second]); b.mp2_ss.push_back(w.mp2_ss[k.second]); b.mp2_done.push_back(w.mp2_done[k.second]); }
         }
+        b.mp2_frozen = w.mp2_frozen;
     }
     std::string msg;
     int rc = plan_batch(opts, topo, ntot, plan, msg);
@@ -946,6 +969,8 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
     size_t per_frag = fragment_bytes(plan);
     // the charges' part of an embedded gradient: Hermite records and the sites' gradient, from the gradient pool
     if (opts.want_gradient && plan.npc > 0) per_frag += sizeof(double) * (gradpc_record_doubles(topo) + 3 * (size_t)plan.npc);
+    // RI-MP2: the transformed tensor and the pair partials, from the stage's own pool
+    if (w.mp2_frozen >= 0) per_frag += rimp2_fragment_bytes(plan.n, plan.nocc, plan.naux, w.mp2_frozen);
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
     free_b += ctx->pool_main.capacity() + ctx->pool_eri.capacity() + ctx->pool_df.capacity() + ctx->pool_gridw.capacity()
@@ -1316,7 +1341,24 @@ struct BatchExtras {            // what the plain batch entry does not have
     double* const* site_gradients = nullptr;        // mqc_hip_scf_gradient_embedded_batch
     const double* const* initial_density = nullptr; // mqc_hip_scf_run_batch_restart (either may be NULL)
     double* const* spin_densities_out = nullptr;
+    bool mp2 = false;                               // mqc_hip_rimp2_batch: [n] arrays of the caller
+    bool frozen_core = false;
+    double *e_os = nullptr, *e_ss = nullptr;
+    int32_t* mp2_done = nullptr;
 };
+
+// frozen-core orbitals of a topology: per real atom 0 for Z <= 2, 1 for Z = 3-10, 5 for Z = 11-18, 9 for Z = 19-36
+// (ghost atoms carry basis functions and no core)
+static int frozen_core_orbitals(const Topology& topo)
+{
+    int nfz = 0;
+    for (int a = 0; a < topo.natoms; ++a) {
+        if (topo.zeff[a] == 0.0) continue;
+        const int z = topo.Z[a];
+        nfz += z <= 2 ? 0 : z <= 10 ? 1 : z <= 18 ? 5 : 9;
+    }
+    return nfz;
+}
 
 // the body of the batch entries
 static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,
@@ -1396,6 +1438,26 @@ static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip
                 continue;
             }
         }
+        if (extras.mp2) {
+            // closed shells only, and at least one active occupied orbital: a refused group runs no SCF
+            std::string why;
+            int code = MQC_HIP_OK;
+            const int nocc = w.topo->nelec / 2;
+            w.mp2_frozen = extras.frozen_core ? frozen_core_orbitals(*w.topo) : 0;
+            if (runs_unrestricted(*opts, w.topo->multiplicity, w.topo->nelec)) {
+                why = "RI-MP2 is built for closed-shell restricted references: unrestricted MP2 (open shells, multiplicity != 1, odd electron counts) is not built";
+                code = MQC_HIP_ERR_UNSUPPORTED;
+            } else if (w.mp2_frozen >= nocc) {
+                why = "RI-MP2: the frozen core (" + std::to_string(w.mp2_frozen) + " orbitals) leaves no active occupied orbital of " + std::to_string(nocc);
+                code = MQC_HIP_ERR_VALIDATION;
+            }
+            if (code != MQC_HIP_OK) {
+                for (auto i : idx) fill_error(&results[i], why);
+                set_error(why);
+                worst = code;
+                continue;
+            }
+        }
         // supplied densities: their size follows from the run's spin treatment; one with a non-finite entry fails its own
         // fragment and nothing else
         std::vector<int64_t> run_idx;
@@ -1433,6 +1495,7 @@ static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip
             if (extras.embedded_entry) w.pcg.push_back(extras.site_gradients ? extras.site_gradients[i] : nullptr);
             if (any_d0) w.d0.push_back(extras.initial_density[i]);
             if (extras.spin_densities_out) w.spin.push_back(extras.spin_densities_out[i]);
+            if (extras.mp2) { w.mp2_os.push_back(extras.e_os + i); w.mp2_ss.push_back(extras.e_ss + i); w.mp2_done.push_back(extras.mp2_done + i); }
         }
         work.push_back(std::move(w));
     }
@@ -1532,6 +1595,32 @@ int mqc_hip_scf_gradient_embedded_batch(mqc_hip_context* ctx, int64_t nfrag, con
     extras.embedded_entry = true;
     extras.site_gradients = point_charge_gradients;
     return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, &o, results, extras);
+}
+
+int mqc_hip_rimp2_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,
+                        const mqc_hip_basis_t* orbitals, const mqc_hip_basis_t* auxes,
+                        const mqc_hip_scf_options_t* opts, mqc_hip_scf_result_t* results,
+                        int32_t frozen_core, double* e_os, double* e_ss, int32_t* mp2_done)
+{
+    if (!opts) return fail(MQC_HIP_ERR_VALIDATION, "null argument");
+    if (nfrag > 0 && (!e_os || !e_ss || !mp2_done)) return fail(MQC_HIP_ERR_VALIDATION, "RI-MP2: e_os, e_ss and mp2_done must not be NULL");
+    for (int64_t i = 0; i < nfrag; ++i) { e_os[i] = 0.0; e_ss[i] = 0.0; mp2_done[i] = 0; }
+    // what the whole call refuses: no fragment runs an SCF
+    std::string why;
+    if (!opts->density_fitting || !auxes) why = "RI-MP2 uses the fitted tensor of a density-fitted SCF: set density_fitting and pass an auxiliary basis";
+    else if (opts->functional[0] != '\0') why = "RI-MP2 on a Kohn-Sham reference: double hybrids are not built";
+    else if (opts->unrestricted) why = "RI-MP2 is built for closed-shell restricted references: unrestricted MP2 is not built";
+    else if (opts->want_gradient) why = "analytic RI-MP2 gradients are not built (energies only)";
+    if (!why.empty()) {
+        if (results)
+            for (int64_t i = 0; i < nfrag; ++i) { init_result(&results[i]); fill_error(&results[i], why); }
+        return fail(MQC_HIP_ERR_UNSUPPORTED, why);
+    }
+    BatchExtras extras;
+    extras.mp2 = true;
+    extras.frozen_core = frozen_core != 0;
+    extras.e_os = e_os; extras.e_ss = e_ss; extras.mp2_done = mp2_done;
+    return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, opts, results, extras);
 }
 
 int mqc_hip_scf_run(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* orbital,

@@ -13,6 +13,7 @@ kept so that bench.py and the tests exercise the engine exactly the way metalqui
                            (backends/libcint/mqc_libcint_fmo.f90:1806-1819); SURVEY.md 8e
   run_mbe                  do_fragment_work over the owned terms (one engine batch), energies
                            returned in a zero-padded vector ready for ONE all-reduce
+  run_mbe_rimp2            the same with RI-MP2 fragment energies (SCF + correlation per term, plain or SCS)
 
 Nothing here touches the GPU; the SCFs are run by methods.run_hip_scf_batch.
 """
@@ -301,6 +302,10 @@ class MbeRun:
     errors: List[str]
     gradient: Optional[np.ndarray] = None      # (n_atoms, 3) weighted sum of the owned fragments' gradients (zero-padded share)
     densities: Optional[Dict[Tuple[int, ...], np.ndarray]] = None   # run_mbe with restart / initial_densities: converged total density per owned term
+    # run_mbe_rimp2 only: per term the opposite-spin and same-spin parts of the correlation energy as they sit in `energies`
+    # (scaled by `scs` where given), zero for terms this rank does not own
+    correlation_os: Optional[np.ndarray] = None
+    correlation_ss: Optional[np.ndarray] = None
 
 
 def _group_layout(system: FragmentedSystem, term_list: Sequence[Tuple[int, ...]]):
@@ -403,6 +408,43 @@ def run_mbe(system: FragmentedSystem, settings: ScfSettings, level: int = 2,
             msg = bytes(rec["message"][k]).split(b"\0", 1)[0].decode(errors="replace")
             errors.append("term %s: %s" % (terms[tix[k]], msg))
     return MbeRun(terms, energies, iters, owned, errors, gradient_total)
+
+
+def run_mbe_rimp2(system: FragmentedSystem, settings: ScfSettings, level: int = 2,
+                  cutoffs: Optional[Dict[int, float]] = None, rank: int = 0, world: int = 1,
+                  terms: Optional[List[Tuple[int, ...]]] = None, costs: Optional[Sequence[float]] = None,
+                  frozen_core: bool = True, scs: Optional[Tuple[float, float]] = None,
+                  solver: Optional[Callable] = None) -> MbeRun:
+    """run_mbe with RI-MP2 fragment energies: the owned terms in one mqc_hip_rimp2_batch call (density-fitted
+    closed-shell Hartree-Fock, then the correlation energy of every converged fragment), `energies` = SCF + correlation
+    per term, ready for compute_mbe and the one all-reduce; `correlation_os` / `correlation_ss` hold the two parts per term.
+    `scs = (c_os, c_ss)` scales the parts before the sum -- (6/5, 1/3) is SCS-MP2 -- and None is plain MP2.  A term whose
+    SCF failed or did not converge has no correlation energy: it goes to `errors` and keeps zeros.
+    `solver(groups) -> (records, e_os, e_ss, mp2_done)` replaces methods.run_hip_rimp2_groups (host tests)."""
+    from .methods import run_hip_rimp2_groups
+    solver = solver or (lambda groups: run_hip_rimp2_groups(settings, groups, frozen_core))
+    c_os, c_ss = (1.0, 1.0) if scs is None else (float(scs[0]), float(scs[1]))
+    terms = terms if terms is not None else generate_mbe_term_list(system, level, cutoffs)
+    owned = partition_terms(len(terms), rank, world) if costs is None else partition_terms_lpt(costs, rank, world)
+    groups, positions = build_fragment_groups(system, [terms[i] for i in owned])
+    owned_arr = np.asarray(owned)
+    energies = np.zeros(len(terms)); e_os = np.zeros(len(terms)); e_ss = np.zeros(len(terms))
+    iters = np.zeros(len(terms), dtype=np.int64)
+    errors: List[str] = []
+    recs, os_g, ss_g, done_g = solver(groups)
+    for pos, rec, os_, ss_, dn in zip(positions, recs, os_g, ss_g, done_g):
+        tix = owned_arr[pos]
+        scf_ok = rec["has_error"] == 0
+        ok = scf_ok & (np.asarray(dn) != 0)
+        e_os[tix[ok]] = c_os * np.asarray(os_)[ok]
+        e_ss[tix[ok]] = c_ss * np.asarray(ss_)[ok]
+        energies[tix[ok]] = rec["e_total"][ok] + e_os[tix[ok]] + e_ss[tix[ok]]
+        iters[tix[ok]] = rec["iterations"][ok]
+        for k in np.nonzero(~ok)[0]:
+            msg = bytes(rec["message"][k]).split(b"\0", 1)[0].decode(errors="replace") if not scf_ok[k] else \
+                "no RI-MP2 energy: the SCF did not converge"
+            errors.append("term %s: %s" % (terms[tix[k]], msg))
+    return MbeRun(terms, energies, iters, owned, errors, None, None, e_os, e_ss)
 
 
 def _run_mbe_restart(system: FragmentedSystem, settings: ScfSettings, terms: List[Tuple[int, ...]], owned: np.ndarray,

@@ -12,6 +12,8 @@
   run_hip_embedded_gradients <- (no counterpart) gradients of fragments in point charges, on atoms and on the charges
                          (mqc_hip_scf_gradient_embedded_batch)
   run_hip_esp         <- (no counterpart) the potential of converged densities at arbitrary points (mqc_hip_esp_batch)
+  run_hip_rimp2_batch, run_hip_rimp2_groups <- (no counterpart: the reference's MP2 is conventional) density-fitted RHF
+                         and the RI-MP2 correlation energy of every converged fragment (mqc_hip_rimp2_batch)
 
 Same names, argument meaning and error behaviour; the numerics all happen in libmqc_hip.so.
 """
@@ -102,15 +104,22 @@ class ScfSettings:
 @dataclass
 class EnergyT:
     scf: float = 0.0
+    mp2_os: float = 0.0        # opposite-spin and same-spin parts of the RI-MP2 correlation energy (run_hip_rimp2_batch)
+    mp2_ss: float = 0.0
+
+    @property
+    def mp2(self) -> float:
+        return self.mp2_os + self.mp2_ss
 
     def total(self) -> float:
-        return self.scf
+        return self.scf + self.mp2
 
 
 @dataclass
 class CalculationResult:
     energy: EnergyT = field(default_factory=EnergyT)
     has_energy: bool = False
+    has_mp2: bool = False
     scf_status: int = SCF_NOT_RUN
     scf_iterations: int = 0
     homo: float = 0.0
@@ -349,13 +358,14 @@ class FragmentGroup:
     point_charge_xyz: Optional[np.ndarray] = None   # (m, n_pc, 3) Bohr: the embedding field of an FMO / EE-MBE fragment
     point_charges: Optional[np.ndarray] = None      # (m, n_pc)
     h_extra: Optional[np.ndarray] = None            # (m, n_ao, n_ao): a further one-electron operator added to H (run_libcint_rhf's h_extra)
+    basis_set: Optional[str] = None                 # this group's orbital basis where it is not settings.basis_set (one call, several bases)
 
 
 def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], want_gradient: bool = False,
                        gradients_out: Optional[list] = None, extras: Sequence[str] = (),
                        extras_out: Optional[list] = None, site_gradients_out: Optional[list] = None,
                        status_out: Optional[list] = None, initial_densities: Optional[Sequence] = None,
-                       spin_densities_out: Optional[list] = None) -> List[np.ndarray]:
+                       spin_densities_out: Optional[list] = None, rimp2: Optional[dict] = None) -> List[np.ndarray]:
     """All fragments of all groups in ONE mqc_hip_scf_run_batch call; returns, per group, a structured array
     viewing the engine's result records (fields of capi.ScfResult: e_total, iterations, has_error, message ...).
 
@@ -376,17 +386,24 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
     (2, n_ao, n_ao), alpha and beta, when it runs unrestricted (runs_unrestricted: forced, multiplicity != 1 or an odd
     electron count).  Any finite density of the right size is legal: the engine projects it onto an SCF state of the new
     geometry.  `spin_densities_out` (a list) receives one (m, 2, n_ao, n_ao) array per group, written for the fragments
-    that ran unrestricted (zeros elsewhere)."""
+    that ran unrestricted (zeros elsewhere).
+
+    `rimp2` (a dict, see run_hip_rimp2_groups) sends the batch through mqc_hip_rimp2_batch."""
     embedded = site_gradients_out is not None
     restart = initial_densities is not None or spin_densities_out is not None
     if restart and embedded:
         raise ValueError("starting densities and the embedded-gradient entry do not combine")
+    if rimp2 is not None and (restart or embedded):
+        raise ValueError("RI-MP2 combines with neither starting densities nor the embedded-gradient entry")
     if initial_densities is not None and len(initial_densities) != len(groups):
         raise ValueError("initial_densities must hold one entry per group")
     want_gradient = bool(want_gradient) or embedded
     sizes = [int(g.xyz.shape[0]) for g in groups]
     n = int(sum(sizes))
     if n == 0:
+        if rimp2 is not None:
+            rimp2.update(e_os=[np.zeros(0) for _ in groups], e_ss=[np.zeros(0) for _ in groups],
+                         mp2_done=[np.zeros(0, dtype=np.int32) for _ in groups])
         return [np.zeros(0, dtype=_RES_DTYPE) for _ in groups]
     lib = capi.load_library()
     ctx = capi.get_context(settings.device_rank)
@@ -414,7 +431,7 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
             nelec = zsum - charge                                        # compute_nelec, :73-83
         else:
             nelec = np.asarray(g.nelec, dtype=np.int32)
-        fb = _flat_basis_z(settings.basis_set, z)
+        fb = _flat_basis_z(g.basis_set or settings.basis_set, z)
         keep += [z, ghost, xyz, fb]
         mols["n_atoms"][sl] = na
         mols["atomic_numbers"][sl] = z.ctypes.data
@@ -464,7 +481,7 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
         lo = 0
         for g, m in zip(groups, sizes):
             z = np.ascontiguousarray(g.element_numbers, dtype=np.int32)
-            nao = _flat_basis_z(settings.basis_set, z).nao
+            nao = _flat_basis_z(g.basis_set or settings.basis_set, z).nao
             got = {}
             for name in extras:
                 if name not in ("density", "embedding_matrix", "mulliken_charges"):
@@ -484,7 +501,7 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
         lo = 0
         for gi, (g, m) in enumerate(zip(groups, sizes)):
             z = np.ascontiguousarray(g.element_numbers, dtype=np.int32)
-            nao = _flat_basis_z(settings.basis_set, z).nao
+            nao = _flat_basis_z(g.basis_set or settings.basis_set, z).nao
             entries = None if initial_densities is None else initial_densities[gi]
             if entries is not None and m:
                 if len(entries) != m:
@@ -528,6 +545,15 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
                                                      bass.ctypes.data_as(C.POINTER(capi.Basis)),
                                                      auxs.ctypes.data_as(C.POINTER(capi.Basis)) if df else None, C.byref(opts), res,
                                                      site_ptr.ctypes.data_as(C.POINTER(capi.c_double_p)))
+    elif rimp2 is not None:
+        e_os, e_ss, done = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
+        rc = lib.mqc_hip_rimp2_batch(ctx, n, mols.ctypes.data_as(C.POINTER(capi.Molecule)),
+                                     bass.ctypes.data_as(C.POINTER(capi.Basis)),
+                                     auxs.ctypes.data_as(C.POINTER(capi.Basis)) if df else None, C.byref(opts), res,
+                                     1 if rimp2.get("frozen_core", True) else 0, capi.dptr(e_os), capi.dptr(e_ss),
+                                     done.ctypes.data_as(capi.c_int32_p))
+        cuts = np.cumsum(sizes)[:-1]
+        rimp2.update(e_os=np.split(e_os, cuts), e_ss=np.split(e_ss, cuts), mp2_done=np.split(done, cuts))
     else:
         rc = lib.mqc_hip_scf_run_batch(ctx, n, mols.ctypes.data_as(C.POINTER(capi.Molecule)),
                                        bass.ctypes.data_as(C.POINTER(capi.Basis)),
@@ -607,6 +633,69 @@ def run_hip_esp(settings: ScfSettings, group: FragmentGroup, densities, points, 
     return out
 
 
+def _groups_of(fragments: Sequence[PhysicalFragment]):
+    """Fragments sorted into FragmentGroups by element sequence and ghost flags -> (groups, index), index[g][k] the
+    position in `fragments` of the k-th fragment of group g."""
+    by_key = {}
+    for i, f in enumerate(fragments):
+        key = (f.element_numbers.tobytes(), None if f.ghost is None else f.ghost.tobytes())
+        by_key.setdefault(key, []).append(i)
+    groups, index = [], []
+    for idx in by_key.values():
+        f0 = fragments[idx[0]]
+        groups.append(FragmentGroup(f0.element_numbers, np.stack([fragments[i].coordinates.T for i in idx]),
+                                    np.array([fragments[i].charge for i in idx], dtype=np.int32),
+                                    np.array([fragments[i].multiplicity for i in idx], dtype=np.int32),
+                                    f0.ghost, np.array([fragments[i].nelec for i in idx], dtype=np.int32)))
+        index.append(idx)
+    return groups, index
+
+
+def frozen_core_count(element_numbers, ghost=None) -> int:
+    """Frozen-core orbitals of a fragment, the engine's table (mqc_hip_rimp2_batch): per atom 0 for Z <= 2, 1 for
+    Z = 3-10, 5 for Z = 11-18, 9 for Z = 19-36; ghost atoms freeze none.  Water: 1; a water dimer: 2; H2: 0."""
+    z = np.asarray(element_numbers, dtype=np.int64).reshape(-1)
+    if np.any(z > 36):
+        raise ValueError("frozen_core_count: the table ends at Z = 36")
+    per_atom = np.where(z <= 2, 0, np.where(z <= 10, 1, np.where(z <= 18, 5, 9)))
+    if ghost is not None:
+        per_atom = np.where(np.asarray(ghost, dtype=bool).reshape(-1), 0, per_atom)
+    return int(per_atom.sum())
+
+
+def run_hip_rimp2_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], frozen_core: bool = True,
+                         extras: Sequence[str] = (), extras_out: Optional[list] = None, status_out: Optional[list] = None):
+    """All fragments of all groups in ONE mqc_hip_rimp2_batch call: the density-fitted closed-shell SCF of
+    run_hip_scf_groups followed, per converged fragment, by its RI-MP2 correlation energy.
+    -> (records, e_os, e_ss, mp2_done): per group the result records (e_total stays the SCF energy) and three arrays
+    (m,): the opposite-spin and same-spin parts (E_corr = e_os + e_ss) and 1 where they were formed -- 0, with zeros
+    for both parts, where the SCF failed or did not converge.  `frozen_core` leaves frozen_core_count(...) lowest
+    orbitals of each fragment out of the sums.  Refusals (no density fitting, a functional, open shells) arrive in the
+    records' messages, the call's status in `status_out`."""
+    box = {"frozen_core": bool(frozen_core)}
+    rec = run_hip_scf_groups(settings, groups, extras=extras, extras_out=extras_out, status_out=status_out, rimp2=box)
+    return rec, box["e_os"], box["e_ss"], box["mp2_done"]
+
+
+def run_hip_rimp2_batch(settings: ScfSettings, fragments: Sequence[PhysicalFragment], frozen_core: bool = True) -> List[CalculationResult]:
+    """Many independent fragments through mqc_hip_rimp2_batch, results as CalculationResult objects: energy.scf, and
+    where has_mp2 is set energy.mp2_os / energy.mp2_ss (energy.total() = scf + mp2).  A fragment whose SCF converged
+    without a correlation energy does not exist: has_mp2 is False exactly where the record carries an error or the SCF
+    did not converge."""
+    results = [CalculationResult() for _ in range(len(fragments))]
+    if not fragments:
+        return results
+    groups, index = _groups_of(fragments)
+    recs, e_os, e_ss, done = run_hip_rimp2_groups(settings, groups, frozen_core)
+    for idx, rec, os_, ss_, dn in zip(index, recs, e_os, e_ss, done):
+        for pos, (i, r) in enumerate(zip(idx, rec)):
+            _fill_record(results[i], r)
+            if results[i].has_energy and dn[pos]:
+                results[i].energy.mp2_os = float(os_[pos]); results[i].energy.mp2_ss = float(ss_[pos])
+                results[i].has_mp2 = True
+    return results
+
+
 def run_hip_scf_batch(settings: ScfSettings, fragments: Sequence[PhysicalFragment],
                       initial_densities: Optional[Sequence] = None) -> List[CalculationResult]:
     """Many independent fragments in one call (mqc_hip_scf_run_batch), results as CalculationResult objects.
@@ -620,18 +709,7 @@ def run_hip_scf_batch(settings: ScfSettings, fragments: Sequence[PhysicalFragmen
     results = [CalculationResult() for _ in range(n)]
     if n == 0:
         return results
-    by_key = {}
-    for i, f in enumerate(fragments):
-        key = (f.element_numbers.tobytes(), None if f.ghost is None else f.ghost.tobytes())
-        by_key.setdefault(key, []).append(i)
-    groups, index = [], []
-    for idx in by_key.values():
-        f0 = fragments[idx[0]]
-        groups.append(FragmentGroup(f0.element_numbers, np.stack([fragments[i].coordinates.T for i in idx]),
-                                    np.array([fragments[i].charge for i in idx], dtype=np.int32),
-                                    np.array([fragments[i].multiplicity for i in idx], dtype=np.int32),
-                                    f0.ghost, np.array([fragments[i].nelec for i in idx], dtype=np.int32)))
-        index.append(idx)
+    groups, index = _groups_of(fragments)
     if initial_densities is None:
         for idx, rec in zip(index, run_hip_scf_groups(settings, groups)):
             for i, r in zip(idx, rec):
