@@ -6,7 +6,7 @@ OUT=../libmqc_hip.so
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Wno-unused-result -Wno-pass-failed"
 mkdir -p _obj
 [ -f lebedev_tables.inc ] || python3 gen_lebedev.py
-HDRS="md_integrals.hpp engine.hpp driver.hpp eri_kernels.hpp ../../include/mqc_hip.h"
+HDRS="md_integrals.hpp engine.hpp driver.hpp eri_kernels.hpp hermite_records.hpp ../../include/mqc_hip.h"
 stale() { # obj src
   [ ! -f "$1" ] && return 0
   [ "$2" -nt "$1" ] && return 0

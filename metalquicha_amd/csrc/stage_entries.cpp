@@ -9,9 +9,9 @@
 
 namespace mqc {
 // kern_esp.hip: potential of nfrag densities at their points (device arrays of one chunk); doubles of records per fragment
-void launch_esp(const TopologyDev& td, const Topology& topo, const double* boys_table, const double* c2s, int nfrag, const double* d_xyz,
+bool launch_esp(const TopologyDev& td, const Topology& topo, const double* boys_table, const double* c2s, int nfrag, const double* d_xyz,
                 const double* d_D, double* d_rec, const double* d_pts, const int* d_npts, int max_points, int include_nuclei, double* d_out,
-                hipStream_t s);
+                hipStream_t s, std::string& err);
 size_t esp_record_doubles(const Topology& topo);
 static DevicePool g_esp_pool;
 
@@ -326,7 +326,8 @@ int mqc_hip_esp_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecul
             if (hn[f] > 0)
                 HIP_CHECK_RET(hipMemcpyAsync(d_pts + (size_t)f * 3 * mp, points + (size_t)(start + f) * 3 * mp, sizeof(double) * 3 * hn[f],
                                              hipMemcpyHostToDevice, ctx->stream));
-        launch_esp(td, topo, ctx->d_boys, ctx->d_c2s, nf, d_xyz, d_D, d_rec, d_pts, d_np, max_points, include_nuclei ? 1 : 0, d_out, ctx->stream);
+        if (!launch_esp(td, topo, ctx->d_boys, ctx->d_c2s, nf, d_xyz, d_D, d_rec, d_pts, d_np, max_points, include_nuclei ? 1 : 0, d_out, ctx->stream, err))
+            return fail(MQC_HIP_ERR_DEVICE, err);
         if ((rc = sync_and_check(ctx->stream)) != MQC_HIP_OK) return rc;
         hout.resize((size_t)nf * mp);
         HIP_CHECK_RET(hipMemcpy(hout.data(), d_out, sizeof(double) * hout.size(), hipMemcpyDeviceToHost));

@@ -1,9 +1,10 @@
 // check_device_math.cpp -- TEST-ONLY harness.  Compiles the `__host__ __device__` integral
-// templates of metalquicha_amd/csrc/md_integrals.hpp for the HOST so that tests/ can compare
+// templates of metalquicha_amd/csrc/md_integrals.hpp and hermite_records.hpp for the HOST so that tests/ can compare
 // the arithmetic the gfx950 kernels instantiate against the oracle here, without a GPU.
 // It is never linked into libmqc_hip.so and is not a fallback path of the product.
 #include "../../metalquicha_amd/csrc/md_integrals.hpp"
 #include "../../metalquicha_amd/csrc/engine.hpp"
+#include "../../metalquicha_amd/csrc/hermite_records.hpp"
 #include <vector>
 #include <set>
 #include <array>
@@ -111,7 +112,121 @@ static double run_twin(const ShellRef* sh, const double* const* second, const bo
     return worst;
 }
 
+// The records of one shell pair (hermite_records.hpp), both kinds, contracted at points as esp_points_kernel and
+// gradpc_points_kernel contract them: one dot product for the potential, six for v_A and v_C.  D is the spherical
+// density of the two shells alone (a first).  Returns the primitive pairs whose X blocks differ between the two kinds.
+template <int LA, int LB>
+static int run_hermite(const ShellRef* sh, const double* D, int npts, const double* pts, double* v, double* va, double* vc)
+{
+    constexpr int L = LA + LB, NH = nherm(L), NH1 = nherm(L + 1);
+    constexpr int RD0 = hermite_rec_doubles(L, false), RD1 = hermite_rec_doubles(L, true), HEAD = hermite_head(true);
+    double dc[ncart(LA) * ncart(LB)];
+    for (int e = 0; e < ncart(LA) * ncart(LB); ++e)
+        dc[e] = cart_density_element<LA, LB>(D, nsph(LA) + nsph(LB), 0, nsph(LA), true, g_c2s.data(), e);
+    const int nrec = sh[0].nprim * sh[1].nprim;
+    std::vector<double> r0((size_t)nrec * RD0, -1.0), r1((size_t)nrec * RD1, -1.0);
+    int differ = 0;
+    for (int pp = 0; pp < nrec; ++pp) {
+        const int ia = pp / sh[1].nprim, ib = pp % sh[1].nprim;
+        hermite_record<LA, LB, false>(dc, sh[0].exps[ia], sh[1].exps[ib], sh[0].coefs[ia], sh[1].coefs[ib], sh[0].x, sh[0].y, sh[0].z, sh[1].x,
+                                      sh[1].y, sh[1].z, 0, 1, &r0[(size_t)pp * RD0]);
+        hermite_record<LA, LB, true>(dc, sh[0].exps[ia], sh[1].exps[ib], sh[0].coefs[ia], sh[1].coefs[ib], sh[0].x, sh[0].y, sh[0].z, sh[1].x,
+                                     sh[1].y, sh[1].z, 0, 1, &r1[(size_t)pp * RD1]);
+        const double *a = &r0[(size_t)pp * RD0], *b = &r1[(size_t)pp * RD1];
+        if (a[0] != b[0]) { ++differ; continue; }
+        if (a[0] == 0.0) continue;
+        if (std::memcmp(a, b, 4 * sizeof(double)) != 0 || std::memcmp(a + 4, b + HEAD, NH * sizeof(double)) != 0 || b[4] != 0.0 || b[5] != 1.0) ++differ;
+    }
+    for (int g = 0; g < npts; ++g) {
+        const double cx = pts[3 * g], cy = pts[3 * g + 1], cz = pts[3 * g + 2];
+        double acc = 0.0, gA[3] = {0.0, 0.0, 0.0}, gC[3] = {0.0, 0.0, 0.0};
+        for (int k = 0; k < nrec; ++k) {
+            {   // esp_points_kernel<L>
+                const double* rec = &r0[(size_t)k * RD0];
+                const double p = rec[0];
+                if (p != 0.0) {
+                    double R[NH];
+                    hermite_r<L>(p, rec[1] - cx, rec[2] - cy, rec[3] - cz, g_boys.data(), R);
+                    double s = 0.0;
+                    for (int h = 0; h < NH; ++h) s += rec[4 + h] * R[h];
+                    acc += s;
+                }
+            }
+            {   // gradpc_points_kernel<L>
+                const double* rec = &r1[(size_t)k * RD1];
+                const double p = rec[0];
+                if (p == 0.0) continue;
+                double R[NH1];
+                hermite_r<L + 1>(p, rec[1] - cx, rec[2] - cy, rec[3] - cz, g_boys.data(), R);
+                const double* x = rec + HEAD;
+                const double* xa = x + NH;
+                double sa[3] = {0.0, 0.0, 0.0}, sc[3] = {0.0, 0.0, 0.0};
+                for (int h = 0; h < NH1; ++h) {
+                    sa[0] += xa[h] * R[h]; sa[1] += xa[NH1 + h] * R[h]; sa[2] += xa[2 * NH1 + h] * R[h];
+                }
+                for (int N = 0; N <= L; ++N)
+                    for (int t = N; t >= 0; --t)
+                        for (int u = N - t; u >= 0; --u) {
+                            const int w = N - t - u;
+                            const double xv = x[hidx(t, u, w)];
+                            sc[0] += xv * R[hidx(t + 1, u, w)]; sc[1] += xv * R[hidx(t, u + 1, w)]; sc[2] += xv * R[hidx(t, u, w + 1)];
+                        }
+                for (int c = 0; c < 3; ++c) { gA[c] += sa[c]; gC[c] += sc[c]; }
+            }
+        }
+        v[g] = acc;
+        for (int c = 0; c < 3; ++c) { va[3 * g + c] = gA[c]; vc[3 * g + c] = gC[c]; }
+    }
+    return differ;
+}
+
 extern "C" {
+
+// One shell pair (la >= lb) on two centres: v[g] = sum over records of X . R at point g, va[g][c] = sum XA^c . R and
+// vc[g][c] = sum X . R_{+1_c} (d/dA_c of v is va, d/dC_c of v is -vc); *differ: see run_hermite.
+int hostcheck_hermite_pair(const int* l, const int* nprim, const double* exps, const double* coefs, const double* xyz /* 2x3 */,
+                           const double* D, int npts, const double* pts, double* v, double* va, double* vc, int* differ)
+{
+    ensure_tables();
+    ShellRef sh[2];
+    int off = 0;
+    for (int k = 0; k < 2; ++k) {
+        sh[k].nprim = nprim[k]; sh[k].exps = exps + off; sh[k].coefs = coefs + off;
+        sh[k].x = xyz[3 * k]; sh[k].y = xyz[3 * k + 1]; sh[k].z = xyz[3 * k + 2];
+        off += nprim[k];
+    }
+#define HCASE(a, b) case (a * 8 + b): *differ = run_hermite<a, b>(sh, D, npts, pts, v, va, vc); return 0;
+    switch (l[0] * 8 + l[1]) {
+        HCASE(0, 0) HCASE(1, 0) HCASE(1, 1) HCASE(2, 0) HCASE(2, 1) HCASE(2, 2) HCASE(3, 0) HCASE(3, 1) HCASE(3, 2) HCASE(3, 3)
+    }
+    return 1;
+}
+
+// hermite_lists of a topology.  out (cap ints): nshell, npairs, per shell (l, atom, nprim), the topology's pairs (A, B),
+// then per class (la, lb), la >= lb, in launch order: its length and its (A, B, first record) triples, then nrec[0..6];
+// offs: group_off[0..6], rec_stride.  Returns the ints written, -1 when the topology fails or cap is too small.
+int hostcheck_hermite_lists(const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, int by_atom_pair, int deriv, int cap, int* out,
+                            unsigned long long* offs)
+{
+    Topology topo;
+    std::string err;
+    if (build_topology(*mol, *bas, topo, err, KERNEL_LMAX, false) != MQC_HIP_OK) return -1;
+    const HermiteLists hl = deriv ? hermite_lists<true>(topo, by_atom_pair != 0) : hermite_lists<false>(topo, by_atom_pair != 0);
+    if (hl.rec_stride != (deriv ? hermite_record_doubles<true>(topo) : hermite_record_doubles<false>(topo))) return -1;
+    std::vector<int> o{(int)topo.shells.size(), (int)topo.pairs.size() / 2};
+    for (const HostShell& s : topo.shells) { o.push_back(s.l); o.push_back(s.atom); o.push_back(s.nprim); }
+    o.insert(o.end(), topo.pairs.begin(), topo.pairs.end());
+    for (int la = 0; la <= KERNEL_LMAX; ++la)
+        for (int lb = 0; lb <= la; ++lb) {
+            o.push_back((int)hl.cls[la][lb].size());
+            o.insert(o.end(), hl.cls[la][lb].begin(), hl.cls[la][lb].end());
+        }
+    for (int L = 0; L <= HERMITE_LMAX; ++L) { o.push_back(hl.nrec[L]); offs[L] = hl.group_off[L]; }
+    offs[HERMITE_LMAX + 1] = hl.rec_stride;
+    if ((int)o.size() > cap) return -1;
+    std::copy(o.begin(), o.end(), out);
+    return (int)o.size();
+}
 
 // shells: for each of the 4 shells: nprim, then pointers are passed flat.
 int hostcheck_eri_block(const int* l, const int* nprim, const double* exps, const double* coefs /* normalised, s/p factor folded */,

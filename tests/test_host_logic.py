@@ -161,6 +161,169 @@ def test_topology_twin_cut_covers_every_quartet_once(hostcheck, zs, basis, expec
     assert (nent.value > 0) == (expect_twins > 0)
 
 
+# ---- the Hermite-record stage of the potential and the point-charge gradient (hermite_records.hpp) ----
+HERMITE_CLASSES = [(la, lb) for la in range(4) for lb in range(la + 1)]
+HERMITE_FD_STEP = 4e-4
+
+
+@pytest.fixture(scope="module")
+def hermite_pair(hostcheck):
+    """Per (la, lb): one shell pair on two atoms, a random density block, three points; the records of both kinds
+    contracted on the host as the point kernels contract them, and the oracle's W(A, C) = sum_ab D_ab (a| 1/|r - C| |b)
+    as a function of the first centre and of the point.  Computed once per class, shared by the tests below."""
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+    cache = {}
+
+    def get(cls):
+        if cls in cache:
+            return cache[cls]
+        la, lb = cls
+        rng = np.random.default_rng(1000 + 7 * la + lb)
+        l = np.array(cls, dtype=np.int32)
+        nprim = rng.integers(1, 4, size=2).astype(np.int32)
+        exps = rng.uniform(0.2, 4.0, size=int(nprim.sum())); exps[0] = 30.0
+        coefs = rng.uniform(-1, 1, size=int(nprim.sum()))
+        xyz = rng.uniform(-0.6, 0.6, size=(2, 3))          # about a bond length apart: the tight primitive's pairs survive
+        pts = rng.uniform(-3.0, 3.0, size=(3, 3))
+        nsa, nsb = 2 * la + 1, 2 * lb + 1
+        D = rng.uniform(-1, 1, size=(nsa + nsb, nsa + nsb))
+        Dab = D[:nsa, nsa:] + D[nsa:, :nsa].T          # an off-diagonal shell pair stands for (a, b) and (b, a)
+
+        def oracle(centres, points):
+            mol = so.make_mol([1, 1], centres, [1, 1], l, nprim, exps, coefs)
+            # point_charge_potential is u = -q (a| 1/|r - C| |b): a unit charge and the sign turned
+            return mol, np.array([-np.sum(Dab * so.point_charge_potential(mol, [r], [1.0])[:nsa, nsa:]) for r in points])
+
+        mol, ref = oracle(xyz, pts)
+        fac = np.array([0.282094791773878143, 0.488602511902919921, 1.0, 1.0])
+        co = mol.coefs.copy()
+        co[:nprim[0]] *= fac[la]; co[nprim[0]:] *= fac[lb]
+        v, va, vc, differ = np.zeros(3), np.zeros((3, 3)), np.zeros((3, 3)), ctypes.c_int(-1)
+        rc = hostcheck.hostcheck_hermite_pair(l.ctypes.data_as(ip), nprim.ctypes.data_as(ip), exps.ctypes.data_as(dp), co.ctypes.data_as(dp),
+                                              np.ascontiguousarray(xyz).ctypes.data_as(dp), np.ascontiguousarray(D).ctypes.data_as(dp), 3,
+                                              np.ascontiguousarray(pts).ctypes.data_as(dp), v.ctypes.data_as(dp), va.ctypes.data_as(dp),
+                                              vc.ctypes.data_as(dp), ctypes.byref(differ))
+        assert rc == 0
+        cache[cls] = dict(xyz=xyz, pts=pts, ref=ref, oracle=lambda c, p: oracle(c, p)[1], v=v, dA=va, dC=-vc, differ=differ.value,
+                          tol=1e-13 * max(1.0, float(np.max(np.abs(ref)))))
+        return cache[cls]
+    return get
+
+
+@pytest.mark.parametrize("cls", HERMITE_CLASSES)
+def test_hermite_records_give_the_oracle_potential(hermite_pair, cls):
+    """sum over records of X . R equals sum_ab D_ab (a| 1/|r - C| |b), to the bound of the host-versus-oracle integral tests."""
+    c = hermite_pair(cls)
+    err = float(np.max(np.abs(c["v"] - c["ref"])))
+    print("class %s: max |oracle| %.3e, max |records - oracle| %.3e, bound %.3e" % (cls, np.max(np.abs(c["ref"])), err, c["tol"]))
+    assert np.max(np.abs(c["ref"])) > 1e-4          # the case is not a screened-out pair
+    assert err <= c["tol"]
+
+
+@pytest.mark.parametrize("cls", HERMITE_CLASSES)
+def test_hermite_records_with_and_without_derivative_blocks_share_their_x_block(hermite_pair, cls):
+    """E1D<LA, LB> and E1D<LA + 1, LB> tables give bitwise the same head and X block for every primitive pair."""
+    assert hermite_pair(cls)["differ"] == 0
+
+
+@pytest.mark.parametrize("cls", HERMITE_CLASSES)
+def test_hermite_record_derivatives_match_central_differences(hermite_pair, cls):
+    """v_C (the charge moves) and v_A (atom A moves, density held fixed) against central differences of the oracle's W at
+    steps h and h/2.  FD(h) - FD(h/2) is three times the truncation error of FD(h/2) to leading order (Richardson), so
+    |analytic - FD(h/2)| <= |FD(h) - FD(h/2)| + eps, eps = the oracle's round-off in a difference = its potential
+    tolerance / (h/2).  h = 4e-4: with third derivatives of order 1-100 (a 30 a.u. exponent) the truncation term,
+    h^2 f''' / 8 ~ 2e-8 f''', stays above eps ~ 5e-10, and the check resolves a relative error of 1e-7 in a derivative."""
+    c = hermite_pair(cls)
+    h = HERMITE_FD_STEP
+    eps = c["tol"] / (0.5 * h)
+
+    def fd(step, move_atom, axis):
+        d = np.zeros(3); d[axis] = step
+        if move_atom:
+            xp, xm = c["xyz"].copy(), c["xyz"].copy()
+            xp[0] += d; xm[0] -= d
+            return (c["oracle"](xp, c["pts"]) - c["oracle"](xm, c["pts"])) / (2 * step)
+        return (c["oracle"](c["xyz"], c["pts"] + d) - c["oracle"](c["xyz"], c["pts"] - d)) / (2 * step)
+
+    worst = 0.0
+    for name, move_atom in (("dA", True), ("dC", False)):
+        for axis in range(3):
+            f1, f2 = fd(h, move_atom, axis), fd(0.5 * h, move_atom, axis)
+            ratio = np.abs(c[name][:, axis] - f2) / (np.abs(f1 - f2) + eps)
+            worst = max(worst, float(np.max(ratio)))
+    print("class %s: worst |analytic - FD(h/2)| / (|FD(h) - FD(h/2)| + eps) = %.3f" % (cls, worst))
+    assert worst <= 1.0
+
+
+# group_off[0..6] and rec_stride of the water molecule, recorded from the build before the stage was shared
+HERMITE_WATER_GOLDEN = {
+    ("6-31g", False): ([0, 975, 1551, 1733, 1733, 1733, 1733], 1760),
+    ("6-31g", True): ([0, 3705, 6585, 7573, 7573, 7573, 7573], 7584),
+    ("cc-pvdz", False): ([0, 2595, 4219, 5101, 5269, 5308, 5308], 5312),
+    ("cc-pvdz", True): ([0, 9861, 17981, 22769, 23686, 23895, 23895], 23904),
+    ("def2-tzvp", False): ([0, 1265, 2609, 3785, 4673, 5102, 5222], 5312),
+    ("def2-tzvp", True): ([0, 4807, 11527, 17911, 22758, 25057, 25685], 26144),
+}
+
+
+@pytest.mark.parametrize("basis,deriv", sorted(HERMITE_WATER_GOLDEN))
+def test_hermite_lists_cover_every_shell_pair_once_in_the_recorded_layout(hostcheck, basis, deriv):
+    """The potential's lists (topology order, 4-double heads) and the gradient's (by atom pair, 6-double heads with
+    derivative blocks) of water in three bases: every shell pair once with la >= lb, first records tile each L group,
+    group offsets and stride as recorded, atom pairs contiguous per group / the topology's order."""
+    from tests import stages
+    ip = ctypes.POINTER(ctypes.c_int)
+    m = stages._marshal(basis, fragment_bohr([8, 1, 1], [[0.0, 0.0, -0.1364652], [0.0, 1.4304924, 1.0826636], [0.0, -1.4304924, 1.0826636]]))
+    out, offs = np.zeros(1 << 16, dtype=np.int32), np.zeros(8, dtype=np.uint64)
+    n = hostcheck.hostcheck_hermite_lists(ctypes.byref(m.mol), ctypes.byref(m.bas), int(deriv), int(deriv), len(out), out.ctypes.data_as(ip),
+                                          offs.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)))
+    assert n > 0
+    nshell, npairs = int(out[0]), int(out[1])
+    shells = out[2:2 + 3 * nshell].reshape(nshell, 3)            # l, atom, nprim
+    pos = 2 + 3 * nshell
+    topo_pairs = out[pos:pos + 2 * npairs].reshape(npairs, 2)
+    pos += 2 * npairs
+    groups = {L: [] for L in range(7)}                           # per L: (first record, A, B)
+    per_class = {}
+    for la in range(4):
+        for lb in range(la + 1):
+            k = int(out[pos]); pos += 1
+            tri = out[pos:pos + k].reshape(-1, 3); pos += k
+            per_class[(la, lb)] = tri
+            for A, B, first in tri:
+                assert (shells[A, 0], shells[B, 0]) == (la, lb)
+                groups[la + lb].append((int(first), int(A), int(B)))
+    nrec = out[pos:pos + 7]
+    assert pos + 7 == n
+    listed = sorted((max(a, b), min(a, b)) for g in groups.values() for _, a, b in g)
+    assert listed == sorted((max(a, b), min(a, b)) for a, b in topo_pairs) and len(set(listed)) == npairs == nshell * (nshell + 1) // 2
+    nh = lambda L: (L + 1) * (L + 2) * (L + 3) // 6
+    off = 0
+    for L in range(7):
+        g = sorted(groups[L])
+        at = 0
+        for first, A, B in g:
+            assert first == at
+            at += int(shells[A, 2] * shells[B, 2])
+        assert at == nrec[L]
+        assert int(offs[L]) == off
+        off += at * ((6 + nh(L) + 3 * nh(L + 1)) if deriv else (4 + nh(L)))
+        keys = [int(shells[A, 1]) * 3 + int(shells[B, 1]) for _, A, B in g]
+        if deriv:
+            assert keys == sorted(keys)                          # one contiguous run per atom pair
+    assert int(offs[7]) == (off + 31) // 32 * 32
+    assert ([int(v) for v in offs[:7]], int(offs[7])) == HERMITE_WATER_GOLDEN[(basis, deriv)]
+    if not deriv:
+        # the topology's order: a class's triples follow the topology's pair list, first records rise with it inside a group
+        order = {(max(a, b), min(a, b)): i for i, (a, b) in enumerate(topo_pairs)}
+        for tri in per_class.values():
+            idx = [order[(max(a, b), min(a, b))] for a, b, _ in tri]
+            assert idx == sorted(idx)
+        for L in range(7):
+            idx = [order[(max(a, b), min(a, b))] for _, a, b in sorted(groups[L])]
+            assert idx == sorted(idx)
+
+
 # ---- device layout of a batch chunk (carve_chunk) ----------------------------------------------
 TWO_E = {"incore": 0, "direct": 1, "df": 2}
 # n, natoms, nshell, lmax of the fragments: STO-3G water, cc-pVDZ water and water dimer, larger cc-pVDZ clusters
