@@ -257,6 +257,36 @@ int mqc_hip_xc_batch(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip_mo
                      const mqc_hip_basis_t *orbital, const char *functional, int32_t grid_level, int32_t unrestricted,
                      const double *D, double *e_xc /* [n] */, double *n_electrons /* [n] */, double *V_xc);
 
+/* The density-fitted J/K stage on GIVEN tensors, for n_fragments of one shape: what one SCF iteration's J/K stage
+ * computes, alone.  No molecule: the kernels read the sizes, exx, D, C and the fitted tensor only.
+ *     B [n][n_aux][npair]   the fitted tensor, packed pairs (mu >= nu, index mu (mu + 1) / 2 + nu) fastest
+ *     D [n][n_ao*n_ao]      the (symmetric) density
+ *     C [n][n_ao*n_ao]      row-major, columns are orbitals, the first n_occ are occupied
+ *     J, K [n][n_ao*n_ao]   J = sum_P B_P tr(B_P D), K = 2 sum_P (B_P C_occ)(B_P C_occ)^T
+ * The arrays are those of a density-fitted SCF batch of this shape and the SCF driver's own dispatch runs once over all
+ * fragments; route (route_len bytes, NUL-terminated) receives the kernel it chose: wave<NTC,NLW>, mfma<JMAX,NLD,K|J> or
+ * v1<NV,lds|global>.  J and K are poisoned before the launch and their neighbours in the pool are compared before and
+ * after (MQC_HIP_ERR_DEVICE when the stage wrote outside).  exx = 0 (a pure functional) specifies J only; K then holds
+ * zeros on the mfma route (its J-only instance) and the plain exchange on the v1 route.
+ * MQC_HIP_ERR_VALIDATION: null pointers, n_fragments < 1, n_ao outside 1..140, n_occ outside 1..n_ao, n_aux < 1, exx
+ * negative or not finite.  (Added without an ABI bump: no struct changed.) */
+int mqc_hip_df_jk_batch(mqc_hip_context *ctx, int64_t n_fragments, int32_t n_ao, int32_t n_occ, int32_t n_aux, double exx,
+                        const double *B, const double *D, const double *C, double *J, double *K,
+                        char *route, int32_t route_len);
+
+/* The build of the fitted tensor alone, for MANY fragments of ONE topology: the integral half and the fit half of a
+ * density-fitted SCF's build stage, with the metric copied out between them (the factor overwrites it in place).
+ *     A3 [n][n_aux][npair]       (P|mu nu)
+ *     metric [n][n_aux*n_aux]    (P|Q), both triangles
+ *     B [n][n_aux][npair]        the fitted tensor: L^-1 A3 (Cholesky) or J^-1/2 A3 (eigen path, eigenvalues above 1e-10)
+ *     fit_flag [n]               0: Cholesky, 2: eigen path (a near-singular metric), 1: the fit failed
+ * The three arrays are poisoned first: an element no task covers reads as NaN.  Refused as a density-fitted SCF refuses:
+ * n_ao > 140, orbital shells above f, a Cartesian basis; MQC_HIP_ERR_VALIDATION: null pointers, n_fragments < 1,
+ * fragments of different elements.  (Added without an ABI bump: no struct changed.) */
+int mqc_hip_df_fit_batch(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip_molecule_t *mols,
+                         const mqc_hip_basis_t *orbital, const mqc_hip_basis_t *aux, double *A3, double *metric,
+                         double *B, double *fit_flag /* [n] */);
+
 /* Analytic gradients of fragments EMBEDDED IN POINT CHARGES (FMO / EE-MBE / QM-MM callers): mqc_hip_scf_run_batch with
  * opts->want_gradient forced on -- grouping by topology, chunking and per-fragment failures in results[i] as there -- and
  * two outputs per fragment, both exact derivatives of the e_total the engine reports (which contains tr(D u) and does NOT

@@ -389,8 +389,18 @@ void launch_becke_weights(const BatchView& bv, hipStream_t s);
 void launch_xc_radial_cache(const BatchView& bv, hipStream_t s);
 // points per tile of the quadrature kernel for n basis functions (kern_xc.hip) = granularity of the radial cache
 inline int xc_tile_points(int n) { return ((n + 15) / 16 <= 6) ? 32 : 16; }     // n <= 96: 32-point tiles (kern_xc.hip, xc_tile_dispatch)
+// launch_df_build = launch_df_integrals ((P|mu nu) and the metric) + launch_df_fit (factorisation and fitted tensor)
 void launch_df_build(const BatchView& bv, const Topology& topo, const Topology& aux, hipStream_t s);
-void launch_df_jk(const BatchView& bv, bool only_active, hipStream_t s);
+void launch_df_integrals(const BatchView& bv, const Topology& topo, const Topology& aux, hipStream_t s);
+void launch_df_fit(const BatchView& bv, hipStream_t s);
+// The kernel launch_df_jk chose: wave<a,b> | mfma<a,b,K or J> (flag: with exchange) | v1<a,lds or global> (flag: the
+// unpacked row of B sits in LDS).  The SCF driver ignores it; mqc_hip_df_jk_batch reports it.
+enum : int { DF_JK_WAVE = 0, DF_JK_MFMA = 1, DF_JK_V1 = 2 };
+struct DfJkRoute {
+    int family, a, b;
+    bool flag;
+};
+DfJkRoute launch_df_jk(const BatchView& bv, bool only_active, hipStream_t s);
 void launch_xc(const BatchView& bv, bool only_active, hipStream_t s);
 bool build_atom_template(int z, int level, int n_radial, int n_angular, std::vector<double>& xyz, std::vector<double>& w, std::string& err);
 bool parse_functional(const char* name, XcSpec& spec, std::string& err);

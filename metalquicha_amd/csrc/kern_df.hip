@@ -974,19 +974,19 @@ static bool df_jk_wave_launch(const BatchView& bv, int oa, hipStream_t s)
 }
 
 // n <= 48, one orbital tile, exchange wanted (MQC_HIP_DF_WAVE=0: the workgroup kernel)
-static bool df_jk_wave_dispatch(const BatchView& bv, int oa, hipStream_t s)
+static bool df_jk_wave_dispatch(const BatchView& bv, int oa, hipStream_t s, DfJkRoute& r)
 {
     static const bool on = [] { const char* e = std::getenv("MQC_HIP_DF_WAVE"); return !(e && e[0] == '0'); }();
     if (!on || bv.exx == 0.0 || bv.n > 48 || bv.nocc > 16) return false;
     const int nt = (bv.n + 15) / 16, nlw = (bv.npair + 63) / 64;
-    if (nt == 1 && nlw <= 3) return df_jk_wave_launch<1, 3>(bv, oa, s);
-    if (nt == 2 && nlw <= 9) return df_jk_wave_launch<2, 9>(bv, oa, s);
-    if (nt == 3 && nlw <= 19) return df_jk_wave_launch<3, 19>(bv, oa, s);
+    if (nt == 1 && nlw <= 3) { r = {DF_JK_WAVE, 1, 3, true}; return df_jk_wave_launch<1, 3>(bv, oa, s); }
+    if (nt == 2 && nlw <= 9) { r = {DF_JK_WAVE, 2, 9, true}; return df_jk_wave_launch<2, 9>(bv, oa, s); }
+    if (nt == 3 && nlw <= 19) { r = {DF_JK_WAVE, 3, 19, true}; return df_jk_wave_launch<3, 19>(bv, oa, s); }
     return false;
 }
 
 // false: no instantiation covers this size (the round-1 kernels take it)
-static bool df_jk_mfma_dispatch(const BatchView& bv, int oa, hipStream_t s)
+static bool df_jk_mfma_dispatch(const BatchView& bv, int oa, hipStream_t s, DfJkRoute& r)
 {
     const int nt = (bv.n + 15) / 16, ntile = nt * (nt + 1) / 2, jobs = (ntile + DJ_NW - 1) / DJ_NW;
     const int nld = (bv.npair + 64 * DJ_NW - 1) / (64 * DJ_NW);
@@ -997,6 +997,7 @@ static bool df_jk_mfma_dispatch(const BatchView& bv, int oa, hipStream_t s)
     if (sizeof(double) * ((size_t)bv.npair + body) > 150 * 1024) return false;
 #define DJ(JM, NL)                                                                                        \
     do {                                                                                                  \
+        r = {DF_JK_MFMA, k ? JM : 1, NL, k};                                                              \
         if (k) { if (dpg) df_jk_mfma_launch<JM, NL, true, true>(bv, oa, s); else df_jk_mfma_launch<JM, NL, true, false>(bv, oa, s); } \
         else { if (dpg) df_jk_mfma_launch<1, NL, false, true>(bv, oa, s); else df_jk_mfma_launch<1, NL, false, false>(bv, oa, s); }   \
         return true;                                                                                      \
@@ -1031,7 +1032,8 @@ static void df2c_launch(const BatchView& bv, const std::vector<int>& t, int* d, 
     hipLaunchKernelGGL((df2c_kernel<LP, LQ>), dim3((int)((total + 63) / 64)), dim3(64), 0, s, bv, d, nt);
 }
 
-void launch_df_build(const BatchView& bv, const Topology& topo, const Topology& aux, hipStream_t s)
+// the integral half of the build: (P|mu nu) into df_a3 and the metric (P|Q), both triangles, into df_metric
+void launch_df_integrals(const BatchView& bv, const Topology& topo, const Topology& aux, hipStream_t s)
 {
     static DevicePool lists_slot[2];
     DevicePool& lists = lists_slot[bv.slot & 1];
@@ -1083,6 +1085,11 @@ void launch_df_build(const BatchView& bv, const Topology& topo, const Topology& 
 #define DF2(p, q) df2c_launch<p, q>(bv, t2[p][q], d + off, s); off += t2[p][q].size();
     DF2(0, 0) DF2(1, 0) DF2(1, 1) DF2(2, 0) DF2(2, 1) DF2(2, 2) DF2(3, 0) DF2(3, 1) DF2(3, 2) DF2(3, 3)
 #undef DF2
+}
+
+// the fit half: the metric is factorised in place (flagged fragments: diagonalised), then df_b = L^-1 A3 (or J^-1/2 A3)
+void launch_df_fit(const BatchView& bv, hipStream_t s)
+{
     {
         static const bool v1 = [] { const char* e = std::getenv("MQC_HIP_DF_CHOL_V1"); return e && e[0] == '1'; }();
         const size_t npad = (size_t)((bv.naux + 15) / 16) * 16;
@@ -1103,18 +1110,25 @@ void launch_df_build(const BatchView& bv, const Topology& topo, const Topology& 
     }
 }
 
+void launch_df_build(const BatchView& bv, const Topology& topo, const Topology& aux, hipStream_t s)
+{
+    launch_df_integrals(bv, topo, aux, s);
+    launch_df_fit(bv, s);
+}
+
 size_t df_k_lds_bytes(int n, int o, bool blds) { return sizeof(double) * ((blds ? (size_t)n * (n + 1) : 0) + (size_t)n * o + (size_t)n * (o + 1) + 8); }
 
-void launch_df_jk(const BatchView& bv, bool only_active, hipStream_t s)
+DfJkRoute launch_df_jk(const BatchView& bv, bool only_active, hipStream_t s)
 {
     const int n = bv.n, oa = only_active ? 1 : 0;
+    DfJkRoute r{};
     (void)hipMemsetAsync(bv.K, 0, sizeof(double) * (size_t)bv.nfrag * n * n, s);
     // MQC_HIP_DF_V1=1: the round-1 kernels (J as one workgroup per fragment with two passes over B, K on the vector units)
     static const bool v1 = [] { const char* e = std::getenv("MQC_HIP_DF_V1"); return e && e[0] == '1'; }();
     if (!v1) {
         (void)hipMemsetAsync(bv.J, 0, sizeof(double) * (size_t)bv.nfrag * n * n, s);
-        if (df_jk_wave_dispatch(bv, oa, s)) return;
-        if (df_jk_mfma_dispatch(bv, oa, s)) return;
+        if (df_jk_wave_dispatch(bv, oa, s, r)) return r;
+        if (df_jk_mfma_dispatch(bv, oa, s, r)) return r;
     }
     const size_t ldsj = sizeof(double) * ((size_t)bv.npair + bv.naux + 8);
     (void)hipFuncSetAttribute((const void*)df_j_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsj);
@@ -1127,11 +1141,14 @@ void launch_df_jk(const BatchView& bv, bool only_active, hipStream_t s)
     const int nv = (n * n + DF_NT - 1) / DF_NT;
 #define DFK(NVV, BL)                                                                                 \
     do {                                                                                             \
+        r = {DF_JK_V1, NVV, 0, BL};                                                                  \
         (void)hipFuncSetAttribute((const void*)df_k_kernel<NVV, BL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsk); \
         hipLaunchKernelGGL((df_k_kernel<NVV, BL>), dim3(gx, bv.nfrag), dim3(DF_NT), ldsk, s, bv, oa); \
     } while (0)
-    if (nv <= 10) DFK(10, true); else if (nv <= 29) DFK(29, true); else if (blds) DFK(54, true); else DFK(77, false);
+    // invariant: NV * 256 >= n * n (n <= 140: 77 * 256 covers it) and the instance's BLDS is the blds that sized ldsk
+    if (!blds) DFK(77, false); else if (nv <= 10) DFK(10, true); else if (nv <= 29) DFK(29, true); else if (nv <= 54) DFK(54, true); else DFK(77, true);
 #undef DFK
+    return r;
 }
 
 

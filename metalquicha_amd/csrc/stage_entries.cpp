@@ -443,6 +443,142 @@ int mqc_hip_xc_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule
     return MQC_HIP_OK;
 }
 
+// The density-fitted J/K stage of an SCF iteration on given tensors (include/mqc_hip.h).  No molecule: the kernels read
+// n, npair, naux, nocc, exx, D, C, df_b and istate only.  The arrays are the ones carve_slot gives a density-fitted
+// batch of this shape, and launch_df_jk runs once, as jk_one runs it.
+int mqc_hip_df_jk_batch(mqc_hip_context* ctx, int64_t nfrag, int32_t n_ao, int32_t n_occ, int32_t n_aux, double exx, const double* B,
+                        const double* D, const double* C, double* J, double* K, char* route, int32_t route_len)
+{
+    if (!ctx || !B || !D || !C || !J || !K || !route || route_len < 1) return fail(MQC_HIP_ERR_VALIDATION, "df jk batch: null argument");
+    if (nfrag < 1) return fail(MQC_HIP_ERR_VALIDATION, "df jk batch: n_fragments must be at least 1");
+    if (n_ao < 1 || n_ao > 140) return fail(MQC_HIP_ERR_VALIDATION, "df jk batch: n_ao must be within 1..140");
+    if (n_occ < 1 || n_occ > n_ao) return fail(MQC_HIP_ERR_VALIDATION, "df jk batch: n_occ must be within 1..n_ao");
+    if (n_aux < 1) return fail(MQC_HIP_ERR_VALIDATION, "df jk batch: n_aux must be at least 1");
+    if (!(exx >= 0.0) || !std::isfinite(exx)) return fail(MQC_HIP_ERR_VALIDATION, "df jk batch: exx must be finite and not negative");
+    HIP_CHECK_RET(hipSetDevice(ctx->device));
+    route[0] = 0;
+    BatchPlan plan;
+    plan.n = n_ao; plan.npair = n_ao * (n_ao + 1) / 2; plan.natoms = 1;
+    plan.nalpha = plan.nbeta = plan.nocc = n_occ;
+    plan.two_e = TWO_E_DF; plan.naux = n_aux;
+    const int ntot = (int)std::min<int64_t>(nfrag, 1 << 30);
+    plan_layout(plan, ntot, 1, 0, false);
+    const size_t nn = (size_t)n_ao * n_ao, bstride = (size_t)n_aux * plan.npair;
+    constexpr size_t GUARD = 1024;         // bytes compared in front of J and behind K (S .. C in front, W behind: never less)
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    free_b += ctx->pool_main.capacity() + ctx->pool_df.capacity();
+    const int64_t chunk = stage_chunk_fragments(free_b, fragment_bytes(plan), nfrag);
+    const Slot sl0 = make_slot(ctx, 0, nullptr);
+    const TopologyDev td{};
+    hipStream_t s = ctx->stream;
+    int rc;
+    for (int64_t start = 0; start < nfrag; start += chunk) {
+        const int nf = (int)std::min<int64_t>(chunk, nfrag - start);
+        BatchView bv{};
+        bv.nalpha = bv.nbeta = bv.nocc = n_occ; bv.exx = exx;
+        if ((rc = carve_slot(ctx, sl0, plan, td, nf, bv)) != MQC_HIP_OK) return rc;
+        const size_t jk_bytes = sizeof(double) * (size_t)nf * nn;
+        unsigned char* lo = (unsigned char*)bv.J - GUARD;
+        unsigned char* mid = (unsigned char*)bv.J + jk_bytes;            // the padding between J and K (under 256 bytes)
+        unsigned char* hi = (unsigned char*)bv.K + jk_bytes;
+        const size_t pad = (size_t)((unsigned char*)bv.K - mid);
+        if (lo < (unsigned char*)bv.xyz || pad > 256) return fail(MQC_HIP_ERR_DEVICE, "df jk batch: J and K are not where the guard band expects them");
+        HIP_CHECK_RET(hipMemsetAsync(bv.istate, 0, sizeof(int) * (size_t)nf * 4, s));
+        HIP_CHECK_RET(hipMemcpyAsync(bv.df_b, B + (size_t)start * bstride, sizeof(double) * bstride * nf, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(bv.D, D + (size_t)start * nn, jk_bytes, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(bv.C, C + (size_t)start * nn, jk_bytes, hipMemcpyHostToDevice, s));
+        // Poison: an element the stage neither zeroes nor writes reads as NaN.  What the poison cannot show is a write
+        // OUTSIDE J and K: the bytes in front of J (the end of C), between the two and behind K (the start of W) do not
+        // change in a J/K launch and are compared across it.
+        HIP_CHECK_RET(hipMemsetAsync(bv.J, 0xFF, jk_bytes, s));
+        HIP_CHECK_RET(hipMemsetAsync(bv.K, 0xFF, jk_bytes, s));
+        if (pad) HIP_CHECK_RET(hipMemsetAsync(mid, 0xFF, pad, s));
+        HIP_CHECK_RET(hipMemsetAsync(hi, 0xFF, GUARD, s));
+        std::vector<unsigned char> before(2 * GUARD + 256), after(2 * GUARD + 256);
+        HIP_CHECK_RET(hipMemcpyAsync(before.data(), lo, GUARD, hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipMemcpyAsync(before.data() + GUARD, hi, GUARD, hipMemcpyDeviceToHost, s));
+        if (pad) HIP_CHECK_RET(hipMemcpyAsync(before.data() + 2 * GUARD, mid, pad, hipMemcpyDeviceToHost, s));
+        const DfJkRoute r = launch_df_jk(bv, false, s);
+        HIP_CHECK_RET(hipMemcpyAsync(after.data(), lo, GUARD, hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipMemcpyAsync(after.data() + GUARD, hi, GUARD, hipMemcpyDeviceToHost, s));
+        if (pad) HIP_CHECK_RET(hipMemcpyAsync(after.data() + 2 * GUARD, mid, pad, hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipMemcpyAsync(J + (size_t)start * nn, bv.J, jk_bytes, hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipMemcpyAsync(K + (size_t)start * nn, bv.K, jk_bytes, hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        if ((rc = stage_check("density-fitted J/K")) != MQC_HIP_OK) return rc;
+        if (std::memcmp(before.data(), after.data(), 2 * GUARD + pad) != 0)
+            return fail(MQC_HIP_ERR_DEVICE, "df jk batch: the stage wrote outside J and K");
+        if (r.family == DF_JK_WAVE) std::snprintf(route, (size_t)route_len, "wave<%d,%d>", r.a, r.b);
+        else if (r.family == DF_JK_MFMA) std::snprintf(route, (size_t)route_len, "mfma<%d,%d,%s>", r.a, r.b, r.flag ? "K" : "J");
+        else std::snprintf(route, (size_t)route_len, "v1<%d,%s>", r.a, r.flag ? "lds" : "global");
+    }
+    return MQC_HIP_OK;
+}
+
+// The build of the fitted tensor alone (include/mqc_hip.h): the plan and the arrays of a density-fitted SCF batch of
+// nfrag fragments, launch_df_integrals, the metric copied out, launch_df_fit -- the two halves of launch_df_build.
+int mqc_hip_df_fit_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols, const mqc_hip_basis_t* orbital,
+                         const mqc_hip_basis_t* aux, double* A3, double* metric, double* B, double* fit_flag)
+{
+    if (!ctx || !mols || !orbital || !aux || !A3 || !metric || !B || !fit_flag) return fail(MQC_HIP_ERR_VALIDATION, "df fit batch: null argument");
+    if (nfrag < 1) return fail(MQC_HIP_ERR_VALIDATION, "df fit batch: n_fragments must be at least 1");
+    HIP_CHECK_RET(hipSetDevice(ctx->device));
+    if (mols[0].n_atoms <= 0 || !same_elements(mols, nfrag))
+        return fail(MQC_HIP_ERR_VALIDATION, "df fit batch: every fragment must have the elements of the first (one topology per call)");
+    mqc_hip_scf_options_t opts;
+    mqc_hip_default_options(&opts);
+    opts.density_fitting = 1;
+    Topology topo, xtopo;
+    std::string msg;
+    int rc = build_topology(mols[0], *orbital, topo, msg, KERNEL_LMAX, false);
+    if (rc != MQC_HIP_OK) return fail(rc, msg);
+    if ((rc = build_topology(mols[0], *aux, xtopo, msg, AUX_LMAX, false)) != MQC_HIP_OK) return fail(rc, "auxiliary basis: " + msg);
+    const int ntot = (int)std::min<int64_t>(nfrag, 1 << 30);
+    BatchPlan plan;
+    if ((rc = plan_batch(opts, topo, ntot, plan, msg)) != MQC_HIP_OK) return fail(rc, msg);
+    plan.naux = xtopo.nao;
+    plan_layout(plan, ntot, (int)topo.shells.size(), topo.lmax, false);
+    TopologyDev td{}, tdx{};
+    if ((rc = upload_topology(ctx, topo, td)) != MQC_HIP_OK) return rc;
+    if ((rc = upload_topology(ctx, xtopo, tdx, &ctx->pool_aux)) != MQC_HIP_OK) return rc;
+    const size_t na = (size_t)xtopo.nao, a3 = na * (size_t)topo.npair, mm = na * na;
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    free_b += ctx->pool_main.capacity() + ctx->pool_df.capacity();
+    const int64_t chunk = stage_chunk_fragments(free_b, fragment_bytes(plan), nfrag);
+    const Slot sl0 = make_slot(ctx, 0, nullptr);
+    hipStream_t s = ctx->stream;
+    std::vector<double> hx, scal;
+    for (int64_t start = 0; start < nfrag; start += chunk) {
+        const int nf = (int)std::min<int64_t>(chunk, nfrag - start);
+        BatchView bv{};
+        bv.nalpha = plan.nalpha; bv.nbeta = plan.nbeta; bv.nocc = plan.nocc; bv.aux = tdx; bv.exx = 1.0;
+        if ((rc = carve_slot(ctx, sl0, plan, td, nf, bv)) != MQC_HIP_OK) return rc;
+        HIP_CHECK_RET(hipMemsetAsync(bv.scal, 0, sizeof(double) * (size_t)nf * 8, s));          // as prepare() does
+        gather_xyz(mols + start, nf, topo.natoms, hx);
+        HIP_CHECK_RET(hipMemcpyAsync(bv.xyz, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemsetAsync(bv.istate, 0, sizeof(int) * (size_t)nf * 4, s));
+        // poison: an element of (P|mu nu), of the metric or of the fitted tensor that no task covers reads as NaN
+        HIP_CHECK_RET(hipMemsetAsync(bv.df_a3, 0xFF, sizeof(double) * a3 * nf, s));
+        HIP_CHECK_RET(hipMemsetAsync(bv.df_metric, 0xFF, sizeof(double) * mm * nf, s));
+        HIP_CHECK_RET(hipMemsetAsync(bv.df_b, 0xFF, sizeof(double) * a3 * nf, s));
+        launch_df_integrals(bv, topo, xtopo, s);
+        if ((rc = stage_check("three- and two-centre integrals")) != MQC_HIP_OK) return rc;
+        // the factorisation overwrites the metric in place: it is copied out between the two halves
+        HIP_CHECK_RET(hipMemcpyAsync(metric + (size_t)start * mm, bv.df_metric, sizeof(double) * mm * nf, hipMemcpyDeviceToHost, s));
+        launch_df_fit(bv, s);
+        scal.resize((size_t)nf * 8);
+        HIP_CHECK_RET(hipMemcpyAsync(A3 + (size_t)start * a3, bv.df_a3, sizeof(double) * a3 * nf, hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipMemcpyAsync(B + (size_t)start * a3, bv.df_b, sizeof(double) * a3 * nf, hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipMemcpyAsync(scal.data(), bv.scal, sizeof(double) * scal.size(), hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));
+        if ((rc = stage_check("density fit")) != MQC_HIP_OK) return rc;
+        for (int f = 0; f < nf; ++f) fit_flag[start + f] = scal[8 * (size_t)f + 7];
+    }
+    return MQC_HIP_OK;
+}
+
 int mqc_hip_syev(mqc_hip_context* ctx, int32_t n, const double* A, double* w, double* V)
 {
     if (!ctx || !A || !w || !V || n <= 0) return fail(MQC_HIP_ERR_VALIDATION, "bad arguments");

@@ -1,5 +1,5 @@
 """Stage-level entry points of the C ABI (mqc_hip_int1e, _eri_packed, _eri_packed_attenuated, _jk_incore, _jk_direct,
-_coulomb_batch, _xc_batch, _syev, _diis_coefficients) as numpy-in / numpy-out functions.  They run the same kernels the SCF
+_coulomb_batch, _xc_batch, _df_jk_batch, _df_fit_batch, _syev, _diis_coefficients) as numpy-in / numpy-out functions.  They run the same kernels the SCF
 driver launches and exist so that each row of the hot-path table can be parity-tested alone.
 Test infrastructure: a ctypes helper for tests/, not part of the product package."""
 from __future__ import annotations
@@ -115,3 +115,44 @@ def xc_batch(basis_set: str, fragments, functional: str, D: np.ndarray, grid_lev
                                                     int(grid_level), 1 if unrestricted else 0, capi.dptr(D), capi.dptr(e), capi.dptr(nel),
                                                     capi.dptr(V)))
     return e, nel, V
+
+
+def df_jk_batch(B: np.ndarray, D: np.ndarray, C_mo: np.ndarray, n_occ: int, exx: float = 1.0):
+    """mqc_hip_df_jk_batch: B (m, n_aux, npair) packed pairs fastest, D and C (m, n, n) -> J, K (m, n, n) and the name
+    of the kernel instance the dispatch chose.  J and K come back as NaN wherever the engine did not write."""
+    B = np.ascontiguousarray(B, dtype=np.float64)
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    C_mo = np.ascontiguousarray(C_mo, dtype=np.float64)
+    m, n = D.shape[0], D.shape[-1]
+    assert B.shape[0] == m and B.shape[2] == n * (n + 1) // 2 and C_mo.shape == D.shape
+    J, K = np.full_like(D, np.nan), np.full_like(D, np.nan)
+    route = C.create_string_buffer(32)
+    capi.check(capi.load_library().mqc_hip_df_jk_batch(capi.get_context(), m, n, int(n_occ), B.shape[1], C.c_double(exx), capi.dptr(B),
+                                                       capi.dptr(D), capi.dptr(C_mo), capi.dptr(J), capi.dptr(K), route, len(route)))
+    return J, K, route.value.decode()
+
+
+def df_fit_batch(basis_set: str, aux_basis_set: str, fragments):
+    """mqc_hip_df_fit_batch for fragments of one element sequence -> A3 (m, n_aux, npair), the metric (m, n_aux, n_aux),
+    the fitted B (m, n_aux, npair), the fit flags (m,).  NaN wherever the engine did not write."""
+    ms = [_marshal(basis_set, f) for f in fragments]
+    xs = [_marshal(aux_basis_set, f) for f in fragments]
+    mols = (capi.Molecule * len(ms))(*[m.mol for m in ms])
+    m, n, na = len(ms), ms[0].fb.nao, xs[0].fb.nao
+    npair = n * (n + 1) // 2
+    A3, B = np.full((m, na, npair), np.nan), np.full((m, na, npair), np.nan)
+    M, flag = np.full((m, na, na), np.nan), np.full(m, np.nan)
+    capi.check(capi.load_library().mqc_hip_df_fit_batch(capi.get_context(), m, mols, C.byref(ms[0].bas), C.byref(xs[0].bas),
+                                                        capi.dptr(A3), capi.dptr(M), capi.dptr(B), capi.dptr(flag)))
+    return A3, M, B, flag
+
+
+def unpack_pairs(P: np.ndarray) -> np.ndarray:
+    """(..., npair) packed pairs (mu >= nu, index mu (mu + 1) / 2 + nu) -> the symmetric (..., n, n)."""
+    npair = P.shape[-1]
+    n = int((np.sqrt(8 * npair + 1) - 1) / 2)
+    ii, jj = np.tril_indices(n)
+    out = np.zeros(P.shape[:-1] + (n, n), dtype=P.dtype)
+    out[..., ii, jj] = P
+    out[..., jj, ii] = P
+    return out
