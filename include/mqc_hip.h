@@ -274,6 +274,40 @@ int mqc_hip_df_jk_batch(mqc_hip_context *ctx, int64_t n_fragments, int32_t n_ao,
                         const double *B, const double *D, const double *C, double *J, double *K,
                         char *route, int32_t route_len);
 
+/* The layout of the in-core tensor an SCF batch of n_fragments fragments of n_ao functions gets (host only, no device
+ * call): triangular = 1 for the triangular block layout (block t = [pair row npair-1-t | pair row t], each padded with
+ * zeros to the end of its last row of the packed triangle, diagonal elements halved), block_doubles its block length (0
+ * for the square), stride_doubles the doubles per fragment (npair^2, or (npair + 1) / 2 blocks).
+ * MQC_HIP_ERR_VALIDATION: null pointers, n_ao or n_fragments < 1.  (Added without an ABI bump: no struct changed.) */
+int mqc_hip_jk_tensor_layout(int32_t n_ao, int64_t n_fragments, int32_t unrestricted, int32_t *triangular,
+                             int64_t *block_doubles, int64_t *stride_doubles);
+
+/* The in-core J/K stage on GIVEN tensors, for n_fragments of one shape: what one SCF iteration's J/K stream computes,
+ * alone.  No molecule: the kernels read the sizes, the tensor, D and the fragment states only.
+ *     tensor [n][stride]     the pair matrix as stored, stride and layout as mqc_hip_jk_tensor_layout reports them
+ *     D [n][n_ao*n_ao]       the (symmetric) density
+ *     done [n] or NULL       non-zero: the fragment is marked finished and the launch is made with only_active set
+ *     J, K [n][n_ao*n_ao]    J_ij = sum_kl (ij|kl) D_kl, K_ik = sum_jl (ij|kl) D_jl
+ *     loaded [n]             chunks of 128 doubles the triangular kernel read per fragment (-1: the plan has no counter,
+ *                            or the fragment was finished and one workgroup per fragment ran)
+ * n_shells > 0 adds the zero-row screening of the triangular kernel: shell_l [n_shells] (2l + 1 functions each, n_ao in
+ * all, n_ao <= 64), Q [n][n_shells*n_shells] and q_thresh; a pair row whose shell pair has Q times the fragment's
+ * largest Q below q_thresh must be all zeros as stored, and is neither loaded nor contracted.
+ * The arrays are those of an in-core SCF batch of this shape (plain or unrestricted; unrestricted runs the alpha view)
+ * and the SCF driver's own dispatch runs once over all fragments; route (route_len bytes, NUL-terminated) receives the
+ * kernel it chose -- wave<KCH,lds|global,NW,MAXU,reg|mem[,full8]>, rowcoop<2,8> or tri<12,10> -- and grid_x the x extent
+ * of its grid.  J and K are poisoned before the launch and their neighbours in the pool are compared before and after
+ * (MQC_HIP_ERR_DEVICE when the stage wrote outside).  The launchers zero K -- and with several workgroups per fragment
+ * on the triangle J too -- for the WHOLE batch: an element of a finished fragment comes back as the poison or as zero.
+ * MQC_HIP_ERR_VALIDATION: null pointers, n_fragments < 1, n_ao < 1 or beyond the in-core limit (116), a stride that is
+ * not the layout's, shell_l that does not add up to n_ao, screening with n_ao > 64.
+ * (Added without an ABI bump: no struct changed.) */
+int mqc_hip_jk_incore_batch(mqc_hip_context *ctx, int64_t n_fragments, int32_t n_ao, int32_t unrestricted,
+                            const double *tensor, int64_t stride, const double *D, const int32_t *done /* or NULL */,
+                            int32_t n_shells /* 0: no screening */, const int32_t *shell_l, const double *Q, double q_thresh,
+                            double *J, double *K, int32_t *loaded /* [n] */, char *route, int32_t route_len,
+                            int32_t *grid_x);
+
 /* The build of the fitted tensor alone, for MANY fragments of ONE topology: the integral half and the fit half of a
  * density-fitted SCF's build stage, with the metric copied out between them (the factor overwrites it in place).
  *     A3 [n][n_aux][npair]       (P|mu nu)

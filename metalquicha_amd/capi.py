@@ -83,6 +83,7 @@ DECLARED_SYMBOLS = [
     "mqc_hip_diis_coefficients", "mqc_hip_get_stats", "mqc_hip_device_name", "mqc_hip_eri_packed_attenuated",
     "mqc_hip_jk_direct", "mqc_hip_esp_batch", "mqc_hip_xc_batch", "mqc_hip_scf_gradient_embedded_batch",
     "mqc_hip_scf_run_batch_restart", "mqc_hip_rimp2_batch", "mqc_hip_df_jk_batch", "mqc_hip_df_fit_batch",
+    "mqc_hip_jk_tensor_layout", "mqc_hip_jk_incore_batch",
 ]
 
 _lib = None
@@ -133,6 +134,10 @@ def load_library():
                                         c_double_p, c_double_p, c_double_p, C.c_char_p, C.c_int32]
     lib.mqc_hip_df_fit_batch.argtypes = [C.c_void_p, C.c_int64, C.POINTER(Molecule), C.POINTER(Basis), C.POINTER(Basis), c_double_p,
                                          c_double_p, c_double_p, c_double_p]
+    lib.mqc_hip_jk_tensor_layout.argtypes = [C.c_int32, C.c_int64, C.c_int32, c_int32_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.mqc_hip_jk_incore_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, c_double_p, C.c_int64, c_double_p, c_int32_p,
+                                            C.c_int32, c_int32_p, c_double_p, C.c_double, c_double_p, c_double_p, c_int32_p, C.c_char_p,
+                                            C.c_int32, c_int32_p]
     lib.mqc_hip_syev.argtypes = [C.c_void_p, C.c_int32, c_double_p, c_double_p, c_double_p]
     lib.mqc_hip_diis_coefficients.argtypes = [C.c_void_p, C.c_int32, c_double_p, c_double_p, c_int32_p]
     lib.mqc_hip_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]

@@ -371,7 +371,16 @@ bool launch_eri_general(const BatchView& bv, int la, int lb, int lc, int ld, con
 bool launch_df3c_general(const BatchView& bv, int la, int lb, int lp, const int* d_list, int nq, hipStream_t s);
 bool launch_schwarz_general(const BatchView& bv, int la, int lb, const int* d_pairs, int npairs, double* Qout, hipStream_t s);
 void eri_set_side_streams(int slot, const hipStream_t* streams, int count);
-void launch_jk_incore(const BatchView& bv, bool only_active, hipStream_t s);
+// The kernel launch_jk_incore chose: wave<KCH,lds|global,NW,MAXU,reg|mem[,full8]> (jk_incore_kernel: K accumulated in
+// LDS or in global memory, density rows through registers or memory) | rowcoop<2,8> | tri<12,10>, and the x extent of
+// its grid.  The SCF driver ignores it; mqc_hip_jk_incore_batch reports it.
+enum : int { JK_WAVE = 0, JK_ROWCOOP = 1, JK_TRI = 2 };
+struct JkRoute {
+    int family, kch, nw, maxu;
+    bool klds, dreg, full8;
+    int grid_x;
+};
+JkRoute launch_jk_incore(const BatchView& bv, bool only_active, hipStream_t s);
 // K <- exx K + exx_lr K_lr for every fragment not yet done (range-separated hybrids, before the SCF step)
 void launch_exchange_fold(const BatchView& bv, double* K, const double* Klr, double exx, double exx_lr, hipStream_t s);
 void launch_direct_setup(const BatchView& bv, const Topology& topo, hipStream_t s);

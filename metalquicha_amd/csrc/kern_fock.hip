@@ -744,12 +744,13 @@ static int jk_grid_x(const BatchView& bv, int nw)
 }
 
 template <int KCH, bool KLDS, int NW, int MAXU, bool DREG, bool FULL8 = false>
-static void jk_launch(const BatchView& bv, int oa, size_t lds, hipStream_t s)
+static JkRoute jk_launch(const BatchView& bv, int oa, size_t lds, hipStream_t s)
 {
     auto kern = jk_incore_kernel<KCH, KLDS, NW, MAXU, DREG, FULL8>;
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     dim3 grid(jk_grid_x(bv, NW), bv.nfrag), block(64 * NW);
     hipLaunchKernelGGL(kern, grid, block, lds, s, bv, oa);
+    return {JK_WAVE, KCH, NW, MAXU, KLDS, DREG, FULL8, (int)grid.x};
 }
 
 static bool jk_rowcoop_on()
@@ -776,7 +777,7 @@ void launch_exchange_fold(const BatchView& bv, double* K, const double* Klr, dou
     hipLaunchKernelGGL(exchange_fold_kernel, dim3((unsigned)((nn + 255) / 256), (unsigned)bv.nfrag), dim3(256), 0, s, bv, K, Klr, exx, exx_lr);
 }
 
-void launch_jk_incore(const BatchView& bv, bool only_active, hipStream_t s)
+JkRoute launch_jk_incore(const BatchView& bv, bool only_active, hipStream_t s)
 {
     const int n = bv.n, np = bv.npair;
     if (bv.eri_tri) {
@@ -798,7 +799,7 @@ void launch_jk_incore(const BatchView& bv, bool only_active, hipStream_t s)
             (void)hipMemsetAsync(bv.J, 0, sizeof(double) * (size_t)bv.nfrag * n * n, s);
         }
         hipLaunchKernelGGL(kern, dim3(gx, bv.nfrag), dim3(64 * JK_TRI_NW), lds, s, bv, only_active ? 1 : 0);
-        return;
+        return {JK_TRI, 1, JK_TRI_NW, JK_TRI_MAXU2, true, true, false, gx};
     }
     (void)hipMemsetAsync(bv.K, 0, sizeof(double) * (size_t)bv.nfrag * n * n, s);
     const int kch = (n + 63) / 64;
@@ -813,18 +814,18 @@ void launch_jk_incore(const BatchView& bv, bool only_active, hipStream_t s)
     if (n <= 64 && np <= 19 * 64 && np > 5 * 64 && lds_reg12 <= LDS_MAX && bv.nfrag >= 64) {
         // dimer-sized fragments in a large batch: one 12-wave workgroup per CU (141 KB of LDS for n = 48)
         // keeps 12 x 9.4 KB of row loads in flight per CU instead of 8 x
-        if (np <= 10 * 64) jk_launch<1, true, 12, 10, true>(bv, oa, lds_reg12, s);
+        if (np <= 10 * 64) return jk_launch<1, true, 12, 10, true>(bv, oa, lds_reg12, s);
         else if (n % 8 == 0 && np % 2 == 0 && sizeof(double) * ((size_t)12 * 10 * 128 + np + (size_t)n * n) <= LDS_MAX)
-            jk_launch<1, true, 12, 19, true, true>(bv, oa, sizeof(double) * ((size_t)12 * 10 * 128 + np + (size_t)n * n), s);
-        else jk_launch<1, true, 12, 19, true>(bv, oa, lds_reg12, s);
+            return jk_launch<1, true, 12, 19, true, true>(bv, oa, sizeof(double) * ((size_t)12 * 10 * 128 + np + (size_t)n * n), s);
+        else return jk_launch<1, true, 12, 19, true>(bv, oa, lds_reg12, s);
     } else if (n <= 64 && lds_reg <= LDS_MAX) {
         // the fragment sizes of an MBE run (n = 48: 65.5 KB -> two workgroups per CU)
-        if (np <= 5 * 64) jk_launch<1, true, 4, 5, true>(bv, oa, lds_reg, s);
-        else if (np <= 10 * 64) jk_launch<1, true, 4, 10, true>(bv, oa, lds_reg, s);
-        else if (np <= 19 * 64) jk_launch<1, true, 4, 19, true>(bv, oa, lds_reg, s);
-        else jk_launch<1, true, 4, 0, true>(bv, oa, lds_reg, s);
+        if (np <= 5 * 64) return jk_launch<1, true, 4, 5, true>(bv, oa, lds_reg, s);
+        else if (np <= 10 * 64) return jk_launch<1, true, 4, 10, true>(bv, oa, lds_reg, s);
+        else if (np <= 19 * 64) return jk_launch<1, true, 4, 19, true>(bv, oa, lds_reg, s);
+        else return jk_launch<1, true, 4, 0, true>(bv, oa, lds_reg, s);
     } else if (lds4k <= LDS_MAX && kch <= 2) {
-        jk_launch<2, true, 4, 0, false>(bv, oa, lds4k, s);
+        return jk_launch<2, true, 4, 0, false>(bv, oa, lds4k, s);
     } else if (kch == 2 && np <= 8 * JKC_NT && sizeof(double) * ((size_t)3 * 8 * JKC_NT + (size_t)n * n + 2 * JKC_NW) <= LDS_MAX && jk_rowcoop_on()) {
         // 64 < n <= 89: rows up to 32 KB, the workgroup-cooperative kernel
         const size_t lds = sizeof(double) * ((size_t)3 * 8 * JKC_NT + (size_t)n * n + 2 * JKC_NW);
@@ -834,14 +835,15 @@ void launch_jk_incore(const BatchView& bv, bool only_active, hipStream_t s)
         if (gx < 1) gx = 1;
         if (gx > np) gx = np;
         hipLaunchKernelGGL(kern, dim3(gx, bv.nfrag), dim3(JKC_NT), lds, s, bv, oa);
+        return {JK_ROWCOOP, 2, JKC_NW, 8, true, false, false, gx};
     } else if (lds4 <= LDS_MAX) {
-        if (kch <= 2) jk_launch<2, false, 4, 0, false>(bv, oa, lds4, s);
-        else if (kch == 3) jk_launch<3, false, 4, 0, false>(bv, oa, lds4, s);
-        else jk_launch<4, false, 4, 0, false>(bv, oa, lds4, s);
+        if (kch <= 2) return jk_launch<2, false, 4, 0, false>(bv, oa, lds4, s);
+        else if (kch == 3) return jk_launch<3, false, 4, 0, false>(bv, oa, lds4, s);
+        else return jk_launch<4, false, 4, 0, false>(bv, oa, lds4, s);
     } else {
-        if (kch <= 2) jk_launch<2, false, 2, 0, false>(bv, oa, lds2, s);
-        else if (kch == 3) jk_launch<3, false, 2, 0, false>(bv, oa, lds2, s);
-        else jk_launch<4, false, 2, 0, false>(bv, oa, lds2, s);
+        if (kch <= 2) return jk_launch<2, false, 2, 0, false>(bv, oa, lds2, s);
+        else if (kch == 3) return jk_launch<3, false, 2, 0, false>(bv, oa, lds2, s);
+        else return jk_launch<4, false, 2, 0, false>(bv, oa, lds2, s);
     }
 }
 

@@ -516,6 +516,141 @@ int mqc_hip_df_jk_batch(mqc_hip_context* ctx, int64_t nfrag, int32_t n_ao, int32
     return MQC_HIP_OK;
 }
 
+// the plan of an in-core SCF batch of ntot fragments of n functions: plan_layout picks the square or the triangle
+static BatchPlan jk_incore_plan(int n, int ntot, bool uhf)
+{
+    BatchPlan plan;
+    plan.n = n; plan.npair = n * (n + 1) / 2; plan.natoms = 1;
+    plan.uhf = uhf;
+    plan.nalpha = plan.nbeta = plan.nocc = 1;
+    plan.two_e = TWO_E_INCORE;
+    plan_layout(plan, ntot, 1, 0, false);
+    return plan;
+}
+
+int mqc_hip_jk_tensor_layout(int32_t n_ao, int64_t nfrag, int32_t unrestricted, int32_t* triangular, int64_t* block_doubles,
+                             int64_t* stride_doubles)
+{
+    if (!triangular || !block_doubles || !stride_doubles) return fail(MQC_HIP_ERR_VALIDATION, "jk tensor layout: null argument");
+    if (n_ao < 1 || n_ao > 256 || nfrag < 1) return fail(MQC_HIP_ERR_VALIDATION, "jk tensor layout: n_ao must be within 1..256 and n_fragments at least 1");
+    const BatchPlan plan = jk_incore_plan(n_ao, (int)std::min<int64_t>(nfrag, 1 << 30), unrestricted != 0);
+    BatchView probe{};
+    carve_chunk(plan, 1, nullptr, probe);
+    *triangular = probe.eri_tri;
+    *block_doubles = probe.eri_tri_pb;
+    *stride_doubles = (int64_t)probe.eri_stride;
+    return MQC_HIP_OK;
+}
+
+// The in-core J/K stage of an SCF iteration on given tensors (include/mqc_hip.h).  No molecule: the kernels read n, npair,
+// the tensor with its layout, D, istate and -- the triangle under screening -- three fields of the topology (nshell,
+// sh_aoff, sh_l), the bounds and their threshold.  The arrays are the ones carve_slot gives an in-core batch of this
+// shape (the layout is plan_layout's choice, the block table carve_slot's upload), and launch_jk_incore runs once over
+// all fragments, as jk_one runs it.  The launchers zero K, and for the triangle with several workgroups per fragment
+// J too, with one memset over the WHOLE batch: an element of a finished fragment (done[f] != 0) comes back as the
+// poison or as zero, never as anything else.
+int mqc_hip_jk_incore_batch(mqc_hip_context* ctx, int64_t nfrag, int32_t n_ao, int32_t unrestricted, const double* tensor, int64_t stride,
+                            const double* D, const int32_t* done, int32_t n_shells, const int32_t* shell_l, const double* Q, double q_thresh,
+                            double* J, double* K, int32_t* loaded, char* route, int32_t route_len, int32_t* grid_x)
+{
+    if (!ctx || !tensor || !D || !J || !K || !loaded || !route || route_len < 1 || !grid_x) return fail(MQC_HIP_ERR_VALIDATION, "jk incore batch: null argument");
+    if (nfrag < 1 || nfrag > (1 << 20)) return fail(MQC_HIP_ERR_VALIDATION, "jk incore batch: n_fragments must be within 1..2^20");
+    if (n_ao < 1 || !incore_supported(n_ao)) return fail(MQC_HIP_ERR_VALIDATION, "jk incore batch: n_ao must be within 1..116 (the in-core limit)");
+    const bool screen = n_shells != 0;
+    std::vector<int> sh_l, sh_aoff;
+    if (screen) {
+        if (n_shells < 0 || !shell_l || !Q) return fail(MQC_HIP_ERR_VALIDATION, "jk incore batch: screening needs shell_l and Q");
+        if (n_ao > 64) return fail(MQC_HIP_ERR_VALIDATION, "jk incore batch: screening is for n_ao <= 64 (the triangular kernel)");
+        if (!std::isfinite(q_thresh)) return fail(MQC_HIP_ERR_VALIDATION, "jk incore batch: q_thresh must be finite");
+        int64_t fun = 0;
+        for (int k = 0; k < n_shells; ++k) {
+            if (shell_l[k] < 0 || shell_l[k] > 32) return fail(MQC_HIP_ERR_VALIDATION, "jk incore batch: shell_l out of range");
+            sh_l.push_back(shell_l[k]); sh_aoff.push_back((int)fun);
+            fun += 2 * shell_l[k] + 1;
+            if (fun > n_ao) break;
+        }
+        if (fun != n_ao) return fail(MQC_HIP_ERR_VALIDATION, "jk incore batch: shell_l does not add up to n_ao functions");
+    }
+    const int nf = (int)nfrag, n = n_ao;
+    const BatchPlan plan = jk_incore_plan(n, nf, unrestricted != 0);
+    {
+        BatchView probe{};
+        carve_chunk(plan, 1, nullptr, probe);
+        if (stride < 0 || (size_t)stride != probe.eri_stride)
+            return fail(MQC_HIP_ERR_VALIDATION, "jk incore batch: stride " + std::to_string(stride) + " is not the layout's (" +
+                                                    std::to_string(probe.eri_stride) + " doubles per fragment, mqc_hip_jk_tensor_layout)");
+    }
+    HIP_CHECK_RET(hipSetDevice(ctx->device));
+    route[0] = 0; *grid_x = 0;
+    const size_t nn = (size_t)n * n;
+    constexpr size_t GUARD = 1024;         // bytes compared in front of J and behind K (S .. C in front, W behind: never less)
+    const Slot sl0 = make_slot(ctx, 0, nullptr);
+    hipStream_t s = ctx->stream;
+    int rc;
+    // one chunk: the dispatch depends on the number of fragments of the launch.  A batch beyond the memory is refused.
+    BatchView bv{};
+    bv.nalpha = bv.nbeta = bv.nocc = 1; bv.exx = 1.0;
+    TopologyDev td{};
+    const double* jk_q = nullptr;
+    if (screen) {
+        // the three fields of the topology jk_tri_kernel reads, and the bounds behind them
+        auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const size_t ib = up(sizeof(int) * (size_t)n_shells), qb = sizeof(double) * (size_t)nf * n_shells * n_shells;
+        char* base = (char*)ctx->pool_topo.ensure(2 * ib + up(qb));
+        if (!base) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (screening tables)");
+        td.sh_l = (int*)base; td.sh_aoff = (int*)(base + ib);
+        td.nshell = n_shells; td.nao = n; td.npair = plan.npair; td.natoms = 1;
+        HIP_CHECK_RET(hipMemcpyAsync(td.sh_l, sh_l.data(), sizeof(int) * (size_t)n_shells, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(td.sh_aoff, sh_aoff.data(), sizeof(int) * (size_t)n_shells, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(base + 2 * ib, Q, qb, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));    // the caller's Q and the host tables are done with
+        jk_q = (const double*)(base + 2 * ib);
+    }
+    if ((rc = carve_slot(ctx, sl0, plan, td, nf, bv)) != MQC_HIP_OK) return rc;
+    bv.jk_q = jk_q; bv.jk_qthresh = q_thresh;
+    const size_t jk_bytes = sizeof(double) * (size_t)nf * nn;
+    unsigned char* lo = (unsigned char*)bv.J - GUARD;
+    unsigned char* mid = (unsigned char*)bv.J + jk_bytes;            // the padding between J and K (under 256 bytes)
+    unsigned char* hi = (unsigned char*)bv.K + jk_bytes;
+    const size_t pad = (size_t)((unsigned char*)bv.K - mid);
+    if (lo < (unsigned char*)bv.xyz || pad > 256 || hi + GUARD > (unsigned char*)bv.diis_state)
+        return fail(MQC_HIP_ERR_DEVICE, "jk incore batch: J and K are not where the guard band expects them");
+    // Poison first (the band behind K reaches into the work matrices, nothing the launch reads), then the inputs
+    HIP_CHECK_RET(hipMemsetAsync(bv.J, 0xFF, jk_bytes, s));
+    HIP_CHECK_RET(hipMemsetAsync(bv.K, 0xFF, jk_bytes, s));
+    if (pad) HIP_CHECK_RET(hipMemsetAsync(mid, 0xFF, pad, s));
+    HIP_CHECK_RET(hipMemsetAsync(hi, 0xFF, GUARD, s));
+    if (bv.jk_loaded) HIP_CHECK_RET(hipMemsetAsync(bv.jk_loaded, 0xFF, sizeof(int) * (size_t)nf, s));
+    std::vector<int> ist((size_t)nf * 4, 0);
+    for (int f = 0; f < nf && done; ++f)
+        if (done[f]) ist[4 * (size_t)f] = ST_DONE;
+    HIP_CHECK_RET(hipMemcpyAsync(bv.istate, ist.data(), sizeof(int) * ist.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemcpyAsync(bv.eri, tensor, sizeof(double) * (size_t)nf * bv.eri_stride, hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemcpyAsync(bv.D, D, jk_bytes, hipMemcpyHostToDevice, s));
+    std::vector<unsigned char> before(2 * GUARD + 256), after(2 * GUARD + 256);
+    HIP_CHECK_RET(hipMemcpyAsync(before.data(), lo, GUARD, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipMemcpyAsync(before.data() + GUARD, hi, GUARD, hipMemcpyDeviceToHost, s));
+    if (pad) HIP_CHECK_RET(hipMemcpyAsync(before.data() + 2 * GUARD, mid, pad, hipMemcpyDeviceToHost, s));
+    const JkRoute r = launch_jk_incore(bv, done != nullptr, s);
+    HIP_CHECK_RET(hipMemcpyAsync(after.data(), lo, GUARD, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipMemcpyAsync(after.data() + GUARD, hi, GUARD, hipMemcpyDeviceToHost, s));
+    if (pad) HIP_CHECK_RET(hipMemcpyAsync(after.data() + 2 * GUARD, mid, pad, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipMemcpyAsync(J, bv.J, jk_bytes, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipMemcpyAsync(K, bv.K, jk_bytes, hipMemcpyDeviceToHost, s));
+    if (bv.jk_loaded) HIP_CHECK_RET(hipMemcpyAsync(loaded, bv.jk_loaded, sizeof(int) * (size_t)nf, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    if ((rc = stage_check("in-core J/K")) != MQC_HIP_OK) return rc;
+    if (!bv.jk_loaded) std::fill(loaded, loaded + nf, -1);
+    if (std::memcmp(before.data(), after.data(), 2 * GUARD + pad) != 0)
+        return fail(MQC_HIP_ERR_DEVICE, "jk incore batch: the stage wrote outside J and K");
+    if (r.family == JK_TRI) std::snprintf(route, (size_t)route_len, "tri<%d,%d>", r.nw, r.maxu);
+    else if (r.family == JK_ROWCOOP) std::snprintf(route, (size_t)route_len, "rowcoop<%d,%d>", r.kch, r.maxu);
+    else std::snprintf(route, (size_t)route_len, "wave<%d,%s,%d,%d,%s%s>", r.kch, r.klds ? "lds" : "global", r.nw, r.maxu, r.dreg ? "reg" : "mem",
+                       r.full8 ? ",full8" : "");
+    *grid_x = r.grid_x;
+    return MQC_HIP_OK;
+}
+
 // The build of the fitted tensor alone (include/mqc_hip.h): the plan and the arrays of a density-fitted SCF batch of
 // nfrag fragments, launch_df_integrals, the metric copied out, launch_df_fit -- the two halves of launch_df_build.
 int mqc_hip_df_fit_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols, const mqc_hip_basis_t* orbital,

@@ -372,6 +372,21 @@ int hostcheck_carve(const int* spec, int nfrag, unsigned long long* pool_bytes, 
     return 0;
 }
 
+// The triangular J/K layout as the engine decides it (host_setup.cpp): the block length of npair pair rows with its
+// table ([(npair + 1) / 2] short-row starts, then [npair] the row of the packed triangle of every pair row; table may be
+// null), whether a batch takes the triangle, and the triangular kernel's LDS bytes.
+int hostcheck_jk_tri_block(int npair, int* table)
+{
+    std::vector<int> t;
+    const int pb = jk_tri_block(npair, table ? &t : nullptr);
+    if (table) std::memcpy(table, t.data(), sizeof(int) * t.size());
+    return pb;
+}
+
+int hostcheck_jk_tri_layout(int n, int nfrag, int uhf) { return jk_tri_layout(n, n * (n + 1) / 2, nfrag, uhf != 0) ? 1 : 0; }
+
+unsigned long long hostcheck_jk_tri_lds_bytes(int n) { return jk_tri_lds_bytes(n, n * (n + 1) / 2); }
+
 // the chunk size of the batched stage entries (mqc_hip_coulomb_batch, _esp_batch, _xc_batch)
 long long hostcheck_stage_chunk(unsigned long long free_bytes, unsigned long long per_fragment, long long nfrag, long long cap)
 {

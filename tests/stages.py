@@ -1,5 +1,5 @@
 """Stage-level entry points of the C ABI (mqc_hip_int1e, _eri_packed, _eri_packed_attenuated, _jk_incore, _jk_direct,
-_coulomb_batch, _xc_batch, _df_jk_batch, _df_fit_batch, _syev, _diis_coefficients) as numpy-in / numpy-out functions.  They run the same kernels the SCF
+_coulomb_batch, _xc_batch, _df_jk_batch, _df_fit_batch, _jk_tensor_layout, _jk_incore_batch, _syev, _diis_coefficients) as numpy-in / numpy-out functions.  They run the same kernels the SCF
 driver launches and exist so that each row of the hot-path table can be parity-tested alone.
 Test infrastructure: a ctypes helper for tests/, not part of the product package."""
 from __future__ import annotations
@@ -145,6 +145,38 @@ def df_fit_batch(basis_set: str, aux_basis_set: str, fragments):
     capi.check(capi.load_library().mqc_hip_df_fit_batch(capi.get_context(), m, mols, C.byref(ms[0].bas), C.byref(xs[0].bas),
                                                         capi.dptr(A3), capi.dptr(M), capi.dptr(B), capi.dptr(flag)))
     return A3, M, B, flag
+
+
+def jk_tensor_layout(n: int, nfrag: int, unrestricted: bool = False):
+    """mqc_hip_jk_tensor_layout (host only, no context): (triangular, doubles per block, doubles per fragment) of the
+    in-core tensor of an SCF batch of nfrag fragments of n functions."""
+    tri, pb, stride = C.c_int32(-1), C.c_int64(-1), C.c_int64(-1)
+    capi.check(capi.load_library().mqc_hip_jk_tensor_layout(int(n), int(nfrag), 1 if unrestricted else 0, C.byref(tri), C.byref(pb),
+                                                            C.byref(stride)))
+    return bool(tri.value), pb.value, stride.value
+
+
+def jk_incore_batch(tensor: np.ndarray, D: np.ndarray, unrestricted: bool = False, done=None, shell_l=None, Q=None, q_thresh: float = 0.0):
+    """mqc_hip_jk_incore_batch: tensor (m, stride) as stored, D (m, n, n) -> J, K (m, n, n), loaded (m,), the name of the
+    kernel instance the dispatch chose and the x extent of its grid.  J and K come back as NaN wherever the engine did
+    not write.  done (m,): fragments marked finished (the launch then runs with only_active); shell_l, Q (m, ns, ns),
+    q_thresh: the zero-row screening of the triangular kernel."""
+    tensor = np.ascontiguousarray(tensor, dtype=np.float64)
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    m, n = D.shape[0], D.shape[-1]
+    assert tensor.ndim == 2 and tensor.shape[0] == m
+    J, K = np.full_like(D, np.nan), np.full_like(D, np.nan)
+    loaded = np.full(m, -2, dtype=np.int32)
+    route, gx = C.create_string_buffer(48), C.c_int32(0)
+    ip = lambda a: a.ctypes.data_as(capi.c_int32_p)
+    dn = None if done is None else np.ascontiguousarray(done, dtype=np.int32)
+    sl = None if shell_l is None else np.ascontiguousarray(shell_l, dtype=np.int32)
+    q = None if Q is None else np.ascontiguousarray(Q, dtype=np.float64)
+    capi.check(capi.load_library().mqc_hip_jk_incore_batch(
+        capi.get_context(), m, n, 1 if unrestricted else 0, capi.dptr(tensor), tensor.shape[1], capi.dptr(D), None if dn is None else ip(dn),
+        0 if sl is None else len(sl), None if sl is None else ip(sl), None if q is None else capi.dptr(q), C.c_double(q_thresh),
+        capi.dptr(J), capi.dptr(K), ip(loaded), route, len(route), C.byref(gx)))
+    return J, K, loaded, route.value.decode(), gx.value
 
 
 def unpack_pairs(P: np.ndarray) -> np.ndarray:
