@@ -106,7 +106,7 @@ __device__ __forceinline__ void row_exchange(const double* __restrict__ rowbuf, 
 #pragma unroll
                 for (int c = 0; c < KCH; ++c) {
                     const int ia = tri[c] + l, ib = lbase + kk[c];
-                    const int idx = ia > ib ? ia : ib;      // tri(max) + min is the larger of the two forms (see row_exchange_tri)
+                    const int idx = ia > ib ? ia : ib;      // tri(max) + min is the larger of the two forms (see exchange_read_full)
                     v[u][c] = rowbuf[idx];
                 }
                 lbase += l + 1;
@@ -119,7 +119,7 @@ __device__ __forceinline__ void row_exchange(const double* __restrict__ rowbuf, 
 #pragma unroll
                 for (int c = 0; c < KCH; ++c) {
                     const int ia = tri[c] + l, ib = lbase + kk[c];
-                    const int idx = ia > ib ? ia : ib;      // tri(max) + min is the larger of the two forms (see row_exchange_tri)
+                    const int idx = ia > ib ? ia : ib;      // tri(max) + min is the larger of the two forms (see exchange_read_full)
                     v[u][c] = rowbuf[idx];
                 }
             }
@@ -452,62 +452,123 @@ __global__ void __launch_bounds__(JKC_NT) jk_rowcoop_kernel(BatchView bv, int on
 // need no masks; the zeros come from the zero fill of the tensor), eri_tri_pb doubles per block -- 1240 for n = 48
 // against 1176 for a row of the square.  A wave streams a block exactly as the square kernel streams a row (16-byte
 // loads, the next block in flight in registers, the block parked in the wave's LDS buffer as it lies in HBM).
-__device__ __forceinline__ void row_exchange_tri(const double* __restrict__ buf, const double* __restrict__ Di,
-                                                 const double* __restrict__ Dj, int i, int lane, double& acc_i, double& acc_j)
+//
+// The exchange of a row (i, j): lane k holds acc_i = sum_l V(k, l) D[j][l] and acc_j = sum_l V(k, l) D[i][l], l = 0 ... i.
+// The two density rows are LANE-RESIDENT: register d[g] holds D[row][16 g + (lane & 15)] in every lane (the same 16
+// values in each of the wave's four rows of 16 lanes), zero beyond l = i, and a step is
+//   ds_read_b64 v;  v_fmac_f64_dpp acc_i, dj[l / 16], v row_newbcast:(l % 16);  v_fmac_f64_dpp acc_j, di[l / 16], v row_newbcast:(l % 16)
+// -- the FP64 FMA takes the broadcast as a DPP operand, at the issue cost of a plain FMA, so no
+// scalar load is left in the loop: scalar loads return out of order, and a loop that has one must drain lgkmcnt to zero
+// after every group of eight; LDS reads alone return in order, and the reads of group g + 1 stay in flight under the
+// FMAs of group g.  Lane and register are immediates, so the l loop is unrolled over the groups of eight, up to
+// n = 16 JK_TRI_NG.
+typedef const double __attribute__((address_space(3))) * lds_cptr;
+// register groups of 16 per density row.  jk_tri_layout takes n in multiples of 8 whose longest row (npair doubles)
+// fits a block of JK_TRI_MAXU2 chunks: n <= 48
+constexpr int JK_TRI_NG = 3;
+static_assert(JK_TRI_MAXU2 * 128 < (16 * JK_TRI_NG + 8) * (16 * JK_TRI_NG + 9) / 2, "density rows of the triangular exchange: more register groups");
+
+// acc += D[l] * v with D[l] broadcast from lane L of every row of 16.  All 64 lanes are active wherever this is used.
+// Not volatile, no memory clobber: the compiler schedules the LDS reads around it and counts its waits per operand.
+template <int L>
+__device__ __forceinline__ void fma_bcast(double& acc, double d, double v)
 {
-    typedef double double8 __attribute__((ext_vector_type(8)));
-    typedef const double8 __attribute__((address_space(4))) * scalar_ptr8;
-    acc_i = 0.0; acc_j = 0.0;
-    const int kk = lane <= i ? lane : i;          // lanes beyond the triangle read lane i's elements and are dropped at the flush
-    const int trik = kk * (kk + 1) / 2;
-    // full blocks of eight l: no clamps, one scalar add per l (tri(l + 1) = tri(l) + l + 1), as in row_exchange.
-    // Element (k, l) of the packed triangle sits at tri(max) + min = max(tri(k) + l, tri(l) + k) -- the form that is not
-    // the valid one is the smaller of the two, (k - l)(k + l + 1) / 2 >= k - l -- so the index needs no compare and
-    // select; with u taken out of both forms the read is [max(tri(k) + l0, tri(l) + k - u)] + u, u in the instruction's
-    // offset field: two integer instructions per element instead of five (the loop is bound by instruction issue)
-    // (all of it in LDS byte addresses, so that no shift is left either)
-    typedef const double __attribute__((address_space(3))) * lds_cptr;
-    const unsigned base = (unsigned)(size_t)(lds_cptr)buf;
-    unsigned rowbase = base + 8u * (unsigned)trik, colbase = base + 8u * (unsigned)kk;
-    asm volatile("" : "+v"(rowbase), "+v"(colbase));      // opaque: otherwise the compiler re-associates the shift back into the loop
-    int l0 = 0, lbase = 0;
-    for (; l0 + 8 <= i + 1; l0 += 8) {             // i is wave-uniform; n is a multiple of 8, so l0 + 8 <= n
-        double v[8];
-        const unsigned rowaddr = rowbase + 8u * (unsigned)l0;
+    asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(d), "v"(v), "n"(L));
+}
+
+// Row `r` of D (r <= i) from the packed (2 - delta) D in LDS: D = D' / 2 off the diagonal, exactly.  Lanes beyond i
+// read element i and are set to zero, whole groups of 16 included -- that zero is what masks the l > i
+// steps of the last, partial group of eight.
+__device__ __forceinline__ void load_density_row(const double* Dp, int r, int i, int lane, double (&d)[JK_TRI_NG])
+{
+    const int tr = r * (r + 1) / 2;
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int l = l0 + u;
-            const unsigned coladdr = colbase + 8u * (unsigned)(lbase - u);
-            const unsigned sel = rowaddr > coladdr ? rowaddr : coladdr;
-            v[u] = *(lds_cptr)(size_t)(sel + 8u * (unsigned)u);
-            lbase += l + 1;
-        }
-        const double8 a = *(scalar_ptr8)(Di + l0), b = *(scalar_ptr8)(Dj + l0);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            acc_i += v[u] * b[u];
-            acc_j += v[u] * a[u];
-        }
-    }
-    if (l0 <= i) {                                  // the last, partial block: l beyond i re-reads l = i with weight zero
-        double v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            // scalar on purpose (readfirstlane): otherwise the compiler builds the two index forms under exec masks
-            const int l = __builtin_amdgcn_readfirstlane((l0 + u <= i) ? l0 + u : i);
-            const int lb = __builtin_amdgcn_readfirstlane(l * (l + 1) / 2);
-            const unsigned ra = rowbase + 8u * (unsigned)l, ca = colbase + 8u * (unsigned)lb;
-            v[u] = *(lds_cptr)(size_t)(ra > ca ? ra : ca);
-        }
-        const double8 a = *(scalar_ptr8)(Di + l0), b = *(scalar_ptr8)(Dj + l0);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const bool live = l0 + u <= i;
-            acc_i += v[u] * (live ? b[u] : 0.0);
-            acc_j += v[u] * (live ? a[u] : 0.0);
-        }
+    for (int g = 0; g < JK_TRI_NG; ++g) {
+        const int c = 16 * g + (lane & 15);
+        const int cc = c < i ? c : i;
+        const int ia = tr + cc, ib = cc * (cc + 1) / 2 + r;
+        const double x = Dp[ia > ib ? ia : ib];               // tri(max) + min is the larger of the two forms
+        d[g] = c > i ? 0.0 : (c == r ? x : 0.5 * x);
     }
 }
+
+// Element (k, l) of the packed triangle sits at tri(max) + min = max(tri(k) + l, tri(l) + k) -- the form that is not
+// the valid one is the smaller of the two, (k - l)(k + l + 1) / 2 >= k - l -- so the index needs no compare and
+// select; with u taken out of both forms the read is [max(tri(k) + l0, tri(l) + k - u)] + u, u in the instruction's
+// offset field: two integer instructions per element (all of it in LDS byte addresses, so that no shift is left either;
+// tri(l) - u is a constant of the unrolled step)
+template <int L>
+__device__ __forceinline__ double exchange_read_full(unsigned rowbase, unsigned colbase)
+{
+    constexpr int u = L & 7;
+    const unsigned rowaddr = rowbase + 8u * (unsigned)(L - u);
+    const unsigned coladdr = colbase + 8u * (unsigned)(L * (L + 1) / 2 - u);
+    const unsigned sel = rowaddr > coladdr ? rowaddr : coladdr;
+    return *(lds_cptr)(size_t)(sel + 8u * (unsigned)u);
+}
+// The last group of a row, full or not: l beyond i re-reads l = i (its density entry is zero).  Every address lane k
+// may read lies at or below that of (i, k), so one more min does it -- no branch, and the row stays straight-line code
+template <int L>
+__device__ __forceinline__ double exchange_read_last(unsigned rowbase, unsigned colbase, unsigned lastaddr)
+{
+    const unsigned rowaddr = rowbase + 8u * (unsigned)L, coladdr = colbase + 8u * (unsigned)(L * (L + 1) / 2);
+    const unsigned sel = rowaddr > coladdr ? rowaddr : coladdr;
+    return *(lds_cptr)(size_t)(sel < lastaddr ? sel : lastaddr);
+}
+// A row whose last group of eight is LAST (= i / 8), from step L on: straight-line code -- the branch on i is taken
+// once per row and none inside, so that every wait is a counted one.  v is a ring of eight: step l consumes v[l % 8]
+// (l ascending, as the sums have always been taken) and puts the read of step l + 8 into the register it has freed, so
+// eight reads (seven behind the one waited for) are in flight all the way.  The scheduler, left to itself, sinks
+// every read to its FMAs (read, wait for it, two FMAs); the barriers hold the order written here.
+template <int L, int LAST>
+__device__ __forceinline__ void exchange_steps(unsigned rowbase, unsigned colbase, unsigned lastaddr, const double (&di)[JK_TRI_NG],
+                                               const double (&dj)[JK_TRI_NG], double (&v)[8], double& acc_i, double& acc_j)
+{
+    constexpr int G = L / 8;
+    fma_bcast<L & 15>(acc_i, dj[L / 16], v[L & 7]);
+    fma_bcast<L & 15>(acc_j, di[L / 16], v[L & 7]);
+    if constexpr (G + 1 < LAST) v[L & 7] = exchange_read_full<L + 8>(rowbase, colbase);
+    else if constexpr (G + 1 == LAST) v[L & 7] = exchange_read_last<L + 8>(rowbase, colbase, lastaddr);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (L + 1 < 8 * (LAST + 1)) exchange_steps<L + 1, LAST>(rowbase, colbase, lastaddr, di, dj, v, acc_i, acc_j);
+}
+
+struct TriExchange {
+    unsigned rowbase, colbase, lastaddr;
+    double v[8];
+    // addresses of the row at `buf` and the reads of its first group (as a last group: one instruction more per read,
+    // and no branch on i here)
+    __device__ __forceinline__ void begin(const double* buf, int i, int lane)
+    {
+        const int kk = lane <= i ? lane : i;          // lanes beyond the triangle read lane i's elements and are dropped at the flush
+        const int trik = kk * (kk + 1) / 2;
+        const unsigned base = (unsigned)(size_t)(lds_cptr)buf;
+        rowbase = base + 8u * (unsigned)trik; colbase = base + 8u * (unsigned)kk;
+        lastaddr = colbase + 8u * (unsigned)(i * (i + 1) / 2);
+        asm volatile("" : "+v"(rowbase), "+v"(colbase));      // opaque: otherwise the compiler re-associates the shift back into the reads
+        v[0] = exchange_read_last<0>(rowbase, colbase, lastaddr); v[1] = exchange_read_last<1>(rowbase, colbase, lastaddr);
+        v[2] = exchange_read_last<2>(rowbase, colbase, lastaddr); v[3] = exchange_read_last<3>(rowbase, colbase, lastaddr);
+        v[4] = exchange_read_last<4>(rowbase, colbase, lastaddr); v[5] = exchange_read_last<5>(rowbase, colbase, lastaddr);
+        v[6] = exchange_read_last<6>(rowbase, colbase, lastaddr); v[7] = exchange_read_last<7>(rowbase, colbase, lastaddr);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __device__ __forceinline__ void finish(int i, double (&di)[JK_TRI_NG], double (&dj)[JK_TRI_NG], double& acc_i, double& acc_j)
+    {
+        // The hazard check does not see into the asm: a VALU write of a register needs two wait states before a DPP
+        // read of it.  The density registers pass through here, so whatever wrote them lies before the s_nop.
+        static_assert(JK_TRI_NG == 3, "list every density register, and every count of groups, here");
+        asm volatile("s_nop 1" : "+v"(di[0]), "+v"(di[1]), "+v"(di[2]), "+v"(dj[0]), "+v"(dj[1]), "+v"(dj[2]));
+        acc_i = 0.0; acc_j = 0.0;
+        switch (i >> 3) {                              // wave-uniform
+        case 0: exchange_steps<0, 0>(rowbase, colbase, lastaddr, di, dj, v, acc_i, acc_j); break;
+        case 1: exchange_steps<0, 1>(rowbase, colbase, lastaddr, di, dj, v, acc_i, acc_j); break;
+        case 2: exchange_steps<0, 2>(rowbase, colbase, lastaddr, di, dj, v, acc_i, acc_j); break;
+        case 3: exchange_steps<0, 3>(rowbase, colbase, lastaddr, di, dj, v, acc_i, acc_j); break;
+        case 4: exchange_steps<0, 4>(rowbase, colbase, lastaddr, di, dj, v, acc_i, acc_j); break;
+        default: exchange_steps<0, 5>(rowbase, colbase, lastaddr, di, dj, v, acc_i, acc_j); break;
+        }
+    }
+};
 
 template <int NW, int MAXU2>       // MAXU2 chunks of 128 doubles cover a block
 __global__ void __launch_bounds__(64 * NW) jk_tri_kernel(BatchView bv, int only_active)
@@ -667,19 +728,43 @@ __global__ void __launch_bounds__(64 * NW) jk_tri_kernel(BatchView bv, int only_
         // the next block's loads go out now and complete while this one is contracted
         const int nt = t + stride;
         if (nt < npairs) load_block(nt);
+        // The exchange reads, lane k, what other lanes of this wave stored to rowbuf above.  LDS operations of one wave
+        // execute in program order, so the hardware needs nothing; this wavefront-scope fence (it emits no instruction)
+        // is what keeps the compiler from moving the reads above the stores.  The data is there when the lgkmcnt wait
+        // in front of the first FMA -- the one the reads need anyway -- has passed.
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        // the density rows and the first group of the first row to be contracted go out here and return under the two
+        // reductions; the short row's follow the flush of the long one (ahead of it they cost registers the kernel, at
+        // the 168 of three waves per SIMD, does not have: scratch)
+        double di[JK_TRI_NG], dj[JK_TRI_NG];
+        TriExchange x;
+        if (!zl) {
+            load_density_row(Dp, il, il, lane, di);
+            load_density_row(Dp, jl, il, lane, dj);
+            x.begin(rowbuf, il, lane);
+        } else if (!zs) {
+            load_density_row(Dp, is, is, lane, di);
+            load_density_row(Dp, js, is, lane, dj);
+            x.begin(rowbuf + sb, is, lane);
+        }
         accl = wave_sum_top(accl);
         accs = wave_sum_top(accs);
         if (lane == 63) { if (!zl) atomicAdd(&Jl[rl], accl); if (!zs) atomicAdd(&Jl[t], accs); }
         double ai, aj;
         if (!zl) {
-            row_exchange_tri(rowbuf, Dg + il * n, Dg + jl * n, il, lane, ai, aj);
+            x.finish(il, di, dj, ai, aj);
             if (lane <= il) {
                 atomicAdd(&Kl[il * n + lane], ai);
                 if (il != jl) atomicAdd(&Kl[jl * n + lane], aj);
             }
+            if (!zs) {
+                load_density_row(Dp, is, is, lane, di);
+                load_density_row(Dp, js, is, lane, dj);
+                x.begin(rowbuf + sb, is, lane);
+            }
         }
         if (!zs) {
-            row_exchange_tri(rowbuf + sb, Dg + is * n, Dg + js * n, is, lane, ai, aj);
+            x.finish(is, di, dj, ai, aj);
             if (lane <= is) {
                 atomicAdd(&Kl[is * n + lane], ai);
                 if (is != js) atomicAdd(&Kl[js * n + lane], aj);
@@ -781,9 +866,18 @@ JkRoute launch_jk_incore(const BatchView& bv, bool only_active, hipStream_t s)
 {
     const int n = bv.n, np = bv.npair;
     if (bv.eri_tri) {
-        const size_t lds = jk_tri_lds_bytes(n, np);
         auto kern = jk_tri_kernel<JK_TRI_NW, JK_TRI_MAXU2>;
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        // the O(npair) size of the LDS image and the kernel's attribute once per shape and device, not per SCF iteration
+        struct TriShape { int n, np, dev; size_t lds; };
+        static thread_local TriShape last = {0, 0, -1, 0};
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        if (last.n != n || last.np != np || last.dev != dev) {
+            const size_t bytes = jk_tri_lds_bytes(n, np);
+            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+            last = {n, np, dev, bytes};
+        }
+        const size_t lds = last.lds;
         // Workgroups per fragment: every workgroup pays a prologue (packed density, 23 KB of LDS zeroed) and a flush, so
         // as few as keep three rounds of workgroups on the card -- ONE from 768 fragments on (2016 dimers, same box:
         // 3.12 ms per launch with one, 3.27 with three, 3.55 with six).  MQC_HIP_JK_TRI_WG overrides (measurements).
