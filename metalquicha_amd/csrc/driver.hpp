@@ -10,17 +10,15 @@ namespace mqc {
 // the HIP error a stage left behind, as the call's failure
 int stage_check(const char* stage);
 
-// One pipeline slot: a stream with its own pools and events.  While the SCF loop of chunk k runs on
-// one slot, the integrals of chunk k+1 are formed on the other (compute-bound ERI kernels fill the
-// gaps the HBM-bound J/K stream and the per-iteration host round trip leave).
+// A lane of the context as the stages of one chunk see it (mqc_hip_context::Lane: stream, pools, events), with its
+// index and the pinned word the SCF loop reads its counter into
+using Lane = mqc_hip_context::Lane;
 struct Slot {
     int id;
-    hipStream_t s;
-    DevicePool* pool[NPOOL];          // indexed by POOL_*
-    hipEvent_t e0, e1, e2, e3, q0, q1, s0, s1;
+    Lane* lane;
     int* h_counter;
 };
-Slot make_slot(mqc_hip_context* ctx, int id, int* h_counter);
+inline Slot make_slot(mqc_hip_context* ctx, int id, int* h_counter) { return {id, &ctx->lane[id], h_counter}; }
 // carve one chunk's arrays out of the slot's pools (carve_chunk) and upload the block table of a triangular tensor
 int carve_slot(mqc_hip_context* ctx, const Slot& sl, const BatchPlan& plan, const TopologyDev& td, int nfrag, BatchView& bv);
 int upload_topology(mqc_hip_context* ctx, const Topology& topo, TopologyDev& td, DevicePool* pool = nullptr, hipStream_t stream = nullptr);
@@ -38,7 +36,7 @@ struct AtomicGuess {
     int nmodes = 0;
 };
 
-// A batch call that defers its small topology groups (scf_run_batch_impl): the largest group's batch opens the gate
+// A batch call that defers its small topology groups (schedule_groups): the largest group's batch opens the gate
 // once its first chunk's integrals are done, the other groups' batches wait at it before they enqueue anything.  Host
 // side only: a wait packet in a hardware queue would hold up the large group's own streams that share that queue.
 struct GroupGate {
@@ -49,26 +47,28 @@ struct GroupGate {
     void wait() { std::unique_lock<std::mutex> lock(m); cv.wait(lock, [this] { return is_open; }); }
 };
 
-// What the stages of one batch call share besides the plan: the inputs, ordered by compactness, the device topology
+// One fragment of a batch call: what the caller gave and where its answers go
+struct FragmentIO {
+    const mqc_hip_molecule_t* mol;     // geometry (mol->xyz), point charges, h_extra
+    mqc_hip_scf_result_t* result;
+    double* pcgrad;                    // mqc_hip_scf_gradient_embedded_batch: the sites' gradient, or null
+    const double* d0;                  // mqc_hip_scf_run_batch_restart: starting density (null: opts.guess)
+    double* spin_out;                  // mqc_hip_scf_run_batch_restart: where an unrestricted run's spin densities go, or null
+    double *mp2_os, *mp2_ss;           // mqc_hip_rimp2_batch: where the opposite-spin and same-spin correlation energies
+    int32_t* mp2_done;                 // and the done flag go
+};
+
+// What the stages of one batch call share besides the plan: the fragments, ordered by compactness, the device topology
 // and grid, and the statistics, gathered locally (two lanes may run at once) and merged at the end
 struct Batch {
     const Topology& topo;
     const Topology* aux;
     const mqc_hip_scf_options_t& opts;
     const AtomicGuess* guess;
-    std::vector<const double*> xyz;
-    std::vector<mqc_hip_scf_result_t*> results;
-    std::vector<const mqc_hip_molecule_t*> mols;     // embedded groups only (point charges, h_extra)
-    std::vector<double*> pcgrad;                     // mqc_hip_scf_gradient_embedded_batch only: the callers' site gradients (or null)
-    // mqc_hip_scf_run_batch_restart only: the callers' starting densities (null entry: opts.guess) and where an
-    // unrestricted run's spin densities go (null entry: nowhere); empty when the call brought none
-    std::vector<const double*> d0;
-    std::vector<double*> spin_out;
-    // mqc_hip_rimp2_batch only (mp2_frozen >= 0: the frozen orbitals of this topology): where each fragment's
-    // opposite-spin and same-spin correlation energies and its done flag go
-    int mp2_frozen = -1;
-    std::vector<double*> mp2_os, mp2_ss;
-    std::vector<int32_t*> mp2_done;
+    std::vector<FragmentIO> frags;
+    bool embedded_entry = false;                     // the call came through mqc_hip_scf_gradient_embedded_batch
+    bool any_d0 = false;                             // some fragment brought a starting density
+    int mp2_frozen = -1;                             // mqc_hip_rimp2_batch only: the frozen orbitals of this topology (>= 0)
     TopologyDev td{}, tdx{};
     GridDev grid;
     Stats stats;
@@ -81,11 +81,10 @@ bool xc_radial_cache_on();
 // exchange-correlation: per-element grid templates and the per-topology point list
 int upload_grid(mqc_hip_context* ctx, Batch& b, DevicePool& pool, hipStream_t s);
 
-
-// The integral stage of `slot` uses its first `count` side streams only, and charges the one-electron chain of the
+// The integral stage of lane `slot` uses its first `count` side streams only, and charges the one-electron chain of the
 // chunk (prepare) to side stream `chain_side` (kern_eri.hip).  Set between calls of the stage, never inside one.
 void eri_limit_side_streams(int slot, int count, int chain_side);
-// Whether the host may wait inside the integral stage of `slot` until its launches are handed out (the dispatcher of
+// Whether the host may wait inside the integral stage of lane `slot` until its launches are handed out (the dispatcher of
 // launch_eri, kern_eri.hip): true unless the host has another chunk's SCF loop to run meanwhile.  Default: true.
 void eri_host_may_wait(int slot, bool yes);
 

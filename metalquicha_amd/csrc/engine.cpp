@@ -71,7 +71,7 @@ static size_t scratch_reservation_bytes(const mqc_hip_context* ctx)
 
 int upload_topology(mqc_hip_context* ctx, const Topology& topo, TopologyDev& td, DevicePool* pool, hipStream_t stream)
 {
-    if (!pool) pool = &ctx->pool_topo;
+    if (!pool) pool = &ctx->lane[0].topo;
     const int ns = (int)topo.shells.size();
     std::vector<int> l(ns), np(ns), po(ns), at(ns), ao(ns);
     for (int s = 0; s < ns; ++s) {
@@ -142,7 +142,7 @@ int upload_topology(mqc_hip_context* ctx, const Topology& topo, TopologyDev& td,
     td.ngroup = ng;
     td.gprim_total = (int)gex.size(); td.gcoef_total = (int)gco.size();
     td.nshell = ns; td.nao = topo.nao; td.npair = topo.npair; td.natoms = topo.natoms; td.lmax = topo.lmax;
-    hipStream_t s = stream ? stream : ctx->stream;
+    hipStream_t s = stream ? stream : ctx->lane[0].stream;
     HIP_CHECK_RET(hipMemcpyAsync(td.sh_l, l.data(), ib, hipMemcpyHostToDevice, s));
     HIP_CHECK_RET(hipMemcpyAsync(td.sh_nprim, np.data(), ib, hipMemcpyHostToDevice, s));
     HIP_CHECK_RET(hipMemcpyAsync(td.sh_poff, po.data(), ib, hipMemcpyHostToDevice, s));
@@ -162,15 +162,6 @@ int upload_topology(mqc_hip_context* ctx, const Topology& topo, TopologyDev& td,
     return MQC_HIP_OK;
 }
 
-Slot make_slot(mqc_hip_context* ctx, int id, int* h_counter)
-{
-    if (id == 0)
-        return {0, ctx->stream, {&ctx->pool_main, &ctx->pool_eri, &ctx->pool_misc, &ctx->pool_gridw, &ctx->pool_df},
-                ctx->ev0, ctx->ev1, ctx->ev2, ctx->ev3, ctx->evq0, ctx->evq1, ctx->evs[0][0], ctx->evs[0][1], h_counter};
-    return {1, ctx->stream2, {&ctx->pool_main2, &ctx->pool_eri2, &ctx->pool_misc2, &ctx->pool_gridw2, &ctx->pool_df2},
-            ctx->evb0, ctx->evb1, ctx->evb2, ctx->evb3, ctx->evq2, ctx->evq3, ctx->evs[1][0], ctx->evs[1][1], h_counter};
-}
-
 int carve_slot(mqc_hip_context* ctx, const Slot& sl, const BatchPlan& plan, const TopologyDev& td, int nfrag, BatchView& bv)
 {
     static const char* const what[NPOOL] = {"SCF matrices", "ERI tensor", "counters", "grid weights", "fitted tensor"};
@@ -178,7 +169,7 @@ int carve_slot(mqc_hip_context* ctx, const Slot& sl, const BatchPlan& plan, cons
     const ChunkBytes need = carve_chunk(plan, nfrag, nullptr, probe);
     char* bases[NPOOL] = {};
     for (int k = 0; k < NPOOL; ++k)
-        if (need.pool[k] && !(bases[k] = (char*)sl.pool[k]->ensure(need.pool[k])))
+        if (need.pool[k] && !(bases[k] = (char*)sl.lane->pool[k].ensure(need.pool[k])))
             return fail(MQC_HIP_ERR_DEVICE, std::string("out of device memory (") + what[k] + ")");
     carve_chunk(plan, nfrag, bases, bv);
     bv.topo = td; bv.slot = sl.id; bv.boys = ctx->d_boys; bv.c2s = ctx->d_c2s; bv.unit = ctx->d_unit;
@@ -186,7 +177,7 @@ int carve_slot(mqc_hip_context* ctx, const Slot& sl, const BatchPlan& plan, cons
         static std::vector<int> sb_host[2];      // stays alive while the copy is in flight
         std::vector<int>& sbh = sb_host[sl.id & 1];
         jk_tri_block(plan.npair, &sbh);
-        if (hipMemcpyAsync((void*)bv.eri_tri_sb, sbh.data(), sizeof(int) * sbh.size(), hipMemcpyHostToDevice, sl.s) != hipSuccess)
+        if (hipMemcpyAsync((void*)bv.eri_tri_sb, sbh.data(), sizeof(int) * sbh.size(), hipMemcpyHostToDevice, sl.lane->stream) != hipSuccess)
             return fail(MQC_HIP_ERR_DEVICE, "upload of the tensor block table failed");
     }
     return MQC_HIP_OK;
@@ -257,7 +248,7 @@ int plan_batch(const mqc_hip_scf_options_t& o, const Topology& topo, int ntot, B
     // the bounds (one thread per shell pair walking its primitive quartets: 1.6 ms for one cc-pVDZ water dimer) cost
     // more than the screened quartets save, and the unscreened tensor needs no zero fill.  Energies move by < 1e-11 Eh
     // either way (that is what the threshold means); MQC_HIP_SCHWARZ_MIN_FRAGMENTS=0 screens always.
-    static const int schwarz_min = [] { const char* e = std::getenv("MQC_HIP_SCHWARZ_MIN_FRAGMENTS"); return e ? std::atoi(e) : 9; }();
+    static const int schwarz_min = env_int("MQC_HIP_SCHWARZ_MIN_FRAGMENTS", 9);
     p.stol = (o.schwarz_tol > 0.0 && ntot >= schwarz_min) ? o.schwarz_tol : 0.0;
     return validate_options(o, topo, p, msg);
 }
@@ -275,9 +266,9 @@ static void fill_error(mqc_hip_scf_result_t* r, const std::string& msg)
 }
 
 // a batch that does not run: every fragment carries the reason
-static int refuse(const std::vector<mqc_hip_scf_result_t*>& results, int code, const std::string& msg)
+static int refuse(const std::vector<FragmentIO>& frags, int code, const std::string& msg)
 {
-    for (auto* r : results) { fill_error(r, msg); r->scf_status = MQC_HIP_SCF_NOT_RUN; }
+    for (const FragmentIO& f : frags) { fill_error(f.result, msg); f.result->scf_status = MQC_HIP_SCF_NOT_RUN; }
     return fail(code, msg);
 }
 
@@ -285,7 +276,8 @@ static DevicePool g_guess_pool[2];
 static DevicePool g_restart_pool[2];     // per slot: which fragments of the chunk restart from a supplied density
 
 struct Job {
-    int start = 0, nf = 0;
+    const FragmentIO* frag = nullptr;      // the chunk's fragments: nf consecutive records of the batch
+    int nf = 0;
     BatchView bv{};
     std::vector<double> hx, hpc;
     std::vector<int> restart;      // per fragment of the chunk: 1 = starts from its supplied density
@@ -293,7 +285,7 @@ struct Job {
 
 bool xc_radial_cache_on()
 {
-    static const bool on = [] { const char* e = std::getenv("MQC_HIP_XC_RADIAL_CACHE"); return !(e && e[0] == '0'); }();
+    static const bool on = env_on("MQC_HIP_XC_RADIAL_CACHE");
     return on;
 }
 
@@ -312,7 +304,7 @@ int upload_grid(mqc_hip_context* ctx, Batch& b, DevicePool& pool, hipStream_t s)
         if (!tmpl_of_z.count(z)) {
             std::vector<double> x, w; std::string e;
             if (!build_atom_template(z, b.opts.grid_level, b.opts.radial_points, b.opts.angular_points, x, w, e))
-                return refuse(b.results, MQC_HIP_ERR_UNSUPPORTED, e);
+                return refuse(b.frags, MQC_HIP_ERR_UNSUPPORTED, e);
             tmpl_of_z[z] = {(int)tw.size(), (int)w.size()};
             txyz.insert(txyz.end(), x.begin(), x.end());
             tw.insert(tw.end(), w.begin(), w.end());
@@ -395,7 +387,8 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
     const Topology& topo = b.topo;
     const mqc_hip_scf_options_t& opts = b.opts;
     const int nf = job.nf, n = plan.n;
-    hipStream_t s = sl.s;
+    const FragmentIO* frag = job.frag;
+    hipStream_t s = sl.lane->stream;
     const double t0 = now_s();
     BatchView& bv = job.bv;
     // range-separated hybrids: K is folded to exx K + exx_lr K_lr before the step, which then takes all of it
@@ -407,7 +400,7 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
     if (rc != MQC_HIP_OK) return rc;
     if (plan.two_e == TWO_E_DF) HIP_CHECK_RET(hipMemsetAsync(bv.scal, 0, sizeof(double) * (size_t)nf * 8, s));
     job.hx.resize((size_t)nf * topo.natoms * 3);
-    for (int f = 0; f < nf; ++f) std::memcpy(&job.hx[(size_t)f * topo.natoms * 3], b.xyz[job.start + f], sizeof(double) * topo.natoms * 3);
+    for (int f = 0; f < nf; ++f) std::memcpy(&job.hx[(size_t)f * topo.natoms * 3], frag[f].mol->xyz, sizeof(double) * topo.natoms * 3);
     HIP_CHECK_RET(hipMemcpyAsync(bv.xyz, job.hx.data(), sizeof(double) * job.hx.size(), hipMemcpyHostToDevice, s));
     if (plan.npc > 0) {
         // layout [charge][x, y, z, q][fragment], FRAGMENT FASTEST: the lanes of a wave are consecutive fragments, so a
@@ -415,7 +408,7 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
         // streamed its own 49 KB array and a wave-load touched 64 cache lines (int1e: 40 % of a 512-fragment FMO run)
         job.hpc.resize((size_t)nf * plan.npc * 4);
         for (int f = 0; f < nf; ++f) {
-            const mqc_hip_molecule_t* m = b.mols[job.start + f];
+            const mqc_hip_molecule_t* m = frag[f].mol;
             for (int g = 0; g < plan.npc; ++g) {
                 double* q = &job.hpc[(size_t)g * 4 * nf + f];
                 q[0] = m->point_charge_xyz[3 * g]; q[(size_t)nf] = m->point_charge_xyz[3 * g + 1]; q[2 * (size_t)nf] = m->point_charge_xyz[3 * g + 2];
@@ -426,7 +419,7 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
     }
     if (plan.hx)
         for (int f = 0; f < nf; ++f)
-            HIP_CHECK_RET(hipMemcpyAsync((void*)(bv.Hx + (size_t)f * n * n), b.mols[job.start + f]->h_extra, sizeof(double) * n * n, hipMemcpyHostToDevice, s));
+            HIP_CHECK_RET(hipMemcpyAsync((void*)(bv.Hx + (size_t)f * n * n), frag[f].mol->h_extra, sizeof(double) * n * n, hipMemcpyHostToDevice, s));
     HIP_CHECK_RET(hipMemsetAsync(bv.istate, 0, sizeof(int) * (size_t)nf * 4, s));
     HIP_CHECK_RET(hipMemsetAsync(bv.eri_count, 0, sizeof(unsigned long long), s));
     const double t1 = now_s();
@@ -437,9 +430,9 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
     // The one-electron stage, the orthogonaliser and the starting guess need the geometry (S, H) only and are
     // latency-bound (six class launches; one workgroup per fragment, Jacobi sweeps): they run on a side stream next
     // to the compute-bound two-electron stage, which does not wait for them (0.7 ms of a single-fragment call)
-    hipStream_t so = ctx->side[sl.id & 1][b.chain_side];
-    HIP_CHECK_RET(hipEventRecord(ctx->evo[sl.id & 1][0], s));             // uploads and resets above are in
-    HIP_CHECK_RET(hipStreamWaitEvent(so, ctx->evo[sl.id & 1][0], 0));
+    hipStream_t so = sl.lane->side[b.chain_side];
+    HIP_CHECK_RET(hipEventRecord(sl.lane->chain[0], s));             // uploads and resets above are in
+    HIP_CHECK_RET(hipStreamWaitEvent(so, sl.lane->chain[0], 0));
     launch_int1e(bv, topo, so);
     // block-sharing plan and class lists of the integral stage: host work that depends on the geometry only, done
     // here while the bounds and one-electron kernels run
@@ -449,20 +442,20 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
     if ((rc = stage_check("orthogonalizer")) != MQC_HIP_OK) return rc;
     // fragments that bring a starting density are projected below; a chunk made of them alone needs no other guess
     int n_restart = 0;
-    if (!b.d0.empty()) {
+    if (b.any_d0) {
         job.restart.assign(nf, 0);
-        for (int f = 0; f < nf; ++f) if (b.d0[job.start + f]) { job.restart[f] = 1; ++n_restart; }
+        for (int f = 0; f < nf; ++f) if (frag[f].d0) { job.restart[f] = 1; ++n_restart; }
     }
     const bool all_restart = n_restart == nf;
     if (!b.guess && !all_restart) launch_guess(bv, opts.guess == MQC_HIP_GUESS_CORE ? MQC_HIP_GUESS_CORE : MQC_HIP_GUESS_GWH, so);
     if ((rc = stage_check("guess")) != MQC_HIP_OK) return rc;
-    HIP_CHECK_RET(hipEventRecord(ctx->evo[sl.id & 1][1], so));
+    HIP_CHECK_RET(hipEventRecord(sl.lane->chain[1], so));
     if (plan.xc.ncomp > 0) { launch_becke_weights(bv, s); if (bv.grid.rad) launch_xc_radial_cache(bv, s); }
     if ((rc = stage_check("grid weights")) != MQC_HIP_OK) return rc;
     const double t2 = now_s();
     b.stats.t_int1e += t2 - t1;
 
-    HIP_CHECK_RET(hipEventRecord(sl.q0, s));
+    HIP_CHECK_RET(hipEventRecord(sl.lane->eri[0], s));
     if (plan.two_e == TWO_E_DF) launch_df_build(bv, topo, *b.aux, s);
     else if (plan.two_e == TWO_E_DIRECT) launch_direct_setup(bv, topo, s);
     else {
@@ -476,10 +469,10 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
         // the bounds of a screened build tell the J/K kernel which pair rows are all zeros (triangular tensor only)
         if (plan.stol > 0.0 && bv.eri_tri) eri_schwarz_view(bv.slot, &bv.jk_q, &bv.jk_qthresh);
     }
-    HIP_CHECK_RET(hipEventRecord(sl.q1, s));
+    HIP_CHECK_RET(hipEventRecord(sl.lane->eri[1], s));
     if ((rc = stage_check("two-electron setup")) != MQC_HIP_OK) return rc;
     b.stats.eri_quartets += topo.n_quartets * nf;
-    HIP_CHECK_RET(hipStreamWaitEvent(s, ctx->evo[sl.id & 1][1], 0));      // join: X, C, D of the guess are ready
+    HIP_CHECK_RET(hipStreamWaitEvent(s, sl.lane->chain[1], 0));      // join: X, C, D of the guess are ready
     if (b.guess && !all_restart) {
         // superposed atoms (build_restricted_guess / atomic_guess_fock, mqc_libcint_atomic_guess.f90:168-212,
         // mqc_libcint_rhf.f90:1382-1411): the same block-diagonal density in every fragment of the topology, its
@@ -507,7 +500,7 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
         const size_t nn = (size_t)n * n, cnt = plan.uhf ? 2 * nn : nn;
         for (int f = 0; f < nf; ++f)
             if (job.restart[f])
-                HIP_CHECK_RET(hipMemcpyAsync(bv.W + (size_t)f * 6 * nn, b.d0[job.start + f], sizeof(double) * cnt, hipMemcpyHostToDevice, s));
+                HIP_CHECK_RET(hipMemcpyAsync(bv.W + (size_t)f * 6 * nn, frag[f].d0, sizeof(double) * cnt, hipMemcpyHostToDevice, s));
         const int* d_flags = nullptr;
         if (!all_restart) {
             int* df = (int*)g_restart_pool[sl.id & 1].ensure(sizeof(int) * (size_t)nf + 256);
@@ -518,7 +511,7 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
         launch_restart(bv, d_flags, s);
         if ((rc = stage_check("restart projection")) != MQC_HIP_OK) return rc;
     }
-    b.stats.t_eri += now_s() - t2;      // host time to enqueue; the kernels are timed by q0/q1
+    b.stats.t_eri += now_s() - t2;      // host time to enqueue; the kernels are timed by the lane's eri events
     return MQC_HIP_OK;
 }
 
@@ -527,7 +520,8 @@ static int scf_loop(const BatchPlan& plan, Batch& b, const Slot& sl, Job& job)
 {
     const int nf = job.nf, n = plan.n;
     const double np = (double)plan.npair;
-    hipStream_t s = sl.s;
+    Lane& lane = *sl.lane;
+    hipStream_t s = lane.stream;
     BatchView& bv = job.bv;
     Stats& st = b.stats;
     const bool df = plan.two_e == TWO_E_DF, ks = plan.xc.ncomp > 0;
@@ -538,7 +532,7 @@ static int scf_loop(const BatchPlan& plan, Batch& b, const Slot& sl, Job& job)
     if (b.gate) b.gate->open();         // deferred small groups start now: from here on this batch uses one stream
     {
         float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, sl.q0, sl.q1);
+        (void)hipEventElapsedTime(&ms, lane.eri[0], lane.eri[1]);
         st.eri_kernel_seconds += ms * 1e-3;
     }
     int remaining = nf;
@@ -548,8 +542,8 @@ static int scf_loop(const BatchPlan& plan, Batch& b, const Slot& sl, Job& job)
     // much as the kernels.  They run BLOCKS of iterations between two reads of the counter -- finished fragments
     // drop out of every kernel by themselves (state machine), so an iteration enqueued past convergence is three
     // empty launches.  Large batches keep one read per iteration (MQC_HIP_SCF_SYNC_BLOCK overrides: 1 = always).
-    static const int sync_block_env = [] { const char* e = std::getenv("MQC_HIP_SCF_SYNC_BLOCK"); return e ? std::atoi(e) : 0; }();
-    static const int block_max_frag = [] { const char* e = std::getenv("MQC_HIP_SCF_BLOCK_MAX_FRAGMENTS"); return e ? std::atoi(e) : 256; }();
+    static const int sync_block_env = env_int("MQC_HIP_SCF_SYNC_BLOCK", 0);
+    static const int block_max_frag = env_int("MQC_HIP_SCF_BLOCK_MAX_FRAGMENTS", 256);
     const bool blocked = sync_block_env != 1 && nf <= block_max_frag;
     const int max_guard = b.opts.max_iter + 2;
     int blocks_done = 0;
@@ -559,25 +553,25 @@ static int scf_loop(const BatchPlan& plan, Batch& b, const Slot& sl, Job& job)
         if (block_len > max_guard - guard) block_len = max_guard - guard;
         ++blocks_done;
         for (int bi = 0; bi < block_len; ++bi) {
-            HIP_CHECK_RET(hipEventRecord(sl.e0, s));
+            HIP_CHECK_RET(hipEventRecord(lane.fock[0], s));
             if ((rc = build_jk(plan, b.topo, bv, s)) != MQC_HIP_OK) return rc;
-            HIP_CHECK_RET(hipEventRecord(sl.e1, s));
+            HIP_CHECK_RET(hipEventRecord(lane.fock[1], s));
             if (guard == 0 && (rc = stage_check("J/K build")) != MQC_HIP_OK) return rc;
             if (ks) {
-                HIP_CHECK_RET(hipEventRecord(sl.e2, s));
+                HIP_CHECK_RET(hipEventRecord(lane.xc[0], s));
                 launch_xc(bv, true, s);
-                HIP_CHECK_RET(hipEventRecord(sl.e3, s));
+                HIP_CHECK_RET(hipEventRecord(lane.xc[1], s));
             }
-            HIP_CHECK_RET(hipEventRecord(sl.s0, s));
+            HIP_CHECK_RET(hipEventRecord(lane.step[0], s));
             launch_scf_step(bv, s);
-            HIP_CHECK_RET(hipEventRecord(sl.s1, s));
+            HIP_CHECK_RET(hipEventRecord(lane.step[1], s));
             if (bi + 1 < block_len) { ++guard; continue; }
             HIP_CHECK_RET(hipMemcpyAsync(sl.h_counter, bv.counters, sizeof(int), hipMemcpyDeviceToHost, s));
             HIP_CHECK_RET(hipStreamSynchronize(s));
             float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, sl.s0, sl.s1);
+            (void)hipEventElapsedTime(&ms, lane.step[0], lane.step[1]);
             st.scf_step_seconds += ms * 1e-3 * block_len;
-            (void)hipEventElapsedTime(&ms, sl.e0, sl.e1);
+            (void)hipEventElapsedTime(&ms, lane.fock[0], lane.fock[1]);
             if (df) {
                 st.df_bytes += (double)remaining * 8.0 * (double)plan.naux * (double)n * (double)n * block_len;
                 st.df_flops += (double)remaining * 4.0 * (double)plan.naux * (double)n * (double)n * (1.0 + (plan.xc.exx != 0.0 ? (double)plan.nocc : 0.0)) * block_len;
@@ -609,7 +603,7 @@ static int scf_loop(const BatchPlan& plan, Batch& b, const Slot& sl, Job& job)
             }
             if (ks) {
                 float mx = 0.f;
-                (void)hipEventElapsedTime(&mx, sl.e2, sl.e3);
+                (void)hipEventElapsedTime(&mx, lane.xc[0], lane.xc[1]);
                 st.xc_kernel_seconds += mx * 1e-3 * block_len;
                 st.xc_points += (double)remaining * plan.npts * block_len;
                 st.xc_flops += (double)remaining * plan.npts * (plan.xc.gga ? 8.0 : 4.0) * (double)n * (double)n * block_len;
@@ -710,8 +704,9 @@ static int write_result(const BatchPlan& plan, Batch& b, const Job& job, const C
     const Topology& topo = b.topo;
     const int n = plan.n, nocc = plan.nocc;
     const size_t nn = (size_t)n * n;
-    mqc_hip_scf_result_t* r = b.results[job.start + f];
-    const double* x = b.xyz[job.start + f];
+    const FragmentIO& io = job.frag[f];
+    mqc_hip_scf_result_t* r = io.result;
+    const double* x = io.mol->xyz;
     const int nmo = o.ist[4 * f + 2];
     r->n_ao = n; r->n_mo = nmo; r->n_occ = nocc;
     if (nocc > nmo) {
@@ -737,8 +732,8 @@ static int write_result(const BatchPlan& plan, Batch& b, const Job& job, const C
         r->has_gradient = 1;
     }
     // the charges stay out of E_nuc, so their gradient is the device's as it stands
-    if (b.opts.want_gradient && plan.npc > 0 && !b.pcgrad.empty() && b.pcgrad[job.start + f])
-        std::memcpy(b.pcgrad[job.start + f], &o.pcgrad[(size_t)f * plan.npc * 3], sizeof(double) * (size_t)plan.npc * 3);
+    if (b.opts.want_gradient && plan.npc > 0 && io.pcgrad)
+        std::memcpy(io.pcgrad, &o.pcgrad[(size_t)f * plan.npc * 3], sizeof(double) * (size_t)plan.npc * 3);
     if (plan.uhf) {
         std::vector<double> Ca(nn), Cb(nn), Sm(nn);
         HIP_CHECK_RET(hipMemcpyAsync(Ca.data(), job.bv.C + (size_t)f * nn, sizeof(double) * nn, hipMemcpyDeviceToHost, s));
@@ -756,9 +751,9 @@ static int write_result(const BatchPlan& plan, Batch& b, const Job& job, const C
         embedding_and_mulliken(topo, o.D.data() + f * nn, embedded ? o.U.data() + f * nn : nullptr,
                                r->mulliken_charges ? o.S.data() + f * nn : nullptr, r);
     if (r->density) std::memcpy(r->density, o.D.data() + f * nn, sizeof(double) * nn);
-    if (plan.uhf && !b.spin_out.empty() && b.spin_out[job.start + f]) {
-        std::memcpy(b.spin_out[job.start + f], o.Da.data() + f * nn, sizeof(double) * nn);
-        std::memcpy(b.spin_out[job.start + f] + nn, o.Db.data() + f * nn, sizeof(double) * nn);
+    if (plan.uhf && io.spin_out) {
+        std::memcpy(io.spin_out, o.Da.data() + f * nn, sizeof(double) * nn);
+        std::memcpy(io.spin_out + nn, o.Db.data() + f * nn, sizeof(double) * nn);
     }
     r->has_error = 0; r->message[0] = '\0';
     if (plan.two_e == TWO_E_DF && o.scal[8 * f + 7] == 1.0)
@@ -768,9 +763,9 @@ static int write_result(const BatchPlan& plan, Batch& b, const Job& job, const C
         fill_error(r, "SCF did not converge in " + std::to_string(r->iterations) + " iterations");
     if (b.mp2_frozen >= 0 && conv && !r->has_error) {
         // the correlation energy belongs to converged orbitals only; everything else keeps the entry's zeros
-        *b.mp2_os[job.start + f] = o.mp2[2 * f];
-        *b.mp2_ss[job.start + f] = o.mp2[2 * f + 1];
-        *b.mp2_done[job.start + f] = 1;
+        *io.mp2_os = o.mp2[2 * f];
+        *io.mp2_ss = o.mp2[2 * f + 1];
+        *io.mp2_done = 1;
     }
     b.stats.scf_iterations_total += r->iterations;
     return MQC_HIP_OK;
@@ -782,7 +777,8 @@ static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& j
     const Topology& topo = b.topo;
     const int nf = job.nf, n = plan.n;
     const size_t tot = (size_t)nf * n * n;
-    hipStream_t s = sl.s;
+    const FragmentIO* frag = job.frag;
+    hipStream_t s = sl.lane->stream;
     const BatchView& bv = job.bv;
     const double t4 = now_s();
     ChunkOut o;
@@ -808,7 +804,7 @@ static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& j
         // (still resident in this slot) prove below 1e-3 of its threshold: a derivative integral exceeds the bound of
         // its undifferentiated quartet, and at the threshold itself the dropped tasks moved a (H2O)6 / cc-pVDZ
         // gradient by 3.8e-9.  MQC_HIP_GRAD_SCREEN=0 forms them all (A/B switch)
-        static const bool grad_screen = [] { const char* e = std::getenv("MQC_HIP_GRAD_SCREEN"); return !(e && e[0] == '0'); }();
+        static const bool grad_screen = env_on("MQC_HIP_GRAD_SCREEN");
         const double* gq = (grad_screen && plan.two_e == TWO_E_DIRECT && n > 140) ? direct_schwarz_view(bv.slot) : nullptr;
         std::string gerr;
         if (!launch_gradient(bv, topo, b.aux, d_grad, gwork, glists, lint, s, gerr, gq, 1.0e-3 * plan.direct_tol)) return fail(MQC_HIP_ERR_UNSUPPORTED, gerr);
@@ -848,7 +844,7 @@ static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& j
     const bool embedded = plan.npc > 0 || plan.hx;
     bool want_d = embedded, want_s = false;
     for (int f = 0; f < nf; ++f) {
-        const mqc_hip_scf_result_t* r = b.results[job.start + f];
+        const mqc_hip_scf_result_t* r = frag[f].result;
         if (r->mulliken_charges) { want_d = true; want_s = true; }
         if (r->density) want_d = true;
     }
@@ -860,8 +856,8 @@ static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& j
     if (embedded) HIP_CHECK_RET(fetch(o.U, bv.U));
     if (want_s) HIP_CHECK_RET(fetch(o.S, bv.S));
     bool want_spin = false;
-    if (plan.uhf && !b.spin_out.empty())
-        for (int f = 0; f < nf; ++f) want_spin = want_spin || b.spin_out[job.start + f] != nullptr;
+    if (plan.uhf)
+        for (int f = 0; f < nf; ++f) want_spin = want_spin || frag[f].spin_out != nullptr;
     if (want_spin) { HIP_CHECK_RET(fetch(o.Da, bv.D)); HIP_CHECK_RET(fetch(o.Db, bv.Db)); }
     if (want_d && plan.uhf) {
         std::vector<double> db;
@@ -881,66 +877,52 @@ static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& j
 
 // One topology group of a batch call, in the caller's order: what run_batch runs and where its status goes
 struct Work {
-    const std::vector<int64_t>* idx;
     std::shared_ptr<Topology> topo, aux;
-    std::vector<const double*> xyz;
-    std::vector<const mqc_hip_molecule_t*> mol;
-    std::vector<mqc_hip_scf_result_t*> res;
-    std::vector<double*> pcg;            // mqc_hip_scf_gradient_embedded_batch only: the site gradients (or null), else empty
-    std::vector<const double*> d0;       // mqc_hip_scf_run_batch_restart only: starting densities ...
-    std::vector<double*> spin;           // ... and the spin densities' destinations; empty when the call brought none
-    int mp2_frozen = -1;                 // mqc_hip_rimp2_batch only: frozen orbitals of the topology (>= 0) ...
-    std::vector<double*> mp2_os, mp2_ss; // ... and where the fragments' components and done flags go
-    std::vector<int32_t*> mp2_done;
+    std::vector<FragmentIO> frags;
+    bool embedded_entry = false;         // the call came through mqc_hip_scf_gradient_embedded_batch
+    bool any_d0 = false;                 // mqc_hip_scf_run_batch_restart: some fragment of the group brought a starting density
+    int mp2_frozen = -1;                 // mqc_hip_rimp2_batch only: frozen orbitals of the topology (>= 0)
     std::shared_ptr<AtomicGuess> guess;
-    // deferred small groups (scf_run_batch_impl): the largest group's batch opens the gate, the others wait at it
+    // deferred small groups (schedule_groups): the largest group's batch opens the gate, the others wait at it
     GroupGate* opens = nullptr;
     GroupGate* waits = nullptr;
     int rc = MQC_HIP_OK;
     std::string msg;
 };
 
-// lane < 0: the batch owns both slots (chunks alternate, next chunk prepared ahead); lane 0/1: it runs on that
-// slot only, so that two topology groups can be driven by two host threads at once
+// lane < 0: the batch owns both lanes (chunks alternate, next chunk prepared ahead); lane 0/1: it runs on that
+// lane only, so that two topology groups can be driven by two host threads at once
 static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_options_t& opts, int lane)
 {
     const Topology& topo = *w.topo;
     const Topology* aux = w.aux.get();
-    const bool second = lane == 1;
-    hipStream_t const lane_stream = second ? ctx->stream2 : ctx->stream;
+    Lane& own = ctx->lane[lane == 1 ? 1 : 0];        // where the per-batch tables go
     const double t_begin = now_s();
-    const int ntot = (int)w.xyz.size();
+    const int ntot = (int)w.frags.size();
     Batch b{topo, aux, opts, w.guess.get()};
+    b.embedded_entry = w.embedded_entry; b.any_d0 = w.any_d0; b.mp2_frozen = w.mp2_frozen;
     b.gate = w.opens;
-    if (w.waits && second) b.chain_side = 1;         // deferred on lane 1: its third side stream stays idle (scf_run_batch_impl)
+    if (w.waits && lane == 1) b.chain_side = 1;      // deferred on lane 1: its third side stream stays idle (schedule_groups)
     // whichever way this batch ends (refusal, error return, no chunk that reaches scf_loop), the waiting groups go on
     struct GateOpener { GroupGate* g; ~GateOpener() { if (g) g->open(); } } const opener{w.opens};
     BatchPlan plan;
     // external point charges (FMO / EE-MBE embedding) and h_extra: the same in every fragment of the group (its key says so)
-    plan.npc = ntot > 0 ? w.mol[0]->n_point_charges : 0;
-    plan.hx = ntot > 0 && w.mol[0]->h_extra != nullptr;
+    plan.npc = ntot > 0 ? w.frags[0].mol->n_point_charges : 0;
+    plan.hx = ntot > 0 && w.frags[0].mol->h_extra != nullptr;
     const bool embedded = plan.npc > 0 || plan.hx;
     {
         // Order the batch by compactness (nuclear repulsion, most compact first).  Lanes of a wave are
         // consecutive fragments: with similar geometries side by side, the primitive-pair screening and
         // the Schwarz ballot drop the same work in every lane, so whole waves skip it.
         std::vector<std::pair<double, int>> key(ntot);
-        for (int i = 0; i < ntot; ++i) key[i] = {-nuclear_repulsion(topo, w.xyz[i]), i};
+        for (int i = 0; i < ntot; ++i) key[i] = {-nuclear_repulsion(topo, w.frags[i].mol->xyz), i};
         std::stable_sort(key.begin(), key.end());
-        for (auto& k : key) {
-            b.xyz.push_back(w.xyz[k.second]); b.results.push_back(w.res[k.second]);
-            if (embedded) b.mols.push_back(w.mol[k.second]);
-            if (!w.pcg.empty()) b.pcgrad.push_back(w.pcg[k.second]);      // the same permutation as the results
-            if (!w.d0.empty()) b.d0.push_back(w.d0[k.second]);
-            if (!w.spin.empty()) b.spin_out.push_back(w.spin[k.second]);
-            if (w.mp2_frozen >= 0) { b.mp2_os.push_back(w.mp2_os[k.second]); b.mp2_ss.push_back(w.mp2_ss[k.second]); b.mp2_done.push_back(w.mp2_done[k.second]); }
-        }
-        b.mp2_frozen = w.mp2_frozen;
+        for (auto& k : key) b.frags.push_back(w.frags[k.second]);      // a whole record: inputs and destinations move together
     }
     std::string msg;
     int rc = plan_batch(opts, topo, ntot, plan, msg);
     if (rc == MQC_HIP_OK && embedded && opts.want_gradient) {
-        if (w.pcg.empty()) {
+        if (!b.embedded_entry) {
             msg = "analytic gradients of a fragment embedded in point charges or an extra one-electron operator are not returned by this entry "
                   "(the result record has no slot for the charges' own gradient): point charges go through mqc_hip_scf_gradient_embedded_batch";
             rc = MQC_HIP_ERR_UNSUPPORTED;
@@ -951,18 +933,18 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
     }
     if (rc == MQC_HIP_OK && plan.npc > 0)
         for (int k = 0; k < ntot && rc == MQC_HIP_OK; ++k)
-            if (!b.mols[k]->point_charge_xyz || !b.mols[k]->point_charges) { msg = "point charges announced but their arrays are NULL"; rc = MQC_HIP_ERR_VALIDATION; }
+            if (!b.frags[k].mol->point_charge_xyz || !b.frags[k].mol->point_charges) { msg = "point charges announced but their arrays are NULL"; rc = MQC_HIP_ERR_VALIDATION; }
     if (rc == MQC_HIP_OK && plan.two_e == TWO_E_DF && !aux) { msg = "density fitting needs an auxiliary basis"; rc = MQC_HIP_ERR_VALIDATION; }
-    if (rc != MQC_HIP_OK) return refuse(b.results, rc, msg);
+    if (rc != MQC_HIP_OK) return refuse(b.frags, rc, msg);
     if (w.waits) w.waits->wait();       // nothing of a deferred group is enqueued before the large group's integrals are done
-    rc = upload_topology(ctx, topo, b.td, second ? &ctx->pool_topo2 : &ctx->pool_topo, lane_stream);
+    rc = upload_topology(ctx, topo, b.td, &own.topo, own.stream);
     if (rc != MQC_HIP_OK) return rc;
     if (plan.two_e == TWO_E_DF) {
-        rc = upload_topology(ctx, *aux, b.tdx, second ? &ctx->pool_aux2 : &ctx->pool_aux, lane_stream);
+        rc = upload_topology(ctx, *aux, b.tdx, &own.aux, own.stream);
         if (rc != MQC_HIP_OK) return rc;
         plan.naux = aux->nao;
     }
-    if (plan.xc.ncomp > 0 && (rc = upload_grid(ctx, b, second ? ctx->pool_grid2 : ctx->pool_grid, lane_stream)) != MQC_HIP_OK) return rc;
+    if (plan.xc.ncomp > 0 && (rc = upload_grid(ctx, b, own.grid, own.stream)) != MQC_HIP_OK) return rc;
     plan.npts = b.grid.npts;
     plan_layout(plan, ntot, (int)topo.shells.size(), topo.lmax, xc_radial_cache_on());
 
@@ -973,34 +955,16 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
     if (w.mp2_frozen >= 0) per_frag += rimp2_fragment_bytes(plan.n, plan.nocc, plan.naux, w.mp2_frozen);
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
-    free_b += ctx->pool_main.capacity() + ctx->pool_eri.capacity() + ctx->pool_df.capacity() + ctx->pool_gridw.capacity()
-            + ctx->pool_main2.capacity() + ctx->pool_eri2.capacity() + ctx->pool_df2.capacity() + ctx->pool_gridw2.capacity();
-    // a lane shares the card with the other lane's batch: 40 % each instead of 80 %
-    size_t budget = (size_t)((lane < 0 ? 0.80 : 0.40) * (double)free_b);
-    {
-        // ... and the pools never take what the runtime's scratch reservation may need (see scratch_reservation_bytes)
-        const size_t res = scratch_reservation_bytes(ctx);
-        const size_t room = free_b > res ? free_b - res : free_b / 8;
-        const size_t cap = lane < 0 ? room : room / 2;
-        if (cap < budget) budget = cap;
-    }
-    if (ctx->hbm_budget_bytes && ctx->hbm_budget_bytes < budget) budget = ctx->hbm_budget_bytes;
-    // Chunking.  Small batches run as one chunk on slot 0.  Large ones are cut into >= 4 chunks that
-    // alternate between the two slots (each slot may hold half of the budget).
-    const bool pipelined = lane < 0 && ctx->pipeline_chunks > 1 && ntot >= ctx->pipeline_min_fragments;
-    long chunk = (long)(budget / per_frag);
-    if (lane < 0 && (pipelined || chunk < ntot)) {
-        // more than one chunk: two are resident at a time
-        chunk = (long)(budget / 2 / per_frag);
-        const long want = pipelined ? (ntot + ctx->pipeline_chunks - 1) / ctx->pipeline_chunks : ntot;
-        if (chunk > want) chunk = want;
-    }
+    // what the lanes' pools hold is free to this batch (the counters' few hundred bytes are not counted)
+    for (const Lane& l : ctx->lane)
+        for (int k = 0; k < NPOOL; ++k)
+            if (k != POOL_MISC) free_b += l.pool[k].capacity();
+    const size_t budget = batch_budget_bytes(free_b, scratch_reservation_bytes(ctx), lane, ctx->hbm_budget_bytes);
+    const long chunk = batch_chunk_fragments(budget, per_frag, ntot, lane, ctx->pipeline_chunks, ctx->pipeline_min_fragments);
     if (chunk < 1) return fail(MQC_HIP_ERR_DEVICE, "not enough device memory for one fragment");
-    if (chunk > ntot) chunk = ntot;
-    if (chunk > 60000) chunk = 60000;    // grid.y limit of the J/K kernel
     std::vector<Job> jobs;
     for (int start = 0; start < ntot; start += (int)chunk) {
-        Job j; j.start = start; j.nf = (int)std::min<long>(chunk, ntot - start);
+        Job j; j.frag = &b.frags[start]; j.nf = (int)std::min<long>(chunk, ntot - start);
         jobs.push_back(std::move(j));
     }
 
@@ -1014,12 +978,12 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
         return r;
     };
     const int njobs = (int)jobs.size();
-    // chunks that alternate between the slots: prepare(k + 1) has to return before finish(k) can start, so the integral
+    // chunks that alternate between the lanes: prepare(k + 1) has to return before finish(k) can start, so the integral
     // stage must not keep the host; a single chunk and a lane go from prepare straight into finish, which blocks anyway
     const bool alternating = lane < 0 && njobs > 1;
     if (alternating) { eri_host_may_wait(0, false); eri_host_may_wait(1, false); }
     if (lane >= 0) {
-        // one slot only: chunks strictly one after the other
+        // one lane only: chunks strictly one after the other
         Slot& sl = slots[lane & 1];
         for (int k = 0; k < njobs && rc == MQC_HIP_OK; ++k)
             if ((rc = prepare(ctx, plan, b, sl, jobs[k])) == MQC_HIP_OK) rc = finish(sl, jobs[k]);
@@ -1034,8 +998,8 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
     if (alternating) { eri_host_may_wait(0, true); eri_host_may_wait(1, true); }
     if (rc != MQC_HIP_OK) {
         // drain the streams before the error return hands the pools back
-        if (lane != 1) (void)hipStreamSynchronize(ctx->stream);
-        if (lane != 0) (void)hipStreamSynchronize(ctx->stream2);
+        if (lane != 1) (void)hipStreamSynchronize(ctx->lane[0].stream);
+        if (lane != 0) (void)hipStreamSynchronize(ctx->lane[1].stream);
     }
     (void)hipHostFree(h_counter);
     if (rc != MQC_HIP_OK) return rc;
@@ -1216,33 +1180,22 @@ void mqc_hip_default_options(mqc_hip_scf_options_t* o)
     o->schwarz_tol = 0.0;
 }
 
-int mqc_hip_context_get(int32_t local_rank, mqc_hip_context** out)
+// streams, events and tables of a new context on its device; whatever exists when a step fails is the caller's to destroy
+static int create_context(mqc_hip_context* ctx)
 {
-    if (!out) return fail(MQC_HIP_ERR_VALIDATION, "null context pointer");
-    if (g_ctx) { *out = g_ctx; return MQC_HIP_OK; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(MQC_HIP_ERR_NO_DEVICE, "no HIP device is visible: the MI355X backend has no CPU fallback");
-    auto* ctx = new mqc_hip_context();
-    ctx->device = ((local_rank % ndev) + ndev) % ndev;    // mqc_cuest_context.f90:188
     HIP_CHECK_RET(hipSetDevice(ctx->device));
     HIP_CHECK_RET(hipGetDeviceProperties(&ctx->prop, ctx->device));
     // creation order matters: streams take the 4 hardware queues round-robin, so each lane's main stream and its
     // three side streams land on four different queues
-    HIP_CHECK_RET(hipStreamCreate(&ctx->stream));
-    for (int k = 0; k < 3; ++k) HIP_CHECK_RET(hipStreamCreateWithFlags(&ctx->side[0][k], hipStreamNonBlocking));
-    HIP_CHECK_RET(hipStreamCreate(&ctx->stream2));
-    for (int k = 0; k < 3; ++k) HIP_CHECK_RET(hipStreamCreateWithFlags(&ctx->side[1][k], hipStreamNonBlocking));
-    for (int l = 0; l < 2; ++l) for (int k = 0; k < 2; ++k) HIP_CHECK_RET(hipEventCreateWithFlags(&ctx->evo[l][k], hipEventDisableTiming));
-    for (int l = 0; l < 2; ++l) for (int k = 0; k < 2; ++k) HIP_CHECK_RET(hipEventCreate(&ctx->evs[l][k]));
-    eri_set_side_streams(0, ctx->side[0], 3);
-    eri_set_side_streams(1, ctx->side[1], 3);
-    for (hipEvent_t* e : {&ctx->evb0, &ctx->evb1, &ctx->evb2, &ctx->evb3, &ctx->evq0, &ctx->evq1, &ctx->evq2, &ctx->evq3})
-        HIP_CHECK_RET(hipEventCreate(e));
-    HIP_CHECK_RET(hipEventCreate(&ctx->ev0));
-    HIP_CHECK_RET(hipEventCreate(&ctx->ev1));
-    HIP_CHECK_RET(hipEventCreate(&ctx->ev2));
-    HIP_CHECK_RET(hipEventCreate(&ctx->ev3));
+    for (Lane& l : ctx->lane) {
+        HIP_CHECK_RET(hipStreamCreate(&l.stream));
+        for (hipStream_t& s : l.side) HIP_CHECK_RET(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    }
+    for (Lane& l : ctx->lane) for (hipEvent_t& e : l.chain) HIP_CHECK_RET(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (int l = 0; l < 2; ++l) eri_set_side_streams(l, ctx->lane[l].side, 3);
+    for (Lane& l : ctx->lane)
+        for (hipEvent_t* pair : {l.fock, l.xc, l.step, l.eri})
+            for (int k = 0; k < 2; ++k) HIP_CHECK_RET(hipEventCreate(&pair[k]));
     std::vector<double> boys;
     build_boys_table(boys);
     HIP_CHECK_RET(hipMalloc((void**)&ctx->d_boys, sizeof(double) * boys.size()));
@@ -1255,17 +1208,53 @@ int mqc_hip_context_get(int32_t local_rank, mqc_hip_context** out)
     build_c2s_tables(ctx->h_c2s, ctx->c2s_off);
     HIP_CHECK_RET(hipMalloc((void**)&ctx->d_c2s, sizeof(double) * ctx->h_c2s.size()));
     HIP_CHECK_RET(hipMemcpy(ctx->d_c2s, ctx->h_c2s.data(), sizeof(double) * ctx->h_c2s.size(), hipMemcpyHostToDevice));
-    const char* env = std::getenv("MQC_HIP_HBM_BUDGET_GB");
-    if (env) ctx->hbm_budget_bytes = (size_t)(std::atof(env) * 1024.0 * 1024.0 * 1024.0);
+    return MQC_HIP_OK;
+}
+
+// Everything a context holds, complete or not (null handles are skipped): mqc_hip_finalize, and mqc_hip_context_get
+// when a device call fails midway
+static void destroy_context(mqc_hip_context* ctx)
+{
+    (void)hipSetDevice(ctx->device);
+    for (Lane& l : ctx->lane) if (l.stream) (void)hipStreamSynchronize(l.stream);
+    for (Lane& l : ctx->lane) for (hipStream_t s : l.side) if (s) (void)hipStreamSynchronize(s);
+    // launcher state bound to this device (side streams, fork/join events, list caches), then every pool:
+    // the context's own and the launchers' function-static ones -- a later context_get starts from nothing
+    eri_reset_state();
+    int1e_reset_state();
+    release_all_pools();
+    for (Lane& l : ctx->lane) {
+        for (hipStream_t s : l.side) if (s) (void)hipStreamDestroy(s);
+        for (hipEvent_t* pair : {l.chain, l.fock, l.xc, l.step, l.eri})
+            for (int k = 0; k < 2; ++k) if (pair[k]) (void)hipEventDestroy(pair[k]);
+    }
+    if (ctx->d_unit) (void)hipFree(ctx->d_unit);
+    if (ctx->d_boys) (void)hipFree(ctx->d_boys);
+    if (ctx->d_c2s) (void)hipFree(ctx->d_c2s);
+    for (Lane& l : ctx->lane) if (l.stream) (void)hipStreamDestroy(l.stream);
+    delete ctx;
+}
+
+int mqc_hip_context_get(int32_t local_rank, mqc_hip_context** out)
+{
+    if (!out) return fail(MQC_HIP_ERR_VALIDATION, "null context pointer");
+    if (g_ctx) { *out = g_ctx; return MQC_HIP_OK; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(MQC_HIP_ERR_NO_DEVICE, "no HIP device is visible: the MI355X backend has no CPU fallback");
+    auto* ctx = new mqc_hip_context();
+    ctx->device = ((local_rank % ndev) + ndev) % ndev;    // mqc_cuest_context.f90:188
+    const int rc = create_context(ctx);
+    if (rc != MQC_HIP_OK) { destroy_context(ctx); return rc; }
+    if (const char* env = std::getenv("MQC_HIP_HBM_BUDGET_GB")) ctx->hbm_budget_bytes = (size_t)(std::atof(env) * 1024.0 * 1024.0 * 1024.0);
     // Two-stream chunk pipeline: measured on (H2O)64 MBE-2 RHF/cc-pVDZ it does not pay (1 chunk 261 ms,
     // 2: 251 ms, 4: 281 ms, 8: 340 ms per evaluation -- the ERI kernels and the J/K stream each fill the
     // chip, co-running them only slows both), so it is off unless MQC_HIP_PIPELINE_CHUNKS asks for it.
-    // Batches that exceed the HBM budget still alternate between the two slots.
-    ctx->pipeline_chunks = 1;
+    // Batches that exceed the HBM budget still alternate between the two lanes.
+    ctx->pipeline_chunks = std::max(1, env_int("MQC_HIP_PIPELINE_CHUNKS", 1));
+    ctx->pipeline_min_fragments = std::max(2, env_int("MQC_HIP_PIPELINE_MIN_FRAGMENTS", ctx->pipeline_min_fragments));
     // MQC_HIP_CONCURRENT_GROUPS=0: topology groups of a batch call run one after the other
-    if (const char* cg = std::getenv("MQC_HIP_CONCURRENT_GROUPS")) ctx->concurrent_groups = std::atoi(cg) != 0;
-    if (const char* pc = std::getenv("MQC_HIP_PIPELINE_CHUNKS")) ctx->pipeline_chunks = std::max(1, std::atoi(pc));
-    if (const char* pm = std::getenv("MQC_HIP_PIPELINE_MIN_FRAGMENTS")) ctx->pipeline_min_fragments = std::max(2, std::atoi(pm));
+    ctx->concurrent_groups = env_int("MQC_HIP_CONCURRENT_GROUPS", 1) != 0;
     g_ctx = ctx;
     *out = ctx;
     return MQC_HIP_OK;
@@ -1273,29 +1262,7 @@ int mqc_hip_context_get(int32_t local_rank, mqc_hip_context** out)
 
 int mqc_hip_finalize(void)
 {
-    if (!g_ctx) return MQC_HIP_OK;
-    (void)hipSetDevice(g_ctx->device);
-    (void)hipStreamSynchronize(g_ctx->stream);
-    (void)hipStreamSynchronize(g_ctx->stream2);
-    for (int l = 0; l < 2; ++l) for (int k = 0; k < 3; ++k) if (g_ctx->side[l][k]) (void)hipStreamSynchronize(g_ctx->side[l][k]);
-    // launcher state bound to this device (side streams, fork/join events, list caches), then every pool:
-    // the context's own and the launchers' function-static ones -- a later context_get starts from nothing
-    eri_reset_state();
-    int1e_reset_state();
-    release_all_pools();
-    for (int l = 0; l < 2; ++l) {
-        for (int k = 0; k < 3; ++k) if (g_ctx->side[l][k]) (void)hipStreamDestroy(g_ctx->side[l][k]);
-        for (int k = 0; k < 2; ++k) { if (g_ctx->evo[l][k]) (void)hipEventDestroy(g_ctx->evo[l][k]); if (g_ctx->evs[l][k]) (void)hipEventDestroy(g_ctx->evs[l][k]); }
-    }
-    if (g_ctx->d_unit) (void)hipFree(g_ctx->d_unit);
-    if (g_ctx->d_boys) (void)hipFree(g_ctx->d_boys);
-    if (g_ctx->d_c2s) (void)hipFree(g_ctx->d_c2s);
-    for (hipEvent_t e : {g_ctx->ev0, g_ctx->ev1, g_ctx->ev2, g_ctx->ev3, g_ctx->evb0, g_ctx->evb1, g_ctx->evb2, g_ctx->evb3,
-                         g_ctx->evq0, g_ctx->evq1, g_ctx->evq2, g_ctx->evq3})
-        (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(g_ctx->stream);
-    (void)hipStreamDestroy(g_ctx->stream2);
-    delete g_ctx;
+    if (g_ctx) destroy_context(g_ctx);
     g_ctx = nullptr;
     return MQC_HIP_OK;
 }
@@ -1360,6 +1327,201 @@ static int frozen_core_orbitals(const Topology& topo)
     return nfz;
 }
 
+// what a batch entry was called with
+struct BatchCall {
+    mqc_hip_context* ctx;
+    int64_t nfrag;
+    const mqc_hip_molecule_t* mols;
+    const mqc_hip_basis_t *orbitals, *auxes;
+    const mqc_hip_scf_options_t* opts;
+    mqc_hip_scf_result_t* results;
+    bool fitted() const { return opts->density_fitting && auxes; }
+};
+
+// Step 1: the fragments of a call by topology key; one without geometry or basis fails alone
+static std::map<std::string, std::vector<int64_t>> group_fragments(const BatchCall& c)
+{
+    const mqc_hip_molecule_t* mols = c.mols; const mqc_hip_basis_t *orbitals = c.orbitals, *auxes = c.auxes;
+    std::map<std::string, std::vector<int64_t>> groups;
+    int64_t last = -1;
+    std::string last_key;
+    std::vector<int64_t>* last_group = nullptr;
+    for (int64_t i = 0; i < c.nfrag; ++i) {
+        if (!mols[i].atomic_numbers || !mols[i].xyz || mols[i].n_atoms <= 0 || !orbitals[i].shell_l ||
+            !orbitals[i].nshell_per_atom || !orbitals[i].shell_nprim || !orbitals[i].exponents || !orbitals[i].coefficients) {
+            fill_error(&c.results[i], "fragment has no geometry or basis");
+            continue;
+        }
+        // consecutive fragments that point at the very same element and basis arrays share their key
+        const bool same_as_last = last >= 0 && mols[i].n_atoms == mols[last].n_atoms && mols[i].atomic_numbers == mols[last].atomic_numbers &&
+                                  mols[i].ghost == mols[last].ghost && mols[i].nelec == mols[last].nelec && mols[i].charge == mols[last].charge &&
+                                  mols[i].multiplicity == mols[last].multiplicity && mols[i].n_point_charges == mols[last].n_point_charges && (mols[i].h_extra != nullptr) == (mols[last].h_extra != nullptr) &&
+                                  std::memcmp(&orbitals[i], &orbitals[last], sizeof(mqc_hip_basis_t)) == 0 &&
+                                  (!c.fitted() || std::memcmp(&auxes[i], &auxes[last], sizeof(mqc_hip_basis_t)) == 0);
+        if (!same_as_last) {
+            last_key = topology_key(mols[i], orbitals[i]);
+            if (c.fitted()) last_key += "//" + topology_key(mols[i], auxes[i]);
+            if (mols[i].n_point_charges > 0) last_key += "//pc" + std::to_string(mols[i].n_point_charges);
+            if (mols[i].h_extra) last_key += "//hx";
+            last_group = &groups[last_key];
+        }
+        last = i;
+        last_group->push_back(i);
+    }
+    return groups;
+}
+
+// the topology of a molecule and basis from the context's cache, or built now and cached
+static int cached_topology(mqc_hip_context* ctx, const mqc_hip_molecule_t& mol, const mqc_hip_basis_t& bas, int max_l, bool quartets,
+                           std::shared_ptr<Topology>& out, std::string& err)
+{
+    const std::string k = topology_key(mol, bas) + (quartets ? "|q" : "|n") + std::to_string(max_l);
+    auto it = ctx->topo_cache.find(k);
+    if (it != ctx->topo_cache.end()) { out = it->second; return MQC_HIP_OK; }
+    auto t = std::make_shared<Topology>();
+    const int rc = build_topology(mol, bas, *t, err, max_l, quartets);
+    if (rc != MQC_HIP_OK) return rc;
+    if (ctx->topo_cache.size() >= 16) ctx->topo_cache.clear();
+    ctx->topo_cache[k] = t;
+    out = t;
+    return MQC_HIP_OK;
+}
+
+// Step 2: one topology group becomes a Work -- its topologies from the cache (or built now), the entry's refusals, one
+// record per fragment that runs, the atomic guess.  Returns MQC_HIP_OK, or the code of what kept a fragment (w.frags
+// may still hold the others) or the whole group (w.frags empty) from running, the reason written to their results.
+static int admit_group(const BatchCall& c, const BatchExtras& extras, const std::vector<int64_t>& idx, Work& w)
+{
+    const mqc_hip_molecule_t& mol0 = c.mols[idx[0]];
+    const mqc_hip_basis_t& orb0 = c.orbitals[idx[0]];
+    auto refuse_group = [&](int code, const std::string& why, const char* prefix = "") {
+        for (auto i : idx) fill_error(&c.results[i], prefix + why);
+        set_error(why);
+        return code;
+    };
+    std::string err;
+    int rc = cached_topology(c.ctx, mol0, orb0, KERNEL_LMAX, !c.fitted(), w.topo, err);
+    if (rc != MQC_HIP_OK) return refuse_group(rc, err);
+    if (c.fitted() && (rc = cached_topology(c.ctx, mol0, c.auxes[idx[0]], AUX_LMAX, false, w.aux, err)) != MQC_HIP_OK)
+        return refuse_group(rc, err, "auxiliary basis: ");
+    const bool uhf = runs_unrestricted(*c.opts, w.topo->multiplicity, w.topo->nelec);
+    if (extras.mp2) {
+        // closed shells only, and at least one active occupied orbital: a refused group runs no SCF
+        const int nocc = w.topo->nelec / 2;
+        w.mp2_frozen = extras.frozen_core ? frozen_core_orbitals(*w.topo) : 0;
+        if (uhf)
+            return refuse_group(MQC_HIP_ERR_UNSUPPORTED, "RI-MP2 is built for closed-shell restricted references: unrestricted MP2 (open shells, multiplicity != 1, odd electron counts) is not built");
+        if (w.mp2_frozen >= nocc)
+            return refuse_group(MQC_HIP_ERR_VALIDATION, "RI-MP2: the frozen core (" + std::to_string(w.mp2_frozen) + " orbitals) leaves no active occupied orbital of " + std::to_string(nocc));
+    }
+    w.embedded_entry = extras.embedded_entry;
+    // supplied densities: their size follows from the run's spin treatment; one with a non-finite entry fails its own
+    // fragment and nothing else
+    int worst = MQC_HIP_OK;
+    bool all_d0 = extras.initial_density != nullptr;
+    const size_t nn = (size_t)w.topo->nao * w.topo->nao, cnt = uhf ? 2 * nn : nn;
+    for (auto i : idx) {
+        FragmentIO io{&c.mols[i], &c.results[i]};
+        if (extras.embedded_entry && extras.site_gradients) io.pcgrad = extras.site_gradients[i];
+        if (extras.initial_density) io.d0 = extras.initial_density[i];
+        if (extras.spin_densities_out) io.spin_out = extras.spin_densities_out[i];
+        if (extras.mp2) { io.mp2_os = extras.e_os + i; io.mp2_ss = extras.e_ss + i; io.mp2_done = extras.mp2_done + i; }
+        bool finite = true;
+        if (io.d0) for (size_t k = 0; k < cnt && finite; ++k) finite = std::isfinite(io.d0[k]);
+        if (!finite) {
+            fill_error(io.result, "initial density: a non-finite entry");
+            set_error("initial density of fragment " + std::to_string(i) + ": a non-finite entry");
+            worst = MQC_HIP_ERR_VALIDATION;
+            continue;
+        }
+        w.frags.push_back(io);
+        if (io.d0) w.any_d0 = true; else all_d0 = false;
+    }
+    if (w.frags.empty()) return worst;
+    if ((c.opts->guess == MQC_HIP_GUESS_SAD || c.opts->guess == MQC_HIP_GUESS_SAC) && !all_d0) {
+        // the free atoms are solved here, before any group of this call holds the pools (nested one-atom calls)
+        w.guess = std::make_shared<AtomicGuess>();
+        rc = build_atomic_guess(c.ctx, mol0, orb0, *w.topo, c.opts->guess, c.opts->density_fitting != 0, *w.guess, err);
+        if (rc != MQC_HIP_OK) {
+            // "a guess that will not build is a reason to start elsewhere, not to fail the run" (:175-178): GWH, loudly
+            std::fprintf(stderr, "mqc_hip: initial guess: %s -- falling back to gwh\n", err.c_str());
+            w.guess.reset();
+        }
+    }
+    return worst;
+}
+
+// Step 3: the groups one after the other, each on both lanes; or, with several groups (monomers and dimers of an MBE
+// list), two at a time, each on its own lane: the small group's latency-bound stages hide behind the large one.
+static void schedule_groups(mqc_hip_context* ctx, std::vector<Work>& work, const mqc_hip_scf_options_t& opts)
+{
+    auto run_one = [&](Work& w, int lane) {
+        (void)hipSetDevice(ctx->device);
+        w.rc = run_batch(ctx, w, opts, lane);
+        if (w.rc != MQC_HIP_OK) w.msg = mqc_hip_last_error();      // the error text is thread-local
+    };
+    if (work.size() < 2 || !ctx->concurrent_groups) {
+        for (auto& w : work) run_one(w, -1);
+        return;
+    }
+    // largest group first on lane 0; the others queue up on lane 1, then lane 0 helps with what is left
+    std::sort(work.begin(), work.end(), [](const Work& a, const Work& b) { return a.frags.size() > b.frags.size(); });
+    // A large group's integral stage wants all four hardware queues: its streams alias pairwise onto the queues of
+    // the other lane's streams, and behind the small groups' latency-bound launches (0.1-2.6 ms each) they started
+    // 2.6-12 ms late ((H2O)64 MBE-2: 2016 dimers behind 64 monomers, profiles/r04_b_..._task_stream.txt).  So when
+    // the largest group has at least DEFER_MIN fragments and every other group holds at most one eighth of its
+    // stored integrals (fragments x n_ao^4: a monomer group as numerous as its dimers still is 1/16 of them), the
+    // other groups wait -- on the host -- until the large group's first chunk has joined its integral stage; they
+    // then run next to its SCF loop, which uses one stream (defer_small_groups, host_setup.cpp).
+    // MQC_HIP_DEFER_SMALL_GROUPS_MIN overrides the border; 0: never defer.  The border is
+    // ERI_TASK_STREAM_MIN_FRAGMENTS' (kern_eri.hip).
+    static const long defer_min = [] { const char* e = std::getenv("MQC_HIP_DEFER_SMALL_GROUPS_MIN"); return e ? std::atol(e) : 1024L; }();
+    std::vector<long> group_nfrag;
+    std::vector<int> group_nao;
+    for (const Work& w : work) { group_nfrag.push_back((long)w.frags.size()); group_nao.push_back(w.topo->nao); }
+    const bool defer = defer_small_groups(group_nfrag.data(), group_nao.data(), (int)work.size(), defer_min);
+    // The deferred groups then run next to the large group's SCF loop, which is one stream on one hardware queue;
+    // lane 1's third side stream shares that queue, and a kernel of the loop waits behind whatever sits there (2.3 ms
+    // of the first iteration behind the monomers' one-electron chain and class launches, profiles/r05_e_...).  So a
+    // deferring call keeps lane 1 to its other streams, the one-electron chain on the second side stream.
+    GroupGate gate;
+    if (defer) {
+        work[0].opens = &gate;
+        for (size_t k = 1; k < work.size(); ++k) work[k].waits = &gate;
+        eri_limit_side_streams(1, 2, 1);
+        // MQC_HIP_DEFER_SMALL_GROUPS_TRACE=1: one line per deferring call (the tests read it)
+        static const bool trace = env_opt_in("MQC_HIP_DEFER_SMALL_GROUPS_TRACE");
+        if (trace) std::fprintf(stderr, "mqc_hip: %zu small groups deferred behind a group of %zu fragments\n", work.size() - 1, work[0].frags.size());
+    }
+    // a deferring call hands the large group to lane 0 itself: lane 1's thread may come first to the counter
+    std::atomic<size_t> next{defer ? 1u : 0u};
+    auto worker = [&](int lane) {
+        for (;;) {
+            const size_t k = next.fetch_add(1);
+            if (k >= work.size()) return;
+            run_one(work[k], lane);
+        }
+    };
+    std::thread t1(worker, 1);
+    if (defer) run_one(work[0], 0);
+    worker(0);
+    t1.join();
+    if (defer) eri_limit_side_streams(1, 1 << 20, 2);
+}
+
+// Step 4: a group that failed as a whole marks its fragments that carry no reason of their own; the call's status
+static int collate(const std::vector<Work>& work, int worst)
+{
+    for (const Work& w : work) {
+        if (w.rc == MQC_HIP_OK) continue;
+        worst = w.rc;
+        set_error(w.msg);
+        for (const FragmentIO& f : w.frags)
+            if (!f.result->has_error) fill_error(f.result, w.msg);
+    }
+    return worst;      // a single-fragment call thus reports the fragment's failure as the call's status, like run_cuest_scf
+}
+
 // the body of the batch entries
 static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,
                               const mqc_hip_basis_t* orbitals, const mqc_hip_basis_t* auxes,
@@ -1370,195 +1532,17 @@ static int scf_run_batch_impl(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip
         return fail(MQC_HIP_ERR_VALIDATION, "null argument");
     HIP_CHECK_RET(hipSetDevice(ctx->device));
     for (int64_t i = 0; i < nfrag; ++i) init_result(&results[i]);
-    // group by topology
-    std::map<std::string, std::vector<int64_t>> groups;
-    int64_t last = -1;
-    std::string last_key;
-    std::vector<int64_t>* last_group = nullptr;
-    for (int64_t i = 0; i < nfrag; ++i) {
-        if (!mols[i].atomic_numbers || !mols[i].xyz || mols[i].n_atoms <= 0 || !orbitals[i].shell_l ||
-            !orbitals[i].nshell_per_atom || !orbitals[i].shell_nprim || !orbitals[i].exponents || !orbitals[i].coefficients) {
-            results[i].has_error = 1;
-            std::snprintf(results[i].message, sizeof(results[i].message), "fragment has no geometry or basis");
-            continue;
-        }
-        // consecutive fragments that point at the very same element and basis arrays share their key
-        const bool same_as_last = last >= 0 && mols[i].n_atoms == mols[last].n_atoms && mols[i].atomic_numbers == mols[last].atomic_numbers &&
-                                  mols[i].ghost == mols[last].ghost && mols[i].nelec == mols[last].nelec && mols[i].charge == mols[last].charge &&
-                                  mols[i].multiplicity == mols[last].multiplicity && mols[i].n_point_charges == mols[last].n_point_charges && (mols[i].h_extra != nullptr) == (mols[last].h_extra != nullptr) &&
-                                  std::memcmp(&orbitals[i], &orbitals[last], sizeof(mqc_hip_basis_t)) == 0 &&
-                                  (!(opts->density_fitting && auxes) || std::memcmp(&auxes[i], &auxes[last], sizeof(mqc_hip_basis_t)) == 0);
-        if (!same_as_last) {
-            last_key = topology_key(mols[i], orbitals[i]);
-            if (opts->density_fitting && auxes) last_key += "//" + topology_key(mols[i], auxes[i]);
-            if (mols[i].n_point_charges > 0) last_key += "//pc" + std::to_string(mols[i].n_point_charges);
-            if (mols[i].h_extra) last_key += "//hx";
-            last_group = &groups[last_key];
-        }
-        last = i;
-        last_group->push_back(i);
-    }
+    const BatchCall call{ctx, nfrag, mols, orbitals, auxes, opts, results};
     int worst = MQC_HIP_OK;
-    // ---- per topology group: topology from the cache (or built now), then the batch.  With several groups
-    // (monomers and dimers of an MBE list) two run at a time, each on its own slot: the small group's
-    // latency-bound stages hide behind the large one.
     std::vector<Work> work;
-    auto cached_topology = [&](const std::string& key, const mqc_hip_molecule_t& mol, const mqc_hip_basis_t& bas, int max_l,
-                               bool quartets, std::shared_ptr<Topology>& out, std::string& err) -> int {
-        const std::string k = key + (quartets ? "|q" : "|n") + std::to_string(max_l);
-        auto it = ctx->topo_cache.find(k);
-        if (it != ctx->topo_cache.end()) { out = it->second; return MQC_HIP_OK; }
-        auto t = std::make_shared<Topology>();
-        const int rc = build_topology(mol, bas, *t, err, max_l, quartets);
-        if (rc != MQC_HIP_OK) return rc;
-        if (ctx->topo_cache.size() >= 16) ctx->topo_cache.clear();
-        ctx->topo_cache[k] = t;
-        out = t;
-        return MQC_HIP_OK;
-    };
-    for (auto& kv : groups) {
-        const auto& idx = kv.second;
+    for (const auto& kv : group_fragments(call)) {
         Work w;
-        w.idx = &idx;
-        std::string err;
-        const bool need_quartets = !(opts->density_fitting && auxes);
-        int rc = cached_topology(topology_key(mols[idx[0]], orbitals[idx[0]]), mols[idx[0]], orbitals[idx[0]], KERNEL_LMAX, need_quartets, w.topo, err);
-        if (rc != MQC_HIP_OK) {
-            for (auto i : idx) { results[i].has_error = 1; std::snprintf(results[i].message, sizeof(results[i].message), "%s", err.c_str()); }
-            set_error(err);
-            worst = rc;
-            continue;
-        }
-        if (opts->density_fitting && auxes) {
-            rc = cached_topology(topology_key(mols[idx[0]], auxes[idx[0]]), mols[idx[0]], auxes[idx[0]], AUX_LMAX, false, w.aux, err);
-            if (rc != MQC_HIP_OK) {
-                for (auto i : idx) { results[i].has_error = 1; std::snprintf(results[i].message, sizeof(results[i].message), "auxiliary basis: %s", err.c_str()); }
-                set_error(err);
-                worst = rc;
-                continue;
-            }
-        }
-        if (extras.mp2) {
-            // closed shells only, and at least one active occupied orbital: a refused group runs no SCF
-            std::string why;
-            int code = MQC_HIP_OK;
-            const int nocc = w.topo->nelec / 2;
-            w.mp2_frozen = extras.frozen_core ? frozen_core_orbitals(*w.topo) : 0;
-            if (runs_unrestricted(*opts, w.topo->multiplicity, w.topo->nelec)) {
-                why = "RI-MP2 is built for closed-shell restricted references: unrestricted MP2 (open shells, multiplicity != 1, odd electron counts) is not built";
-                code = MQC_HIP_ERR_UNSUPPORTED;
-            } else if (w.mp2_frozen >= nocc) {
-                why = "RI-MP2: the frozen core (" + std::to_string(w.mp2_frozen) + " orbitals) leaves no active occupied orbital of " + std::to_string(nocc);
-                code = MQC_HIP_ERR_VALIDATION;
-            }
-            if (code != MQC_HIP_OK) {
-                for (auto i : idx) fill_error(&results[i], why);
-                set_error(why);
-                worst = code;
-                continue;
-            }
-        }
-        // supplied densities: their size follows from the run's spin treatment; one with a non-finite entry fails its own
-        // fragment and nothing else
-        std::vector<int64_t> run_idx;
-        bool any_d0 = false, all_d0 = extras.initial_density != nullptr;
-        {
-            const size_t nn = (size_t)w.topo->nao * w.topo->nao;
-            const size_t cnt = runs_unrestricted(*opts, w.topo->multiplicity, w.topo->nelec) ? 2 * nn : nn;
-            for (auto i : idx) {
-                const double* d = extras.initial_density ? extras.initial_density[i] : nullptr;
-                bool finite = true;
-                if (d) for (size_t k = 0; k < cnt && finite; ++k) finite = std::isfinite(d[k]);
-                if (!finite) {
-                    fill_error(&results[i], "initial density: a non-finite entry");
-                    set_error("initial density of fragment " + std::to_string(i) + ": a non-finite entry");
-                    worst = MQC_HIP_ERR_VALIDATION;
-                    continue;
-                }
-                run_idx.push_back(i);
-                if (d) any_d0 = true; else all_d0 = false;
-            }
-        }
-        if (run_idx.empty()) continue;
-        if ((opts->guess == MQC_HIP_GUESS_SAD || opts->guess == MQC_HIP_GUESS_SAC) && !all_d0) {
-            // the free atoms are solved here, before any group of this call holds the pools (nested one-atom calls)
-            w.guess = std::make_shared<AtomicGuess>();
-            rc = build_atomic_guess(ctx, mols[idx[0]], orbitals[idx[0]], *w.topo, opts->guess, opts->density_fitting != 0, *w.guess, err);
-            if (rc != MQC_HIP_OK) {
-                // "a guess that will not build is a reason to start elsewhere, not to fail the run" (:175-178): GWH, loudly
-                std::fprintf(stderr, "mqc_hip: initial guess: %s -- falling back to gwh\n", err.c_str());
-                w.guess.reset();
-            }
-        }
-        for (auto i : run_idx) {
-            w.xyz.push_back(mols[i].xyz); w.mol.push_back(&mols[i]); w.res.push_back(&results[i]);
-            if (extras.embedded_entry) w.pcg.push_back(extras.site_gradients ? extras.site_gradients[i] : nullptr);
-            if (any_d0) w.d0.push_back(extras.initial_density[i]);
-            if (extras.spin_densities_out) w.spin.push_back(extras.spin_densities_out[i]);
-            if (extras.mp2) { w.mp2_os.push_back(extras.e_os + i); w.mp2_ss.push_back(extras.e_ss + i); w.mp2_done.push_back(extras.mp2_done + i); }
-        }
-        work.push_back(std::move(w));
+        const int rc = admit_group(call, extras, kv.second, w);
+        if (rc != MQC_HIP_OK) worst = rc;
+        if (!w.frags.empty()) work.push_back(std::move(w));
     }
-    auto run_one = [&](Work& w, int lane) {
-        (void)hipSetDevice(ctx->device);
-        w.rc = run_batch(ctx, w, *opts, lane);
-        if (w.rc != MQC_HIP_OK) w.msg = mqc_hip_last_error();      // the error text is thread-local
-    };
-    if (work.size() >= 2 && ctx->concurrent_groups) {
-        // largest group first on lane 0; the others queue up on lane 1, then lane 0 helps with what is left
-        std::sort(work.begin(), work.end(), [](const Work& a, const Work& b) { return a.xyz.size() > b.xyz.size(); });
-        // A large group's integral stage wants all four hardware queues: its streams alias pairwise onto the queues of
-        // the other lane's streams, and behind the small groups' latency-bound launches (0.1-2.6 ms each) they started
-        // 2.6-12 ms late ((H2O)64 MBE-2: 2016 dimers behind 64 monomers, profiles/r04_b_..._task_stream.txt).  So when
-        // the largest group has at least DEFER_MIN fragments and every other group holds at most one eighth of its
-        // stored integrals (fragments x n_ao^4: a monomer group as numerous as its dimers still is 1/16 of them), the
-        // other groups wait -- on the host -- until the large group's first chunk has joined its integral stage; they
-        // then run next to its SCF loop, which uses one stream.  MQC_HIP_DEFER_SMALL_GROUPS_MIN overrides the border;
-        // 0: never defer.  The border is ERI_TASK_STREAM_MIN_FRAGMENTS' (kern_eri.hip).
-        static const long defer_min = [] { const char* e = std::getenv("MQC_HIP_DEFER_SMALL_GROUPS_MIN"); return e ? std::atol(e) : 1024L; }();
-        auto weight = [](const Work& x) { const double n = (double)x.topo->nao; return (double)x.xyz.size() * n * n * n * n; };
-        bool defer = defer_min > 0 && (long)work[0].xyz.size() >= defer_min;
-        for (size_t k = 1; k < work.size() && defer; ++k) defer = 8.0 * weight(work[k]) <= weight(work[0]);
-        // The deferred groups then run next to the large group's SCF loop, which is one stream on one hardware queue;
-        // lane 1's third side stream shares that queue, and a kernel of the loop waits behind whatever sits there (2.3 ms
-        // of the first iteration behind the monomers' one-electron chain and class launches, profiles/r05_e_...).  So a
-        // deferring call keeps lane 1 to its other streams, the one-electron chain on the second side stream.
-        GroupGate gate;
-        if (defer) {
-            work[0].opens = &gate;
-            for (size_t k = 1; k < work.size(); ++k) work[k].waits = &gate;
-            eri_limit_side_streams(1, 2, 1);
-            // MQC_HIP_DEFER_SMALL_GROUPS_TRACE=1: one line per deferring call (the tests read it)
-            static const bool trace = [] { const char* e = std::getenv("MQC_HIP_DEFER_SMALL_GROUPS_TRACE"); return e && e[0] == '1'; }();
-            if (trace) std::fprintf(stderr, "mqc_hip: %zu small groups deferred behind a group of %zu fragments\n", work.size() - 1, work[0].xyz.size());
-        }
-        // a deferring call hands the large group to lane 0 itself: lane 1's thread may come first to the counter
-        std::atomic<size_t> next{defer ? 1u : 0u};
-        auto worker = [&](int lane) {
-            for (;;) {
-                const size_t k = next.fetch_add(1);
-                if (k >= work.size()) return;
-                run_one(work[k], lane);
-            }
-        };
-        std::thread t1(worker, 1);
-        if (defer) run_one(work[0], 0);
-        worker(0);
-        t1.join();
-        if (defer) eri_limit_side_streams(1, 1 << 20, 2);
-    } else {
-        for (auto& w : work) run_one(w, -1);
-    }
-    for (auto& w : work) {
-        if (w.rc == MQC_HIP_OK) continue;
-        worst = w.rc;
-        set_error(w.msg);
-        for (auto* r : w.res)
-            if (!r->has_error) { r->has_error = 1; std::snprintf(r->message, sizeof(r->message), "%s", w.msg.c_str()); }
-    }
-    // single-fragment calls report the fragment's failure as the call's status, like run_cuest_scf
-    if (nfrag == 1 && worst != MQC_HIP_OK) return worst;
-    return (nfrag == 1) ? MQC_HIP_OK : worst;
+    schedule_groups(ctx, work, *opts);
+    return collate(work, worst);
 }
 
 int mqc_hip_scf_run_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,

@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 #include <map>
@@ -276,7 +277,7 @@ struct BatchPlan {
     double stol = 0.0, direct_tol = 0.0;       // Schwarz thresholds of the in-core build and of the direct digest
 };
 
-// The device pools one chunk is carved from (a Slot holds one of each)
+// The device pools one chunk is carved from (a lane of the context holds one of each)
 enum : int { POOL_MAIN = 0, POOL_ERI, POOL_MISC, POOL_GRIDW, POOL_DF, NPOOL };
 struct ChunkBytes {
     size_t pool[NPOOL] = {};
@@ -292,21 +293,22 @@ struct CarvedArray {
 
 struct mqc_hip_context {
     int device = 0;
-    hipStream_t stream = nullptr;
     hipDeviceProp_t prop;
     double* d_boys = nullptr;
     double* d_c2s = nullptr;
     std::vector<double> h_c2s;                 // packed l = 0..LMAX_AO, (2l+1) x ncart(l)
     int c2s_off[8];
-    mqc::DevicePool pool_main, pool_eri, pool_topo, pool_misc, pool_grid, pool_gridw, pool_aux, pool_df;
-    // second pipeline slot: the next chunk's integrals are formed while the current chunk iterates
-    mqc::DevicePool pool_main2, pool_eri2, pool_misc2, pool_gridw2, pool_df2, pool_topo2, pool_aux2, pool_grid2;
-    hipStream_t stream2 = nullptr;
-    hipStream_t side[2][3] = {};        // per lane: side streams of the ERI stage, created right after the lane's main stream
-    hipEvent_t evo[2][2] = {};          // per lane: one-electron stage done / orthogonaliser + guess done
-    hipEvent_t evb0 = nullptr, evb1 = nullptr, evb2 = nullptr, evb3 = nullptr;
-    hipEvent_t evq0 = nullptr, evq1 = nullptr, evq2 = nullptr, evq3 = nullptr;   // integral-stage timing per slot
-    hipEvent_t evs[2][2] = {};          // per slot: SCF-step kernel timing
+    // One pipeline lane: a stream with its own pools and events.  While the SCF loop of chunk k runs on one lane, the integrals
+    // of chunk k+1 are formed on the other; two topology groups of one call take a lane each; the stage entries run on lane 0
+    struct Lane {
+        hipStream_t stream = nullptr;       // blocking
+        hipStream_t side[3] = {};           // non-blocking side streams of the ERI stage, created right after the lane's main stream
+        mqc::DevicePool pool[mqc::NPOOL];   // indexed by POOL_*: what a chunk is carved from
+        mqc::DevicePool topo, aux, grid;    // per batch: shell tables of the orbital and auxiliary basis, grid templates
+        // timing pairs: the J/K build, the quadrature and the SCF-step kernel of an iteration; the integral stage of a chunk
+        hipEvent_t fock[2] = {}, xc[2] = {}, step[2] = {}, eri[2] = {};
+        hipEvent_t chain[2] = {};           // one-electron chain forked / orthogonaliser + guess done (timing disabled)
+    } lane[2];
     int pipeline_chunks = 4;            // chunks a large batch is cut into
     int pipeline_min_fragments = 256;   // batches below this run as one chunk
     double* d_unit = nullptr;
@@ -316,8 +318,7 @@ struct mqc_hip_context {
     std::map<std::string, std::shared_ptr<mqc::Topology>> topo_cache;
     // converged free atoms of the superposed-atom guesses: total density (n_atom_ao^2, row-major) per element + shells
     std::map<std::string, std::shared_ptr<std::vector<double>>> atom_cache;
-    int concurrent_groups = 1;          // 1: topology groups of one batch call run two at a time (one per slot)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
+    int concurrent_groups = 1;          // 1: topology groups of one batch call run two at a time (one per lane)
     size_t hbm_budget_bytes = 0;
 };
 
@@ -346,6 +347,19 @@ ChunkBytes carve_chunk(const BatchPlan& p, int nfrag, char* const* bases, BatchV
 size_t fragment_bytes(const BatchPlan& p);
 // fragments per chunk of a batched stage entry: what fits 70 % of free_bytes, at most nfrag and cap, at least one
 int64_t stage_chunk_fragments(size_t free_bytes, size_t per_fragment_bytes, int64_t nfrag, int64_t cap = 16384);
+// The scheduling arithmetic of the batch driver (engine.cpp: run_batch, schedule_groups).  lane < 0: the batch owns both.
+// Bytes a batch may carve: 80 % of free_b (free memory plus what the lanes' pools hold), 40 % on a lane; never what the
+// runtime's scratch reservation may need (a lane: half of the rest); at most a non-zero hbm_budget
+size_t batch_budget_bytes(size_t free_b, size_t reservation, int lane, size_t hbm_budget);
+// fragments per chunk: what fits the budget (half of it where two chunks are resident), at most ntot and 60000; 0: none fits
+long batch_chunk_fragments(size_t budget, size_t per_frag, int ntot, int lane, int pipeline_chunks, int pipeline_min_fragments);
+// whether the small topology groups of a call wait for the largest one's integral stage (groups sorted largest first):
+// the largest has at least defer_min > 0 fragments and every other holds at most 1/8 of its nfrag x nao^4
+bool defer_small_groups(const long* nfrag, const int* nao, int ngroups, long defer_min);
+// MQC_HIP_* switches: on unless "0", off unless "1", an integer with a default; a static const at every site reads each once
+inline bool env_on(const char* name) { const char* e = std::getenv(name); return !(e && e[0] == '0'); }
+inline bool env_opt_in(const char* name) { const char* e = std::getenv(name); return e && e[0] == '1'; }
+inline int env_int(const char* name, int dflt) { const char* e = std::getenv(name); return e ? std::atoi(e) : dflt; }
 // host-side pieces (basis_norm.cpp, boys_table.cpp, batch.cpp)
 void set_error(const std::string& msg);
 int fail(int code, const std::string& msg);

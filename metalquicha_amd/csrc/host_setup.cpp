@@ -382,7 +382,7 @@ size_t jk_tri_lds_bytes(int n, int np)
 // MQC_HIP_ERI_TRI=0: the square.
 bool jk_tri_layout(int n, int np, int nfrag, bool uhf)
 {
-    static const bool on = [] { const char* e = std::getenv("MQC_HIP_ERI_TRI"); return !(e && e[0] == '0'); }();
+    static const bool on = env_on("MQC_HIP_ERI_TRI");
     if (!on || uhf || nfrag < 64 || n > 64 || n % 8 != 0 || np <= 10 * 64) return false;
     if (jk_tri_block(np) > JK_TRI_MAXU2 * 128) return false;
     return jk_tri_lds_bytes(n, np) <= (size_t)160 * 1024 - 1024;
@@ -486,6 +486,44 @@ size_t fragment_bytes(const BatchPlan& p)
 int64_t stage_chunk_fragments(size_t free_bytes, size_t per_fragment_bytes, int64_t nfrag, int64_t cap)
 {
     return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nfrag, cap), (int64_t)((double)free_bytes * 0.7 / (double)per_fragment_bytes)));
+}
+
+size_t batch_budget_bytes(size_t free_b, size_t reservation, int lane, size_t hbm_budget)
+{
+    // a lane shares the card with the other lane's batch: 40 % each instead of 80 %
+    size_t budget = (size_t)((lane < 0 ? 0.80 : 0.40) * (double)free_b);
+    // ... and the pools never take what the runtime's scratch reservation may need (engine.cpp, scratch_reservation_bytes)
+    const size_t room = free_b > reservation ? free_b - reservation : free_b / 8;
+    const size_t cap = lane < 0 ? room : room / 2;
+    if (cap < budget) budget = cap;
+    if (hbm_budget && hbm_budget < budget) budget = hbm_budget;
+    return budget;
+}
+
+// Small batches run as one chunk on lane 0.  Large ones are cut into >= pipeline_chunks chunks that alternate between
+// the two lanes (each lane may hold half of the budget).
+long batch_chunk_fragments(size_t budget, size_t per_frag, int ntot, int lane, int pipeline_chunks, int pipeline_min_fragments)
+{
+    const bool pipelined = lane < 0 && pipeline_chunks > 1 && ntot >= pipeline_min_fragments;
+    long chunk = (long)(budget / per_frag);
+    if (lane < 0 && (pipelined || chunk < ntot)) {
+        // more than one chunk: two are resident at a time
+        chunk = (long)(budget / 2 / per_frag);
+        const long want = pipelined ? (ntot + pipeline_chunks - 1) / pipeline_chunks : ntot;
+        if (chunk > want) chunk = want;
+    }
+    if (chunk < 1) return 0;
+    if (chunk > ntot) chunk = ntot;
+    if (chunk > 60000) chunk = 60000;    // grid.y limit of the J/K kernel
+    return chunk;
+}
+
+bool defer_small_groups(const long* nfrag, const int* nao, int ngroups, long defer_min)
+{
+    auto weight = [&](int k) { const double n = (double)nao[k]; return (double)nfrag[k] * n * n * n * n; };
+    bool defer = ngroups > 0 && defer_min > 0 && nfrag[0] >= defer_min;
+    for (int k = 1; k < ngroups && defer; ++k) defer = 8.0 * weight(k) <= weight(0);
+    return defer;
 }
 
 double nuclear_repulsion(const Topology& topo, const double* xyz)

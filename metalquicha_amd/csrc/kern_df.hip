@@ -976,7 +976,7 @@ static bool df_jk_wave_launch(const BatchView& bv, int oa, hipStream_t s)
 // n <= 48, one orbital tile, exchange wanted (MQC_HIP_DF_WAVE=0: the workgroup kernel)
 static bool df_jk_wave_dispatch(const BatchView& bv, int oa, hipStream_t s, DfJkRoute& r)
 {
-    static const bool on = [] { const char* e = std::getenv("MQC_HIP_DF_WAVE"); return !(e && e[0] == '0'); }();
+    static const bool on = env_on("MQC_HIP_DF_WAVE");
     if (!on || bv.exx == 0.0 || bv.n > 48 || bv.nocc > 16) return false;
     const int nt = (bv.n + 15) / 16, nlw = (bv.npair + 63) / 64;
     if (nt == 1 && nlw <= 3) { r = {DF_JK_WAVE, 1, 3, true}; return df_jk_wave_launch<1, 3>(bv, oa, s); }
@@ -1091,7 +1091,7 @@ void launch_df_integrals(const BatchView& bv, const Topology& topo, const Topolo
 void launch_df_fit(const BatchView& bv, hipStream_t s)
 {
     {
-        static const bool v1 = [] { const char* e = std::getenv("MQC_HIP_DF_CHOL_V1"); return e && e[0] == '1'; }();
+        static const bool v1 = env_opt_in("MQC_HIP_DF_CHOL_V1");
         const size_t npad = (size_t)((bv.naux + 15) / 16) * 16;
         const size_t lds_m = sizeof(double) * (npad * 16 + 2 * 16 * 17 + 8);
         if (v1 || lds_m > 150 * 1024) {
@@ -1124,7 +1124,7 @@ DfJkRoute launch_df_jk(const BatchView& bv, bool only_active, hipStream_t s)
     DfJkRoute r{};
     (void)hipMemsetAsync(bv.K, 0, sizeof(double) * (size_t)bv.nfrag * n * n, s);
     // MQC_HIP_DF_V1=1: the round-1 kernels (J as one workgroup per fragment with two passes over B, K on the vector units)
-    static const bool v1 = [] { const char* e = std::getenv("MQC_HIP_DF_V1"); return e && e[0] == '1'; }();
+    static const bool v1 = env_opt_in("MQC_HIP_DF_V1");
     if (!v1) {
         (void)hipMemsetAsync(bv.J, 0, sizeof(double) * (size_t)bv.nfrag * n * n, s);
         if (df_jk_wave_dispatch(bv, oa, s, r)) return r;

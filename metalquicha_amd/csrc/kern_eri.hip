@@ -64,14 +64,14 @@ ERI_CLASSES(DIG_DECL)
 // MQC_HIP_NO_TWIN_BLOCKS=1 forces the segmented treatment everywhere (A/B measurements, tests)
 static bool twin_blocks_disabled()
 {
-    static const bool off = [] { const char* e = std::getenv("MQC_HIP_NO_TWIN_BLOCKS"); return e && e[0] == '1'; }();
+    static const bool off = env_opt_in("MQC_HIP_NO_TWIN_BLOCKS");
     return off;
 }
 
 // MQC_HIP_NO_BLOCK_SHARING=1: every fragment forms all of its own integral blocks
 static bool block_sharing_disabled()
 {
-    static const bool off = [] { const char* e = std::getenv("MQC_HIP_NO_BLOCK_SHARING"); return e && e[0] == '1'; }();
+    static const bool off = env_opt_in("MQC_HIP_NO_BLOCK_SHARING");
     return off;
 }
 
@@ -373,7 +373,7 @@ void launch_eri_bounds(const BatchView& bv, const Topology& topo, double schwarz
     // primitive quartets of an oxygen (1s 1s|1s 1s) survive), i.e. the threads the whole launch waited for (the
     // (ss| launch of 2016 dimers: 6.8 ms, ahead of every class kernel).  They are formed for fragment 0 only and
     // copied (schwarz_copy_kernel, first thing in launch_eri).  MQC_HIP_SCHWARZ_ONE_CENTRE=0 turns that off.
-    static const bool one_centre = [] { const char* e = std::getenv("MQC_HIP_SCHWARZ_ONE_CENTRE"); return !(e && e[0] == '0'); }();
+    static const bool one_centre = env_on("MQC_HIP_SCHWARZ_ONE_CENTRE");
     const bool split = one_centre && bv.nfrag >= 4;
     for (size_t k = 0; k + 1 < topo.pairs.size(); k += 2) {
         int A = topo.pairs[k], B = topo.pairs[k + 1];
@@ -629,9 +629,9 @@ static void launch_entry(const BatchView& bv, const Topology& topo, const EriLau
     // MQC_HIP_ERI_GENERAL=k: classes whose total angular momentum is >= k AND that would take the pass kernels go
     // through the wave-cooperative LDS kernel instead (no scratch, one wave per quartet and fragment);
     // default 7: (dd|dp) and (dd|dd); k moves the border (4 = every pass class, 99 = f shells only)
-    static const int gen_from = [] { const char* e = std::getenv("MQC_HIP_ERI_GENERAL"); return e ? std::atoi(e) : 7; }();
+    static const int gen_from = env_int("MQC_HIP_ERI_GENERAL", 7);
     // small batches only, and only the dense half
-    static const int twin_wave_max = [] { const char* e = std::getenv("MQC_HIP_TWIN_WAVE_MAX"); return e ? std::atoi(e) : ERI_TWIN_WAVE_MAX_FRAGMENTS; }();
+    static const int twin_wave_max = env_int("MQC_HIP_TWIN_WAVE_MAX", ERI_TWIN_WAVE_MAX_FRAGMENTS);
     const auto& cl = topo.classes[L.cls];
     const HalfList h = which == Half::dense ? HalfList{d + L.dense_off, L.dense_n, nullptr, 0} : HalfList{d + L.sh_off, L.sh_n, d + L.task_off, L.ntasks};
     const bool twin_wave = which == Half::dense && bv.nfrag <= twin_wave_max;
@@ -709,8 +709,8 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
     // A range-separated hybrid calls launch_eri twice (eri, then eri_lr): the caller's stream joins every side stream
     // at the end of a call and the next call's fork event is recorded behind that join, so the second call's tasks and
     // copy start after the whole first call and work on the second tensor only (the view is passed by value).
-    static const int spread_max = [] { const char* e = std::getenv("MQC_HIP_ERI_SPREAD_MAX"); return e ? std::atoi(e) : (1 << 30); }();
-    static const int task_stream_min = [] { const char* e = std::getenv("MQC_HIP_ERI_TASK_STREAM_MIN"); return e ? std::atoi(e) : ERI_TASK_STREAM_MIN_FRAGMENTS; }();
+    static const int spread_max = env_int("MQC_HIP_ERI_SPREAD_MAX", (1 << 30));
+    static const int task_stream_min = env_int("MQC_HIP_ERI_TASK_STREAM_MIN", ERI_TASK_STREAM_MIN_FRAGMENTS);
     const bool spread = bv.nfrag <= spread_max;
     const bool forked = cc->shared || spread;
     const bool task_stream = cc->shared && bv.nfrag >= task_stream_min;      // !plan.on: exactly the earlier path
@@ -731,14 +731,14 @@ void launch_eri(const BatchView& bv_in, const Topology& topo, double schwarz_tol
     // as its neighbours let it, the stage as long as the summed work: 2016 dimers, same box, builds
     // alternating, five runs each, ms per evaluation median / min / max 86.19 / 85.91 / 86.32 -> 85.21 / 84.71 / 85.79,
     // stage clock 29.05 -> 28.09 ms (profiles/r06_a).
-    static const int dispatch_min = [] { const char* e = std::getenv("MQC_HIP_ERI_DISPATCH_MIN"); return e ? std::atoi(e) : ERI_TASK_STREAM_MIN_FRAGMENTS; }();
+    static const int dispatch_min = env_int("MQC_HIP_ERI_DISPATCH_MIN", ERI_TASK_STREAM_MIN_FRAGMENTS);
     static const int dispatch_depth = [] {
         const char* e = std::getenv("MQC_HIP_ERI_DISPATCH_DEPTH");
         const int v = e ? std::atoi(e) : 2;
         return v < 1 ? 1 : (v > eri_dispatch::MAX_DEPTH ? eri_dispatch::MAX_DEPTH : v);
     }();
     // MQC_HIP_ERI_DISPATCH_TRACE=1: one line per dispatching call (the tests read it)
-    static const bool dispatch_trace = [] { const char* e = std::getenv("MQC_HIP_ERI_DISPATCH_TRACE"); return e && e[0] == '1'; }();
+    static const bool dispatch_trace = env_opt_in("MQC_HIP_ERI_DISPATCH_TRACE");
     bool dynamic = spread && st.host_may_wait && dispatch_min >= 0 && bv.nfrag >= dispatch_min && hipPeekAtLastError() == hipSuccess;
     if (dynamic) {
         auto make = [&](hipEvent_t& e) { if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { e = nullptr; dynamic = false; } };
@@ -986,7 +986,7 @@ void launch_jk_direct_incremental(const BatchView& bv, const Topology& topo, dou
     // OFF by default: measured on (H2O)8 / cc-pVDZ (n = 192, scripts/direct_incremental_probe.py) the corrections dropped
     // by the density screen cost three more SCF cycles at 1e-10 / 1e-8 (17 against 14) for the same energy and no gain
     // in wall time (1.23 s against 1.16 s); MQC_HIP_DIRECT_INCREMENTAL=1 turns it on
-    static const bool on = [] { const char* e = std::getenv("MQC_HIP_DIRECT_INCREMENTAL"); return e && e[0] == '1'; }();
+    static const bool on = env_opt_in("MQC_HIP_DIRECT_INCREMENTAL");
     if (!on || bv.uhf) { launch_jk_direct(bv, topo, thresh, only_active, s); return; }
     DirectIncrState& st = g_direct_incr[bv.slot & 1];
     const int n = bv.n, oa = only_active ? 1 : 0;

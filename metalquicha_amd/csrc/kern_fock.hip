@@ -840,7 +840,7 @@ static JkRoute jk_launch(const BatchView& bv, int oa, size_t lds, hipStream_t s)
 
 static bool jk_rowcoop_on()
 {
-    static const bool on = [] { const char* e = std::getenv("MQC_HIP_JK_ROWCOOP"); return !(e && e[0] == '0'); }();
+    static const bool on = env_on("MQC_HIP_JK_ROWCOOP");
     return on;
 }
 
@@ -881,7 +881,7 @@ JkRoute launch_jk_incore(const BatchView& bv, bool only_active, hipStream_t s)
         // Workgroups per fragment: every workgroup pays a prologue (packed density, 23 KB of LDS zeroed) and a flush, so
         // as few as keep three rounds of workgroups on the card -- ONE from 768 fragments on (2016 dimers, same box:
         // 3.12 ms per launch with one, 3.27 with three, 3.55 with six).  MQC_HIP_JK_TRI_WG overrides (measurements).
-        static const int gx_env = [] { const char* e = std::getenv("MQC_HIP_JK_TRI_WG"); return e ? std::atoi(e) : 0; }();
+        static const int gx_env = env_int("MQC_HIP_JK_TRI_WG", 0);
         int gx = gx_env > 0 ? gx_env : (768 + bv.nfrag - 1) / bv.nfrag;
         const int maxx = ((np + 1) / 2 + JK_TRI_NW - 1) / JK_TRI_NW;
         if (gx < 1) gx = 1;

@@ -997,7 +997,7 @@ bool launch_gradient(const BatchView& bv, const Topology& topo, const Topology* 
     double* Wm = work;
     double* Dtot = bv.D;
     // MQC_HIP_GRAD_TIMING=1 (measurement): the span of this stage and of its XC part on stderr, per batch
-    static const bool timing = [] { const char* e = std::getenv("MQC_HIP_GRAD_TIMING"); return e && e[0] == '1'; }();
+    static const bool timing = env_opt_in("MQC_HIP_GRAD_TIMING");
     hipEvent_t ev[3] = {};
     if (timing) for (auto& e : ev) { (void)hipEventCreate(&e); }
     if (timing) (void)hipEventRecord(ev[0], s);

@@ -148,7 +148,7 @@ bool launch_pc_gradient(const BatchView& bv, const Topology& topo, const double*
     static std::vector<int> host_lists[2];      // stays alive while the upload is in flight
     const HermiteLists hl = hermite_lists<true>(topo, true);
     // MQC_HIP_GRAD_TIMING=1 (measurement): the span of this stage on stderr, per chunk
-    static const bool timing = [] { const char* e = std::getenv("MQC_HIP_GRAD_TIMING"); return e && e[0] == '1'; }();
+    static const bool timing = env_opt_in("MQC_HIP_GRAD_TIMING");
     hipEvent_t ev[3] = {};
     if (timing) for (auto& e : ev) { (void)hipEventCreate(&e); }
     if (timing) (void)hipEventRecord(ev[0], s);

@@ -403,7 +403,7 @@ void launch_int1e(const BatchView& bv_in, const Topology& topo, hipStream_t s)
     static DevicePool far_slot[2];
     BatchView bv = bv_in;
     bv.pc_far_r2 = nullptr; bv.pc_far_tab = nullptr;
-    static const bool far_on = [] { const char* e = std::getenv("MQC_HIP_PC_FAR"); return !(e && e[0] == '0'); }();
+    static const bool far_on = env_on("MQC_HIP_PC_FAR");
     if (far_on && bv.npc >= PC_FAR_MIN && bv.pc) {
         // per atom: beyond R^2 = 42 / p_min (p_min = twice the most diffuse exponent on the atom) a charge is far for
         // every primitive pair on it

@@ -266,7 +266,7 @@ bool launch_rimp2(const BatchView& bv, int n_frozen, double* h_out, hipStream_t 
     // C in LDS where it leaves room for at least two waves' buffers (one workgroup per CU, up to eight waves) ...
     const size_t c_lds = sizeof(double) * (size_t)(4 * ((n + 3) / 4)) * (nop + mv.nvpad);
     // (MQC_HIP_MP2_C_LDS=0: never, the A/B switch of the two variants)
-    static const bool clds_on = [] { const char* e = std::getenv("MQC_HIP_MP2_C_LDS"); return !(e && e[0] == '0'); }();
+    static const bool clds_on = env_on("MQC_HIP_MP2_C_LDS");
     const bool clds = clds_on && nop <= 64 && c_lds + lds_of(2, nop) <= lds_max;
     int nw = MP2_TW;
     size_t lds = 0;
@@ -287,7 +287,7 @@ bool launch_rimp2(const BatchView& bv, int n_frozen, double* h_out, hipStream_t 
     }
     mv.ts = mv.oc + 1;
     // MQC_HIP_MP2_TIMING=1 (measurement): the span of this stage on stderr, per chunk
-    static const bool timing = [] { const char* e = std::getenv("MQC_HIP_MP2_TIMING"); return e && e[0] == '1'; }();
+    static const bool timing = env_opt_in("MQC_HIP_MP2_TIMING");
     hipEvent_t ev[3] = {};
     if (timing) for (auto& e : ev) { (void)hipEventCreate(&e); }
     if (timing) (void)hipEventRecord(ev[0], s);

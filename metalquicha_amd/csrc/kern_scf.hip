@@ -1014,7 +1014,7 @@ void launch_scf_step_wide(const BatchView& bv, hipStream_t s);
 // batches of at most this many fragments take the 512-thread build (MQC_HIP_SCF_WIDE_MAX; 0 turns it off)
 static int scf_wide_max()
 {
-    static const int v = [] { const char* e = std::getenv("MQC_HIP_SCF_WIDE_MAX"); return e ? std::atoi(e) : 640; }();
+    static const int v = env_int("MQC_HIP_SCF_WIDE_MAX", 640);
     return v;
 }
 #define MQC_SCF_PUBLIC(name) name

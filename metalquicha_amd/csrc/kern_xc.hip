@@ -1344,7 +1344,7 @@ static void xc_tile_launch(const BatchView& bv, int oa, hipStream_t s)
     size_t lds = sizeof(double) * ((size_t)(GGA ? 4 : 2) * np * (PT + 1) + 8 * PT + 3 * 64 + 6 * PT + ((tab + 1) & ~(size_t)1));
     // the radial tile rides in LDS when that does not cost a resident workgroup (OCC of them share 160 KB)
     const size_t rad_lds = sizeof(double) * (size_t)bv.topo.nshell * 2 * PT;
-    static const bool rad_lds_on = [] { const char* e = std::getenv("MQC_HIP_XC_RADIAL_LDS"); return !(e && e[0] == '0'); }();
+    static const bool rad_lds_on = env_on("MQC_HIP_XC_RADIAL_LDS");
     const size_t lds_cap = (size_t)160 * 1024 / (OCC < 1 ? 1 : OCC) - 512;
     if (rad_lds_on && bv.grid.rad && bv.grid.rad_pt == PT && (lds + rad_lds <= lds_cap || (lds > lds_cap && lds + rad_lds <= 156 * 1024))) {
         lds += rad_lds;
@@ -1352,7 +1352,7 @@ static void xc_tile_launch(const BatchView& bv, int oa, hipStream_t s)
     }
     auto kern = xc_tile_kernel<GGA, PT, JMAX, OCC, DREG, NTC, false, NWV, RSH>;
     if constexpr (DREG) {
-        static const bool fast_on = [] { const char* e = std::getenv("MQC_HIP_XC_FAST_SLAB"); return !(e && e[0] == '0'); }();
+        static const bool fast_on = env_on("MQC_HIP_XC_FAST_SLAB");
         if (fast_on && (oa & 2) && bv.topo.lmax <= 2) kern = xc_tile_kernel<GGA, PT, JMAX, OCC, DREG, NTC, true, NWV, RSH>;
     }
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1393,7 +1393,7 @@ static bool xc_tile_dispatch(const BatchView& bv, int oa, hipStream_t s)
     // 64 < n <= 96 (def2-TZVP water dimer, n = 86): still 32-point tiles with the density fragments in registers, ONE
     // workgroup per CU (101 KB of slab) and the whole register file for its four waves -- against 16-point tiles the
     // functional runs on twice the lanes and the density is not re-read from L2 per tile (MQC_HIP_XC_WIDE_TILE=0: off)
-    static const bool wide_tile = [] { const char* e = std::getenv("MQC_HIP_XC_WIDE_TILE"); return !(e && e[0] == '0'); }();
+    static const bool wide_tile = env_on("MQC_HIP_XC_WIDE_TILE");
     if (wide_tile && nt <= 6) {
         // (eight waves per workgroup -- half the accumulators per wave -- measured the same: 3.94 against 3.92 s)
         if (nt == 5) xc_tile_launch<GGA, 32, 7, 1, true, 5>(bv, oa, s);
@@ -1765,7 +1765,7 @@ static bool xc_pipe_launch(const BatchView& bv, int oa, hipStream_t s)
 template <bool GGA>
 static bool xc_pipe_dispatch(const BatchView& bv, int oa, hipStream_t s)
 {
-    static const bool on = [] { const char* e = std::getenv("MQC_HIP_XC_PIPE"); return e && e[0] == '1'; }();
+    static const bool on = env_opt_in("MQC_HIP_XC_PIPE");
     if (!on || bv.uhf || bv.n > 64 || bv.topo.lmax > 2 || !bv.grid.rad || bv.grid.rad_pt != XP_PT) return false;
     // no RSH instantiation: range-separated hybrids (ITYH, wB97X) go on to the tile kernel
     if (bv.xc.omega > 0.0) return false;
@@ -2235,7 +2235,7 @@ static bool xc_split_launch(const BatchView& bv, int oa, hipStream_t s)
 template <bool GGA>
 static bool xc_split_dispatch(const BatchView& bv, int oa, hipStream_t s)
 {
-    static const bool on = [] { const char* e = std::getenv("MQC_HIP_XC_SPLIT"); return !(e && e[0] == '0'); }();
+    static const bool on = env_on("MQC_HIP_XC_SPLIT");
     if (!on || bv.uhf || bv.n > 96 || bv.topo.lmax > 3 || !bv.grid.rad || bv.grid.rad_pt != XS_PT || !bv.grid.pt4) return false;
     const int nt = (bv.n + 15) / 16;
     const bool f = bv.topo.lmax == 3;
@@ -3132,7 +3132,7 @@ bool launch_xc_gradient(const BatchView& bv, double* d_grad, hipStream_t s, std:
     const int NA = gga ? 10 : 4, NX = (gga ? 4 : 1) * (uks ? 2 : 1);
     const size_t lds = sizeof(double) * ((size_t)(NA + NX) * n * (XG_PT + 1) + 8 * XG_PT + 3 * bv.topo.natoms + 8) + sizeof(int) * (bv.topo.natoms + 2 + XG_PT);
     // MQC_HIP_XC_GRAD_WIDE=1: the wide kernel at every n (A/B switch); otherwise only where the slab above does not fit
-    static const bool wide_env = [] { const char* e = std::getenv("MQC_HIP_XC_GRAD_WIDE"); return e && e[0] == '1'; }();
+    static const bool wide_env = env_opt_in("MQC_HIP_XC_GRAD_WIDE");
     if (wide_env || lds > 160 * 1024) {
         auto wide_lds = [&](int pt) { return sizeof(double) * ((size_t)(4 + NX) * n * (pt + 1) + 8 * pt + 3 * bv.topo.natoms + 8) + sizeof(int) * (pt + 8); };
         const int pt = wide_lds(8) <= 160 * 1024 ? 8 : 4;

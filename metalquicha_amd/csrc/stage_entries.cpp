@@ -1,6 +1,6 @@
 // stage_entries.cpp -- the stage-level extern "C" entry points of libmqc_hip.so: one stage of the engine on the caller's
 // inputs (one-electron integrals, the ERI tensor, J/K, Coulomb and potential batches, the XC quadrature, the
-// eigen-solver, the DIIS coefficients).  They run on slot 0 with the driver's own pieces (driver.hpp).
+// eigen-solver, the DIIS coefficients).  They run on lane 0 with the driver's own pieces (driver.hpp).
 #include "driver.hpp"
 #include <algorithm>
 #include <cmath>
@@ -87,8 +87,8 @@ int mqc_hip_int1e(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc
     StageBatch sb;
     int rc = stage_setup(ctx, mol, bas, false, sb);
     if (rc != MQC_HIP_OK) return rc;
-    launch_int1e(sb.bv, sb.topo, ctx->stream);
-    if ((rc = sync_and_check(ctx->stream)) != MQC_HIP_OK) return rc;
+    launch_int1e(sb.bv, sb.topo, ctx->lane[0].stream);
+    if ((rc = sync_and_check(ctx->lane[0].stream)) != MQC_HIP_OK) return rc;
     const size_t nn = (size_t)sb.topo.nao * sb.topo.nao;
     if (S) HIP_CHECK_RET(hipMemcpy(S, sb.bv.S, sizeof(double) * nn, hipMemcpyDeviceToHost));
     if (T) HIP_CHECK_RET(hipMemcpy(T, sb.bv.W, sizeof(double) * nn, hipMemcpyDeviceToHost));
@@ -104,9 +104,9 @@ static int stage_eri_packed(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol,
     int rc = stage_setup(ctx, mol, bas, true, sb);
     if (rc != MQC_HIP_OK) return rc;
     // stage-level check of the tensor: poison it first, so that an element no class list covers shows up as NaN
-    HIP_CHECK_RET(hipMemsetAsync(sb.bv.eri, 0xFF, sizeof(double) * (size_t)sb.topo.npair * sb.topo.npair, ctx->stream));
-    launch_eri(sb.bv, sb.topo, schwarz_tol, ctx->stream, nullptr, omega);
-    if ((rc = sync_and_check(ctx->stream)) != MQC_HIP_OK) return rc;
+    HIP_CHECK_RET(hipMemsetAsync(sb.bv.eri, 0xFF, sizeof(double) * (size_t)sb.topo.npair * sb.topo.npair, ctx->lane[0].stream));
+    launch_eri(sb.bv, sb.topo, schwarz_tol, ctx->lane[0].stream, nullptr, omega);
+    if ((rc = sync_and_check(ctx->lane[0].stream)) != MQC_HIP_OK) return rc;
     const size_t np = (size_t)sb.topo.npair;
     HIP_CHECK_RET(hipMemcpy(M, sb.bv.eri, sizeof(double) * np * np, hipMemcpyDeviceToHost));
     return MQC_HIP_OK;
@@ -130,10 +130,10 @@ int mqc_hip_jk_incore(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const
     int rc = stage_setup(ctx, mol, bas, true, sb);
     if (rc != MQC_HIP_OK) return rc;
     const size_t nn = (size_t)sb.topo.nao * sb.topo.nao;
-    launch_eri(sb.bv, sb.topo, 0.0, ctx->stream);
-    HIP_CHECK_RET(hipMemcpyAsync(sb.bv.D, D, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));
-    launch_jk_incore(sb.bv, false, ctx->stream);
-    if ((rc = sync_and_check(ctx->stream)) != MQC_HIP_OK) return rc;
+    launch_eri(sb.bv, sb.topo, 0.0, ctx->lane[0].stream);
+    HIP_CHECK_RET(hipMemcpyAsync(sb.bv.D, D, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->lane[0].stream));
+    launch_jk_incore(sb.bv, false, ctx->lane[0].stream);
+    if ((rc = sync_and_check(ctx->lane[0].stream)) != MQC_HIP_OK) return rc;
     HIP_CHECK_RET(hipMemcpy(J, sb.bv.J, sizeof(double) * nn, hipMemcpyDeviceToHost));
     HIP_CHECK_RET(hipMemcpy(K, sb.bv.K, sizeof(double) * nn, hipMemcpyDeviceToHost));
     return MQC_HIP_OK;
@@ -152,11 +152,11 @@ int mqc_hip_jk_direct(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const
     if (sb.topo.nao > 256) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large (n_ao <= 256)");
     const size_t nn = (size_t)sb.topo.nao * sb.topo.nao;
     sb.bv.exx = exx;
-    HIP_CHECK_RET(hipMemsetAsync(sb.bv.eri_count, 0, sizeof(unsigned long long), ctx->stream));
-    HIP_CHECK_RET(hipMemcpyAsync(sb.bv.D, D, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->stream));
-    launch_direct_setup(sb.bv, sb.topo, ctx->stream);
-    launch_jk_direct(sb.bv, sb.topo, schwarz_tol, false, ctx->stream);
-    if ((rc = sync_and_check(ctx->stream)) != MQC_HIP_OK) return rc;
+    HIP_CHECK_RET(hipMemsetAsync(sb.bv.eri_count, 0, sizeof(unsigned long long), ctx->lane[0].stream));
+    HIP_CHECK_RET(hipMemcpyAsync(sb.bv.D, D, sizeof(double) * nn, hipMemcpyHostToDevice, ctx->lane[0].stream));
+    launch_direct_setup(sb.bv, sb.topo, ctx->lane[0].stream);
+    launch_jk_direct(sb.bv, sb.topo, schwarz_tol, false, ctx->lane[0].stream);
+    if ((rc = sync_and_check(ctx->lane[0].stream)) != MQC_HIP_OK) return rc;
     HIP_CHECK_RET(hipMemcpy(J, sb.bv.J, sizeof(double) * nn, hipMemcpyDeviceToHost));
     HIP_CHECK_RET(hipMemcpy(K, sb.bv.K, sizeof(double) * nn, hipMemcpyDeviceToHost));
     return MQC_HIP_OK;
@@ -204,14 +204,14 @@ int mqc_hip_coulomb_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_mol
     // full mode: in-core (the packed tensor of every fragment of a chunk resident at once, chunks sized to the free HBM).
     // cross mode: the direct digest over the filtered lists -- no tensor at all, the few (leading | source) quartets
     // are contracted with the density as they are formed (Schwarz screening at 1e-12)
-    static const bool cross_incore = [] { const char* e = std::getenv("MQC_HIP_COULOMB_CROSS_INCORE"); return e && e[0] == '1'; }();
+    static const bool cross_incore = env_opt_in("MQC_HIP_COULOMB_CROSS_INCORE");
     const bool direct = cross && !cross_incore;
     if (!direct && !incore_supported(topo.nao)) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large for the in-core ERI path");
     if (topo.nao > 256) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large (n_ao <= 256)");
     const BatchPlan plan = stage_plan(topo, direct ? TWO_E_DIRECT : TWO_E_INCORE, (int)std::min<int64_t>(nfrag, 1 << 30));
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
-    free_b += ctx->pool_main.capacity() + ctx->pool_eri.capacity();
+    free_b += ctx->lane[0].pool[POOL_MAIN].capacity() + ctx->lane[0].pool[POOL_ERI].capacity();
     const int64_t chunk = stage_chunk_fragments(free_b, fragment_bytes(plan), nfrag);
     const Slot sl0 = make_slot(ctx, 0, nullptr);
     std::vector<double> hx;
@@ -224,20 +224,20 @@ int mqc_hip_coulomb_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_mol
         // form K alongside J in the same pass over the tensor either way
         bv.nocc = std::max(1, topo.nelec / 2); bv.exx = direct ? 0.0 : 1.0;
         gather_xyz(mols + start, nf, topo.natoms, hx);
-        HIP_CHECK_RET(hipMemcpyAsync(bv.xyz, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_CHECK_RET(hipMemsetAsync(bv.istate, 0, sizeof(int) * (size_t)nf * 4, ctx->stream));
-        HIP_CHECK_RET(hipMemsetAsync(bv.eri_count, 0, sizeof(unsigned long long), ctx->stream));
-        HIP_CHECK_RET(hipMemcpyAsync(bv.D, D + (size_t)start * nn, sizeof(double) * nn * nf, hipMemcpyHostToDevice, ctx->stream));
+        HIP_CHECK_RET(hipMemcpyAsync(bv.xyz, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, ctx->lane[0].stream));
+        HIP_CHECK_RET(hipMemsetAsync(bv.istate, 0, sizeof(int) * (size_t)nf * 4, ctx->lane[0].stream));
+        HIP_CHECK_RET(hipMemsetAsync(bv.eri_count, 0, sizeof(unsigned long long), ctx->lane[0].stream));
+        HIP_CHECK_RET(hipMemcpyAsync(bv.D, D + (size_t)start * nn, sizeof(double) * nn * nf, hipMemcpyHostToDevice, ctx->lane[0].stream));
         if (direct) {
-            launch_direct_setup(bv, topo, ctx->stream);
-            launch_jk_direct(bv, topo, 1.0e-12, false, ctx->stream);
+            launch_direct_setup(bv, topo, ctx->lane[0].stream);
+            launch_jk_direct(bv, topo, 1.0e-12, false, ctx->lane[0].stream);
         } else {
             // a restricted list leaves most of the tensor untouched: those blocks must read as zero
-            if (cross) HIP_CHECK_RET(hipMemsetAsync(bv.eri, 0, sizeof(double) * (size_t)nf * bv.eri_stride, ctx->stream));
-            launch_eri(bv, topo, 0.0, ctx->stream, hx.data());
-            launch_jk_incore(bv, false, ctx->stream);
+            if (cross) HIP_CHECK_RET(hipMemsetAsync(bv.eri, 0, sizeof(double) * (size_t)nf * bv.eri_stride, ctx->lane[0].stream));
+            launch_eri(bv, topo, 0.0, ctx->lane[0].stream, hx.data());
+            launch_jk_incore(bv, false, ctx->lane[0].stream);
         }
-        if ((rc = sync_and_check(ctx->stream)) != MQC_HIP_OK) return rc;
+        if ((rc = sync_and_check(ctx->lane[0].stream)) != MQC_HIP_OK) return rc;
         HIP_CHECK_RET(hipMemcpy(J + (size_t)start * nn, bv.J, sizeof(double) * nn * nf, hipMemcpyDeviceToHost));
     }
     return MQC_HIP_OK;
@@ -316,19 +316,19 @@ int mqc_hip_esp_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecul
         gather_xyz(mols + start, nf, na, hx);
         hn.resize(nf);
         for (int f = 0; f < nf; ++f) hn[f] = n_points ? n_points[start + f] : max_points;
-        HIP_CHECK_RET(hipMemcpyAsync(d_xyz, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_CHECK_RET(hipMemcpyAsync(d_np, hn.data(), sizeof(int) * hn.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_CHECK_RET(hipMemcpyAsync(d_D, D + (size_t)start * nn, sizeof(double) * nn * nf, hipMemcpyHostToDevice, ctx->stream));
+        HIP_CHECK_RET(hipMemcpyAsync(d_xyz, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, ctx->lane[0].stream));
+        HIP_CHECK_RET(hipMemcpyAsync(d_np, hn.data(), sizeof(int) * hn.size(), hipMemcpyHostToDevice, ctx->lane[0].stream));
+        HIP_CHECK_RET(hipMemcpyAsync(d_D, D + (size_t)start * nn, sizeof(double) * nn * nf, hipMemcpyHostToDevice, ctx->lane[0].stream));
         // a fragment's points beyond its count are not touched on the host: each fragment's live part goes up on its own
         const bool full = std::all_of(hn.begin(), hn.end(), [&](int v) { return v == max_points; });
-        if (full) HIP_CHECK_RET(hipMemcpyAsync(d_pts, points + (size_t)start * 3 * mp, sizeof(double) * 3 * mp * nf, hipMemcpyHostToDevice, ctx->stream));
+        if (full) HIP_CHECK_RET(hipMemcpyAsync(d_pts, points + (size_t)start * 3 * mp, sizeof(double) * 3 * mp * nf, hipMemcpyHostToDevice, ctx->lane[0].stream));
         for (int f = 0; f < nf && !full; ++f)
             if (hn[f] > 0)
                 HIP_CHECK_RET(hipMemcpyAsync(d_pts + (size_t)f * 3 * mp, points + (size_t)(start + f) * 3 * mp, sizeof(double) * 3 * hn[f],
-                                             hipMemcpyHostToDevice, ctx->stream));
-        if (!launch_esp(td, topo, ctx->d_boys, ctx->d_c2s, nf, d_xyz, d_D, d_rec, d_pts, d_np, max_points, include_nuclei ? 1 : 0, d_out, ctx->stream, err))
+                                             hipMemcpyHostToDevice, ctx->lane[0].stream));
+        if (!launch_esp(td, topo, ctx->d_boys, ctx->d_c2s, nf, d_xyz, d_D, d_rec, d_pts, d_np, max_points, include_nuclei ? 1 : 0, d_out, ctx->lane[0].stream, err))
             return fail(MQC_HIP_ERR_DEVICE, err);
-        if ((rc = sync_and_check(ctx->stream)) != MQC_HIP_OK) return rc;
+        if ((rc = sync_and_check(ctx->lane[0].stream)) != MQC_HIP_OK) return rc;
         hout.resize((size_t)nf * mp);
         HIP_CHECK_RET(hipMemcpy(hout.data(), d_out, sizeof(double) * hout.size(), hipMemcpyDeviceToHost));
         for (int f = 0; f < nf; ++f) std::memcpy(esp + (size_t)(start + f) * mp, &hout[(size_t)f * mp], sizeof(double) * hn[f]);
@@ -364,7 +364,7 @@ int mqc_hip_xc_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule
     if (plan.uhf && !unrestricted) return fail(MQC_HIP_ERR_VALIDATION, "xc batch: an open-shell fragment takes spin densities (unrestricted != 0)");
     Batch b{topo, nullptr, opts, nullptr};
     if ((rc = upload_topology(ctx, topo, b.td)) != MQC_HIP_OK) return rc;
-    if ((rc = upload_grid(ctx, b, ctx->pool_grid, ctx->stream)) != MQC_HIP_OK) return rc;
+    if ((rc = upload_grid(ctx, b, ctx->lane[0].grid, ctx->lane[0].stream)) != MQC_HIP_OK) return rc;
     plan.npts = b.grid.npts;
     plan_layout(plan, ntot, (int)topo.shells.size(), topo.lmax, xc_radial_cache_on());
 
@@ -373,10 +373,10 @@ int mqc_hip_xc_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule
     constexpr size_t GUARD = 4096;         // bytes compared on either side of the accumulator
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
-    free_b += ctx->pool_main.capacity() + ctx->pool_eri.capacity() + ctx->pool_gridw.capacity();
+    free_b += ctx->lane[0].pool[POOL_MAIN].capacity() + ctx->lane[0].pool[POOL_ERI].capacity() + ctx->lane[0].pool[POOL_GRIDW].capacity();
     const int64_t chunk = stage_chunk_fragments(free_b, fragment_bytes(plan), nfrag);
     const Slot sl0 = make_slot(ctx, 0, nullptr);
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx->lane[0].stream;
     std::vector<double> hx, acc, scal;
     std::vector<unsigned char> before(2 * GUARD), after(2 * GUARD);
     for (int64_t start = 0; start < nfrag; start += chunk) {
@@ -385,7 +385,7 @@ int mqc_hip_xc_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule
             // room behind the last array of the quadrature's pool, so that the guard band exists where nothing follows V_xc
             BatchView probe{};
             const ChunkBytes need = carve_chunk(plan, nf, nullptr, probe);
-            if (!sl0.pool[POOL_GRIDW]->ensure(need.pool[POOL_GRIDW] + GUARD + 256)) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (grid weights)");
+            if (!sl0.lane->pool[POOL_GRIDW].ensure(need.pool[POOL_GRIDW] + GUARD + 256)) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (grid weights)");
         }
         BatchView bv{};
         bv.nalpha = plan.nalpha; bv.nbeta = plan.nbeta; bv.nocc = plan.nocc;
@@ -467,11 +467,11 @@ int mqc_hip_df_jk_batch(mqc_hip_context* ctx, int64_t nfrag, int32_t n_ao, int32
     constexpr size_t GUARD = 1024;         // bytes compared in front of J and behind K (S .. C in front, W behind: never less)
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
-    free_b += ctx->pool_main.capacity() + ctx->pool_df.capacity();
+    free_b += ctx->lane[0].pool[POOL_MAIN].capacity() + ctx->lane[0].pool[POOL_DF].capacity();
     const int64_t chunk = stage_chunk_fragments(free_b, fragment_bytes(plan), nfrag);
     const Slot sl0 = make_slot(ctx, 0, nullptr);
     const TopologyDev td{};
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx->lane[0].stream;
     int rc;
     for (int64_t start = 0; start < nfrag; start += chunk) {
         const int nf = (int)std::min<int64_t>(chunk, nfrag - start);
@@ -585,7 +585,7 @@ int mqc_hip_jk_incore_batch(mqc_hip_context* ctx, int64_t nfrag, int32_t n_ao, i
     const size_t nn = (size_t)n * n;
     constexpr size_t GUARD = 1024;         // bytes compared in front of J and behind K (S .. C in front, W behind: never less)
     const Slot sl0 = make_slot(ctx, 0, nullptr);
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx->lane[0].stream;
     int rc;
     // one chunk: the dispatch depends on the number of fragments of the launch.  A batch beyond the memory is refused.
     BatchView bv{};
@@ -596,7 +596,7 @@ int mqc_hip_jk_incore_batch(mqc_hip_context* ctx, int64_t nfrag, int32_t n_ao, i
         // the three fields of the topology jk_tri_kernel reads, and the bounds behind them
         auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
         const size_t ib = up(sizeof(int) * (size_t)n_shells), qb = sizeof(double) * (size_t)nf * n_shells * n_shells;
-        char* base = (char*)ctx->pool_topo.ensure(2 * ib + up(qb));
+        char* base = (char*)ctx->lane[0].topo.ensure(2 * ib + up(qb));
         if (!base) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (screening tables)");
         td.sh_l = (int*)base; td.sh_aoff = (int*)(base + ib);
         td.nshell = n_shells; td.nao = n; td.npair = plan.npair; td.natoms = 1;
@@ -676,14 +676,14 @@ int mqc_hip_df_fit_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_mole
     plan_layout(plan, ntot, (int)topo.shells.size(), topo.lmax, false);
     TopologyDev td{}, tdx{};
     if ((rc = upload_topology(ctx, topo, td)) != MQC_HIP_OK) return rc;
-    if ((rc = upload_topology(ctx, xtopo, tdx, &ctx->pool_aux)) != MQC_HIP_OK) return rc;
+    if ((rc = upload_topology(ctx, xtopo, tdx, &ctx->lane[0].aux)) != MQC_HIP_OK) return rc;
     const size_t na = (size_t)xtopo.nao, a3 = na * (size_t)topo.npair, mm = na * na;
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
-    free_b += ctx->pool_main.capacity() + ctx->pool_df.capacity();
+    free_b += ctx->lane[0].pool[POOL_MAIN].capacity() + ctx->lane[0].pool[POOL_DF].capacity();
     const int64_t chunk = stage_chunk_fragments(free_b, fragment_bytes(plan), nfrag);
     const Slot sl0 = make_slot(ctx, 0, nullptr);
-    hipStream_t s = ctx->stream;
+    hipStream_t s = ctx->lane[0].stream;
     std::vector<double> hx, scal;
     for (int64_t start = 0; start < nfrag; start += chunk) {
         const int nf = (int)std::min<int64_t>(chunk, nfrag - start);
@@ -720,11 +720,11 @@ int mqc_hip_syev(mqc_hip_context* ctx, int32_t n, const double* A, double* w, do
     if (n > 256) return fail(MQC_HIP_ERR_UNSUPPORTED, "matrix too large for the Jacobi solver (n <= 256)");
     HIP_CHECK_RET(hipSetDevice(ctx->device));
     const size_t nn = (size_t)n * n;
-    double* d = (double*)ctx->pool_main.ensure(sizeof(double) * (2 * nn + n) + 1024);
+    double* d = (double*)ctx->lane[0].pool[POOL_MAIN].ensure(sizeof(double) * (2 * nn + n) + 1024);
     if (!d) return fail(MQC_HIP_ERR_DEVICE, "out of device memory");
     HIP_CHECK_RET(hipMemcpy(d, A, sizeof(double) * nn, hipMemcpyHostToDevice));
-    launch_syev(n, d, d + 2 * nn, d + nn, ctx->stream);
-    const int rc = sync_and_check(ctx->stream);
+    launch_syev(n, d, d + 2 * nn, d + nn, ctx->lane[0].stream);
+    const int rc = sync_and_check(ctx->lane[0].stream);
     if (rc != MQC_HIP_OK) return rc;
     HIP_CHECK_RET(hipMemcpy(w, d + 2 * nn, sizeof(double) * n, hipMemcpyDeviceToHost));
     HIP_CHECK_RET(hipMemcpy(V, d + nn, sizeof(double) * nn, hipMemcpyDeviceToHost));
@@ -736,11 +736,11 @@ int mqc_hip_diis_coefficients(mqc_hip_context* ctx, int32_t n_stored, const doub
     if (!ctx || !overlap || !coefficients || !ok) return fail(MQC_HIP_ERR_VALIDATION, "bad arguments");
     if (n_stored < 1 || n_stored > DIIS_MAX) return fail(MQC_HIP_ERR_VALIDATION, "n_stored must be within 1..8");
     HIP_CHECK_RET(hipSetDevice(ctx->device));
-    double* d = (double*)ctx->pool_misc.ensure(4096);
+    double* d = (double*)ctx->lane[0].pool[POOL_MISC].ensure(4096);
     if (!d) return fail(MQC_HIP_ERR_DEVICE, "out of device memory");
     HIP_CHECK_RET(hipMemcpy(d + 32, overlap, sizeof(double) * n_stored * n_stored, hipMemcpyHostToDevice));
-    launch_diis_coeff(n_stored, d + 32, d + 128, (int*)d, ctx->stream);
-    HIP_CHECK_RET(hipStreamSynchronize(ctx->stream));
+    launch_diis_coeff(n_stored, d + 32, d + 128, (int*)d, ctx->lane[0].stream);
+    HIP_CHECK_RET(hipStreamSynchronize(ctx->lane[0].stream));
     HIP_CHECK_RET(hipMemcpy(coefficients, d + 128, sizeof(double) * n_stored, hipMemcpyDeviceToHost));
     int okv = 0;
     HIP_CHECK_RET(hipMemcpy(&okv, d, sizeof(int), hipMemcpyDeviceToHost));

@@ -393,6 +393,23 @@ long long hostcheck_stage_chunk(unsigned long long free_bytes, unsigned long lon
     return stage_chunk_fragments((size_t)free_bytes, (size_t)per_fragment, nfrag, cap);
 }
 
+// the scheduling arithmetic of the batch driver (run_batch, schedule_groups)
+unsigned long long hostcheck_batch_budget(unsigned long long free_b, unsigned long long reservation, int lane, unsigned long long hbm_budget)
+{
+    return batch_budget_bytes((size_t)free_b, (size_t)reservation, lane, (size_t)hbm_budget);
+}
+
+long long hostcheck_batch_chunk(unsigned long long budget, unsigned long long per_frag, int ntot, int lane, int pipeline_chunks, int pipeline_min_fragments)
+{
+    return batch_chunk_fragments((size_t)budget, (size_t)per_frag, ntot, lane, pipeline_chunks, pipeline_min_fragments);
+}
+
+int hostcheck_defer_small_groups(const long long* nfrag, const int* nao, int ngroups, long long defer_min)
+{
+    std::vector<long> nf(nfrag, nfrag + ngroups);
+    return defer_small_groups(nf.data(), nao, ngroups, (long)defer_min) ? 1 : 0;
+}
+
 void hostcheck_boys(int L, double T, double* F)
 {
     ensure_tables();

@@ -222,6 +222,30 @@ def test_mixed_batch_on_the_chunked_route_and_the_256_thread_kernels(route, tmp_
     assert np.max(np.abs(np.array(got["e"]) - rec["e_total"])) < 1e-11
 
 
+def test_spin_densities_come_back_in_the_callers_order():
+    """The driver runs a batch in the order of compactness (nuclear repulsion, most compact first) and hands every answer
+    back to the caller's slot.  Three water monomers in STO-3G (n = 7), O-H lengths 2.0, 1.8 and 1.6 bohr, passed least
+    compact first -- the reverse of the order they run in -- and forced unrestricted: each fragment's spin densities,
+    total density and energy are those of the same fragment alone in a call.  Bounds: the energies to the
+    batch-versus-single bound of test_gpu_parity.py; the densities to 100 x D_TOL (a run ends once an iteration moves
+    the density by less than D_TOL rms, so two runs of one fragment that differ in rounding agree far inside that,
+    while neighbouring fragments' densities differ in the second decimal)."""
+    st = methods.ScfSettings(basis_set="sto-3g", unrestricted=True, **TIGHT)
+    half = np.deg2rad(104.5) / 2.0
+    frags = [fragment_bohr([8, 1, 1], [[0.0, 0.0, 0.0], [0.0, r * np.sin(half), r * np.cos(half)], [0.0, -r * np.sin(half), r * np.cos(half)]])
+             for r in (2.0, 1.8, 1.6)]
+    rec, dens, spin, status = solve(st, frags, spin=True)
+    assert status == 0 and not np.any(rec["has_error"])
+    assert min(np.max(np.abs(dens[a] - dens[b])) for a, b in ((0, 1), (1, 2), (0, 2))) > 1e-3       # a swap would show
+    for k, f in enumerate(frags):
+        one, dens1, spin1, status = solve(st, [f], spin=True)
+        assert status == 0 and not one["has_error"][0]
+        assert abs(rec["e_total"][k] - one["e_total"][0]) < 1e-11, k
+        assert np.max(np.abs(spin[k] - spin1[0])) < 100 * rc.D_TOL, k
+        assert np.max(np.abs(dens[k] - dens1[0])) < 100 * rc.D_TOL, k
+        assert np.max(np.abs(spin[k][0] + spin[k][1] - dens[k])) < 1e-13, k
+
+
 # ---- validation ------------------------------------------------------------------------------------------------------------
 def test_a_non_finite_density_fails_its_own_fragment_only():
     st = methods.ScfSettings(basis_set="6-31g", **TIGHT)

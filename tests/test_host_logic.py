@@ -406,6 +406,73 @@ def test_stage_chunk_size_is_the_budget_formula(hostcheck, free, per, nfrag, cap
     assert expected is None or got == expected
 
 
+@pytest.mark.parametrize("free,reservation,lane,hbm,expected", [
+    (1000, 100, -1, 0, 800), (1000, 500, -1, 0, 500), (1000, 500, 1, 0, 250), (1000, 2000, -1, 0, 125), (1000, 100, -1, 300, 300),
+    (int(288e9), 4 * 8192 * 64 * 256 * 32, 0, 0, None), (int(288e9), 4 * 8192 * 64 * 256 * 32, -1, int(64e9), None)])
+def test_batch_budget_is_the_share_under_the_scratch_reservation(hostcheck, free, reservation, lane, hbm, expected):
+    """run_batch's budget (batch_budget_bytes): 80 % of the free bytes, 40 % on a lane; never what the scratch
+    reservation may need (free / 8 where the reservation exceeds everything; a lane: half); a non-zero HBM budget caps it."""
+    hostcheck.hostcheck_batch_budget.restype = ctypes.c_ulonglong
+    got = hostcheck.hostcheck_batch_budget(ctypes.c_ulonglong(free), ctypes.c_ulonglong(reservation), lane, ctypes.c_ulonglong(hbm))
+    room = free - reservation if free > reservation else free // 8
+    want = min(int((0.80 if lane < 0 else 0.40) * free), room if lane < 0 else room // 2)      # IEEE doubles on both sides
+    if hbm:
+        want = min(want, hbm)
+    assert got == want
+    assert expected is None or got == expected
+
+
+@pytest.mark.parametrize("budget,per,ntot,lane,chunks,min_frag,expected", [
+    (1000, 10, 50, -1, 1, 256, 50), (1000, 10, 250, -1, 1, 256, 50), (1000, 10, 250, 0, 1, 256, 100),
+    (10 ** 6, 10, 1000, -1, 4, 256, 250), (10 ** 6, 10, 1001, -1, 4, 256, 251), (10 ** 6, 10, 255, -1, 4, 256, 255),
+    (5, 10, 3, -1, 1, 256, 0), (15, 10, 3, -1, 1, 256, 0), (10 ** 7, 10, 100000, 1, 1, 256, 60000)])
+def test_batch_chunk_size_is_the_budget_formula(hostcheck, budget, per, ntot, lane, chunks, min_frag, expected):
+    """run_batch's chunk size (batch_chunk_fragments).  A batch that owns both lanes and needs more than one chunk keeps
+    two resident, half the budget each; a pipelined one is cut into `chunks`; 0 is the driver's "not enough device memory
+    for one fragment"; 60000 is the J/K kernel's grid limit.  (15, 10, 3): one fragment would fit, half the budget holds
+    none -- pinned as the driver behaves, not endorsed."""
+    hostcheck.hostcheck_batch_chunk.restype = ctypes.c_longlong
+    got = hostcheck.hostcheck_batch_chunk(ctypes.c_ulonglong(budget), ctypes.c_ulonglong(per), ntot, lane, chunks, min_frag)
+    pipelined = lane < 0 and chunks > 1 and ntot >= min_frag
+    want = budget // per
+    if lane < 0 and (pipelined or want < ntot):
+        want = min(budget // 2 // per, (ntot + chunks - 1) // chunks if pipelined else ntot)
+    want = 0 if want < 1 else min(want, ntot, 60000)
+    assert got == want == expected
+
+
+@pytest.mark.parametrize("groups,defer_min,expected", [
+    ([(2016, 48), (64, 24)], 1024, True), ([(1000, 48), (64, 24)], 1024, False), ([(2016, 48), (2016, 24)], 1024, True),
+    ([(2016, 48), (252, 48)], 1024, True), ([(2016, 48), (253, 48)], 1024, False), ([(2016, 48), (64, 24)], 0, False),
+    ([(2016, 48), (64, 24), (253, 48)], 1024, False), ([(2016, 48)], 1024, True)])
+def test_small_groups_are_deferred_behind_a_large_one(hostcheck, groups, defer_min, expected):
+    """schedule_groups' rule (defer_small_groups), groups sorted largest first: the largest has at least defer_min > 0
+    fragments and every other holds at most one eighth of its fragments x n_ao^4.  Every product here is below 2^53, so
+    the doubles compare exactly: 8 x 252 = 2016 defers, 253 does not; a group as numerous at half the n_ao is 1/16."""
+    nfrag = (ctypes.c_longlong * len(groups))(*[g[0] for g in groups])
+    nao = (ctypes.c_int * len(groups))(*[g[1] for g in groups])
+    got = hostcheck.hostcheck_defer_small_groups(nfrag, nao, len(groups), ctypes.c_longlong(defer_min))
+    weight = [float(f) * float(n) ** 4 for f, n in groups]
+    assert max(8.0 * w for w in weight) < 2.0 ** 53
+    want = defer_min > 0 and groups[0][0] >= defer_min and all(8.0 * w <= weight[0] for w in weight[1:])
+    assert bool(got) == want == expected
+
+
+def test_every_environment_switch_is_in_the_readme():
+    """Every MQC_HIP_* name the library's sources mention is named in README.md's switch list.  The names include/mqc_hip.h
+    declares (status codes, enumerators, the ABI version) are the C API's, not switches, and are left out."""
+    csrc = os.path.join(ROOT, "metalquicha_amd", "csrc")
+    names = set()
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith((".cpp", ".hip", ".hpp")):
+            names |= set(re.findall(r"MQC_HIP_[A-Z0-9_]+", open(os.path.join(csrc, fn)).read()))
+    api = set(re.findall(r"MQC_HIP_[A-Z0-9_]+", open(os.path.join(ROOT, "include", "mqc_hip.h")).read()))
+    switches = names - api
+    assert len(switches) > 40, sorted(switches)
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    assert sorted(n for n in switches if not re.search(r"\b%s\b" % n, readme)) == []
+
+
 # ---- MBE assembly ----------------------------------------------------------------------------
 def test_mbe_term_list_and_coefficients():
     system = mbe.water_cluster(2)
