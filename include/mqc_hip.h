@@ -387,6 +387,56 @@ int mqc_hip_rimp2_batch(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip
                         int32_t frozen_core,
                         double *e_os /* [n] */, double *e_ss /* [n] */, int32_t *mp2_done /* [n] */);
 
+/* ---- C-PCM implicit solvation -------------------------------------------------------- */
+/* The SCF in a conductor-like polarisable continuum (the reference's cuestPCMPotentialCompute term: "C-PCM charges +
+ * V_pcm", F = H + J - K + V_xc + V_pcm, mqc_cuest_integrals.f90:974-1366).  The discretisation is this engine's own
+ * (DESIGN.md section 9), no parity with the reference's closed library is claimed:
+ *   spheres    one per real (non-ghost) atom, radius = radius_scale x Bondi radius (H 1.20, He 1.40, Li 1.82, C 1.70,
+ *              N 1.55, O 1.52, F 1.47, Ne 1.54, Na 2.27, Mg 1.73, Si 2.10, P 1.80, S 1.80, Cl 1.75, Ar 1.88 Angstrom), or
+ *              radii_by_z[Z] where that is non-zero (Bohr, NOT scaled)
+ *   tesserae   the Lebedev rule of angular_points points on every sphere, s = R_I + rho_I u_k, a = 4 pi rho_I^2 w_k
+ *              (sum w = 1), kept iff |s - R_J| >= rho_J for every other real atom J; ordered by atom, then by the rule
+ *   cavity     S_ii = zeta_i sqrt(2/pi), S_ij = erf(zeta_ij r_ij)/r_ij, zeta_i = 4.90/sqrt(a_i),
+ *              zeta_ij = zeta_i zeta_j / sqrt(zeta_i^2 + zeta_j^2)
+ *   response   v_i = sum_A Z_A/|s_i - R_A| - sum D_mn (m| 1/|r - s_i| |n),  q = -f S^-1 v,  f = (epsilon - 1)/epsilon,
+ *              E_pcm = q.v / 2,  (V_pcm)_mn = -sum_i q_i (m| 1/|r - s_i| |n)   (the same for both spins)
+ *   energy     1/2 tr D (H + F0) + E_xc + E_pcm + E_nuc, F0 the Fock matrix without V_xc and V_pcm
+ * The surface cut is sharp: energies only. */
+#define MQC_HIP_PCM_RADII_LEN 119
+typedef struct {
+    double epsilon;                  /* dielectric constant, >= 1 and finite; 1 is the vacuum */
+    int32_t angular_points;          /* a Lebedev rule of the engine up to 590 points; default 110 */
+    double radius_scale;             /* default 1.2 */
+    const double *radii_by_z;        /* NULL, or [MQC_HIP_PCM_RADII_LEN] indexed by atomic number: Bohr, unscaled, 0 = built-in */
+} mqc_hip_pcm_options_t;
+void mqc_hip_default_pcm_options(mqc_hip_pcm_options_t *pcm);   /* epsilon 78.39 (water), 110 points, scale 1.2, no table */
+
+/* mqc_hip_scf_run_batch in the continuum: grouping by topology, chunking under MQC_HIP_HBM_BUDGET_GB, concurrent
+ * groups, the blocked SCF loop and per-fragment failures in results[i] as there; every two-electron path, restricted and
+ * unrestricted, Hartree-Fock and every functional of the plain entry, ghost atoms (basis functions, no sphere, no charge).
+ * results[i].e_total and e_electronic contain E_pcm (the convergence test sees it, as it sees E_xc); e_xc stays the XC
+ * energy.  e_pcm[i] = E_pcm and n_tesserae[i] = T of fragment i; e_pcm[i] = 0 for a fragment that failed.
+ * MQC_HIP_ERR_UNSUPPORTED: opts->want_gradient (the cut surface is not differentiable), a fragment that carries point
+ * charges or h_extra.  MQC_HIP_ERR_VALIDATION: epsilon < 1 or not finite, an angular_points that is no rule of the engine
+ * up to 590, an element without a radius, a NULL pcm / e_pcm / n_tesserae; per fragment: more than 4096 tesserae, a cavity
+ * matrix that could not be factorised.  (Added without an ABI bump: no struct changed.) */
+int mqc_hip_scf_pcm_batch(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip_molecule_t *mols,
+                          const mqc_hip_basis_t *orbitals, const mqc_hip_basis_t *auxes /* NULL unless DF */,
+                          const mqc_hip_scf_options_t *opts, const mqc_hip_pcm_options_t *pcm,
+                          mqc_hip_scf_result_t *results, double *e_pcm /* [n] */, int32_t *n_tesserae /* [n] */);
+
+/* The PCM stage of ONE fragment for a GIVEN total density D [n_ao*n_ao] (symmetric): the setup and one iteration's
+ * kernels of the SCF entry, with everything in between copied out.  n_tesserae receives T; arrays the caller passes as
+ * NULL are skipped; the others must hold at least
+ *     tesserae [3*T], areas [T], v [T], q [T]      -- tessera_capacity >= T
+ *     A [T*npair], packed pairs (mu >= nu, index mu (mu + 1) / 2 + nu) fastest -- a_capacity (doubles) >= T*npair
+ *     e_pcm [1], V_pcm [n_ao*n_ao]
+ * MQC_HIP_ERR_VALIDATION when a capacity is too small (n_tesserae is still written), plus the entry's own refusals above. */
+int mqc_hip_pcm_stage(mqc_hip_context *ctx, const mqc_hip_molecule_t *mol, const mqc_hip_basis_t *orbital,
+                      const mqc_hip_pcm_options_t *pcm, const double *D, int32_t tessera_capacity, int64_t a_capacity,
+                      int32_t *n_tesserae, double *tesserae, double *areas, double *A, double *v, double *q,
+                      double *e_pcm, double *V_pcm);
+
 int mqc_hip_syev(mqc_hip_context *ctx, int32_t n, const double *A, double *w, double *V);
 /* DIIS coefficients from an age-ordered overlap matrix, the device routine's algorithm
  * (diis_coefficients/solve_diis, src/methods/mqc_diis.f90:164-273) */

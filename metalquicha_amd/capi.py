@@ -64,6 +64,14 @@ class ScfResult(C.Structure):
                 ("e_embedding", C.c_double), ("embedding_matrix", c_double_p), ("mulliken_charges", c_double_p)]
 
 
+class PcmOptions(C.Structure):
+    _fields_ = [("epsilon", C.c_double), ("angular_points", C.c_int32), ("radius_scale", C.c_double),
+                ("radii_by_z", c_double_p)]
+
+
+PCM_RADII_LEN = 119          # MQC_HIP_PCM_RADII_LEN: a caller's radii_by_z is indexed by atomic number
+
+
 class Stats(C.Structure):
     _fields_ = [("t_setup", C.c_double), ("t_int1e", C.c_double), ("t_eri", C.c_double),
                 ("t_fock", C.c_double), ("t_scf_step", C.c_double), ("t_total", C.c_double),
@@ -84,6 +92,7 @@ DECLARED_SYMBOLS = [
     "mqc_hip_jk_direct", "mqc_hip_esp_batch", "mqc_hip_xc_batch", "mqc_hip_scf_gradient_embedded_batch",
     "mqc_hip_scf_run_batch_restart", "mqc_hip_rimp2_batch", "mqc_hip_df_jk_batch", "mqc_hip_df_fit_batch",
     "mqc_hip_jk_tensor_layout", "mqc_hip_jk_incore_batch",
+    "mqc_hip_default_pcm_options", "mqc_hip_scf_pcm_batch", "mqc_hip_pcm_stage",
 ]
 
 _lib = None
@@ -120,6 +129,13 @@ def load_library():
                                                   C.POINTER(ScfOptions), C.POINTER(ScfResult), C.POINTER(c_double_p), C.POINTER(c_double_p)]
     lib.mqc_hip_rimp2_batch.argtypes = [C.c_void_p, C.c_int64, C.POINTER(Molecule), C.POINTER(Basis), C.POINTER(Basis),
                                         C.POINTER(ScfOptions), C.POINTER(ScfResult), C.c_int32, c_double_p, c_double_p, c_int32_p]
+    lib.mqc_hip_default_pcm_options.argtypes = [C.POINTER(PcmOptions)]
+    lib.mqc_hip_default_pcm_options.restype = None
+    lib.mqc_hip_scf_pcm_batch.argtypes = [C.c_void_p, C.c_int64, C.POINTER(Molecule), C.POINTER(Basis), C.POINTER(Basis),
+                                          C.POINTER(ScfOptions), C.POINTER(PcmOptions), C.POINTER(ScfResult), c_double_p, c_int32_p]
+    lib.mqc_hip_pcm_stage.argtypes = [C.c_void_p, C.POINTER(Molecule), C.POINTER(Basis), C.POINTER(PcmOptions), c_double_p, C.c_int32,
+                                      C.c_int64, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                      c_double_p]
     lib.mqc_hip_int1e.argtypes = [C.c_void_p, C.POINTER(Molecule), C.POINTER(Basis), c_double_p, c_double_p, c_double_p]
     lib.mqc_hip_eri_packed.argtypes = [C.c_void_p, C.POINTER(Molecule), C.POINTER(Basis), C.c_double, c_double_p]
     lib.mqc_hip_eri_packed_attenuated.argtypes = [C.c_void_p, C.POINTER(Molecule), C.POINTER(Basis), C.c_double, C.c_double, c_double_p]

@@ -2,6 +2,7 @@
 // Declarations only; everything here is defined in engine.cpp.
 #pragma once
 #include "engine.hpp"
+#include "pcm_cavity.hpp"
 #include <condition_variable>
 #include <mutex>
 
@@ -20,7 +21,8 @@ struct Slot {
 };
 inline Slot make_slot(mqc_hip_context* ctx, int id, int* h_counter) { return {id, &ctx->lane[id], h_counter}; }
 // carve one chunk's arrays out of the slot's pools (carve_chunk) and upload the block table of a triangular tensor
-int carve_slot(mqc_hip_context* ctx, const Slot& sl, const BatchPlan& plan, const TopologyDev& td, int nfrag, BatchView& bv);
+int carve_slot(mqc_hip_context* ctx, const Slot& sl, const BatchPlan& plan, const TopologyDev& td, int nfrag, BatchView& bv,
+               PcmView* pcm = nullptr);
 int upload_topology(mqc_hip_context* ctx, const Topology& topo, TopologyDev& td, DevicePool* pool = nullptr, hipStream_t stream = nullptr);
 
 bool incore_supported(int n);
@@ -56,6 +58,8 @@ struct FragmentIO {
     double* spin_out;                  // mqc_hip_scf_run_batch_restart: where an unrestricted run's spin densities go, or null
     double *mp2_os, *mp2_ss;           // mqc_hip_rimp2_batch: where the opposite-spin and same-spin correlation energies
     int32_t* mp2_done;                 // and the done flag go
+    const pcm::Cavity* cavity;         // mqc_hip_scf_pcm_batch: the fragment's tesserae, and where E_pcm goes
+    double* e_pcm;
 };
 
 // What the stages of one batch call share besides the plan: the fragments, ordered by compactness, the device topology
@@ -69,12 +73,19 @@ struct Batch {
     bool embedded_entry = false;                     // the call came through mqc_hip_scf_gradient_embedded_batch
     bool any_d0 = false;                             // some fragment brought a starting density
     int mp2_frozen = -1;                             // mqc_hip_rimp2_batch only: the frozen orbitals of this topology (>= 0)
+    double pcm_f = -1.0;                             // mqc_hip_scf_pcm_batch only: (epsilon - 1) / epsilon (>= 0)
     TopologyDev td{}, tdx{};
     GridDev grid;
     Stats stats;
     GroupGate* gate = nullptr;                       // opened when the first chunk's integral stage has been joined (scf_loop)
     int chain_side = 2;                              // side stream of the one-electron chain (prepare)
 };
+
+// C-PCM, host side (host_setup.cpp, the one place that instantiates pcm_cavity.hpp's builders).  The refusals of the
+// settings themselves (MQC_HIP_ERR_VALIDATION: epsilon, the rule) and of a molecule in the continuum (UNSUPPORTED: point
+// charges, h_extra; VALIDATION: an element without a radius, too many tesserae), then its cavity
+int pcm_check_options(const mqc_hip_pcm_options_t* pcm, std::string& msg);
+int pcm_build_cavity(const mqc_hip_molecule_t& mol, const mqc_hip_pcm_options_t& pcm, pcm::Cavity& cav, std::string& msg);
 
 // radial cache of the quadrature: MQC_HIP_XC_RADIAL_CACHE=0 turns it off
 bool xc_radial_cache_on();

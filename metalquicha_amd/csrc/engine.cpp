@@ -162,16 +162,16 @@ int upload_topology(mqc_hip_context* ctx, const Topology& topo, TopologyDev& td,
     return MQC_HIP_OK;
 }
 
-int carve_slot(mqc_hip_context* ctx, const Slot& sl, const BatchPlan& plan, const TopologyDev& td, int nfrag, BatchView& bv)
+int carve_slot(mqc_hip_context* ctx, const Slot& sl, const BatchPlan& plan, const TopologyDev& td, int nfrag, BatchView& bv, PcmView* pcm)
 {
-    static const char* const what[NPOOL] = {"SCF matrices", "ERI tensor", "counters", "grid weights", "fitted tensor"};
+    static const char* const what[NPOOL] = {"SCF matrices", "ERI tensor", "counters", "grid weights", "fitted tensor", "PCM arrays"};
     BatchView probe{};
     const ChunkBytes need = carve_chunk(plan, nfrag, nullptr, probe);
     char* bases[NPOOL] = {};
     for (int k = 0; k < NPOOL; ++k)
         if (need.pool[k] && !(bases[k] = (char*)sl.lane->pool[k].ensure(need.pool[k])))
             return fail(MQC_HIP_ERR_DEVICE, std::string("out of device memory (") + what[k] + ")");
-    carve_chunk(plan, nfrag, bases, bv);
+    carve_chunk(plan, nfrag, bases, bv, nullptr, pcm);
     bv.topo = td; bv.slot = sl.id; bv.boys = ctx->d_boys; bv.c2s = ctx->d_c2s; bv.unit = ctx->d_unit;
     if (bv.eri_tri) {
         static std::vector<int> sb_host[2];      // stays alive while the copy is in flight
@@ -281,7 +281,33 @@ struct Job {
     BatchView bv{};
     std::vector<double> hx, hpc;
     std::vector<int> restart;      // per fragment of the chunk: 1 = starts from its supplied density
+    PcmView pcm{};                 // C-PCM arrays of the chunk (stride 0: none), tesserae and counts as uploaded
+    std::vector<double> hpcm;
+    std::vector<int> hnt;
 };
+
+// MQC_HIP_PCM_TIMING=1: HIP-event times of the PCM setup and of its per-iteration kernel, one line per batch call.
+// Everything is per lane: two topology groups of one call run on a lane each, from two host threads.
+struct PcmTiming {
+    hipEvent_t ev[2][4] = {};      // setup begin / end, iteration begin / end
+    bool ready = false;
+    double setup_s[2] = {}, iter_s[2] = {}, iter_bytes[2] = {};
+    long launches[2] = {};
+};
+static PcmTiming g_pcm_timing;
+static bool pcm_timing_on()
+{
+    // a function-local static: two lanes' host threads may come here at once, the events are made once
+    static const bool on = [] {
+        const bool want = env_opt_in("MQC_HIP_PCM_TIMING");
+        if (want) {
+            for (auto& lane : g_pcm_timing.ev) for (hipEvent_t& e : lane) (void)hipEventCreate(&e);
+            g_pcm_timing.ready = true;
+        }
+        return want;
+    }();
+    return on;
+}
 
 bool xc_radial_cache_on()
 {
@@ -396,9 +422,22 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
     bv.exx = plan.rsh ? 1.0 : plan.xc.exx; bv.e_tol = opts.energy_tol; bv.d_tol = opts.density_tol;
     bv.max_iter = opts.max_iter; bv.diis_size = opts.use_diis ? opts.diis_size : 0;
     bv.xc = plan.xc; bv.grid = b.grid;
-    int rc = carve_slot(ctx, sl, plan, b.td, nf, bv);
+    int rc = carve_slot(ctx, sl, plan, b.td, nf, bv, &job.pcm);
     if (rc != MQC_HIP_OK) return rc;
     if (plan.two_e == TWO_E_DF) HIP_CHECK_RET(hipMemsetAsync(bv.scal, 0, sizeof(double) * (size_t)nf * 8, s));
+    if (plan.pcm_stride > 0) {
+        // the tesserae of every fragment at the chunk's stride (the padding is never read as a position) and their counts
+        const size_t ts = (size_t)plan.pcm_stride;
+        job.hpcm.assign((size_t)nf * ts * 4, 0.0);
+        job.hnt.resize(nf);
+        for (int f = 0; f < nf; ++f) {
+            const pcm::Cavity& cav = *frag[f].cavity;
+            job.hnt[f] = cav.count;
+            std::memcpy(&job.hpcm[(size_t)f * ts * 4], cav.xyza.data(), sizeof(double) * 4 * (size_t)cav.count);
+        }
+        HIP_CHECK_RET(hipMemcpyAsync(job.pcm.pts, job.hpcm.data(), sizeof(double) * job.hpcm.size(), hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(job.pcm.nt, job.hnt.data(), sizeof(int) * (size_t)nf, hipMemcpyHostToDevice, s));
+    }
     job.hx.resize((size_t)nf * topo.natoms * 3);
     for (int f = 0; f < nf; ++f) std::memcpy(&job.hx[(size_t)f * topo.natoms * 3], frag[f].mol->xyz, sizeof(double) * topo.natoms * 3);
     HIP_CHECK_RET(hipMemcpyAsync(bv.xyz, job.hx.data(), sizeof(double) * job.hx.size(), hipMemcpyHostToDevice, s));
@@ -471,6 +510,14 @@ static int prepare(mqc_hip_context* ctx, const BatchPlan& plan, Batch& b, const 
     }
     HIP_CHECK_RET(hipEventRecord(sl.lane->eri[1], s));
     if ((rc = stage_check("two-electron setup")) != MQC_HIP_OK) return rc;
+    if (plan.pcm_stride > 0) {
+        // C-PCM setup, once per geometry, behind the two-electron stage on the lane's stream
+        const bool timed = pcm_timing_on();
+        if (timed) HIP_CHECK_RET(hipEventRecord(g_pcm_timing.ev[sl.id & 1][0], s));
+        launch_pcm_setup(bv, job.pcm, topo, s);
+        if (timed) HIP_CHECK_RET(hipEventRecord(g_pcm_timing.ev[sl.id & 1][1], s));
+        if ((rc = stage_check("PCM setup")) != MQC_HIP_OK) return rc;
+    }
     b.stats.eri_quartets += topo.n_quartets * nf;
     HIP_CHECK_RET(hipStreamWaitEvent(s, sl.lane->chain[1], 0));      // join: X, C, D of the guess are ready
     if (b.guess && !all_restart) {
@@ -525,10 +572,16 @@ static int scf_loop(const BatchPlan& plan, Batch& b, const Slot& sl, Job& job)
     BatchView& bv = job.bv;
     Stats& st = b.stats;
     const bool df = plan.two_e == TWO_E_DF, ks = plan.xc.ncomp > 0;
+    const bool pcm_on = plan.pcm_stride > 0, pcm_timed = pcm_on && pcm_timing_on();
     int rc;
     const double t3 = now_s();
     HIP_CHECK_RET(hipStreamSynchronize(s));
     if ((rc = stage_check("integrals")) != MQC_HIP_OK) return rc;
+    if (pcm_timed) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, g_pcm_timing.ev[sl.id & 1][0], g_pcm_timing.ev[sl.id & 1][1]);
+        g_pcm_timing.setup_s[sl.id & 1] += ms * 1e-3;
+    }
     if (b.gate) b.gate->open();         // deferred small groups start now: from here on this batch uses one stream
     {
         float ms = 0.f;
@@ -562,6 +615,12 @@ static int scf_loop(const BatchPlan& plan, Batch& b, const Slot& sl, Job& job)
                 launch_xc(bv, true, s);
                 HIP_CHECK_RET(hipEventRecord(lane.xc[1], s));
             }
+            if (pcm_on) {
+                // V_pcm and E_pcm of this density into the accumulator and scal[5], after the quadrature (which zeroes both)
+                if (pcm_timed) HIP_CHECK_RET(hipEventRecord(g_pcm_timing.ev[sl.id & 1][2], s));
+                launch_pcm_iteration(bv, job.pcm, ks, s);
+                if (pcm_timed) HIP_CHECK_RET(hipEventRecord(g_pcm_timing.ev[sl.id & 1][3], s));
+            }
             HIP_CHECK_RET(hipEventRecord(lane.step[0], s));
             launch_scf_step(bv, s);
             HIP_CHECK_RET(hipEventRecord(lane.step[1], s));
@@ -569,6 +628,15 @@ static int scf_loop(const BatchPlan& plan, Batch& b, const Slot& sl, Job& job)
             HIP_CHECK_RET(hipMemcpyAsync(sl.h_counter, bv.counters, sizeof(int), hipMemcpyDeviceToHost, s));
             HIP_CHECK_RET(hipStreamSynchronize(s));
             float ms = 0.f;
+            if (pcm_timed) {
+                // bytes of the kernel's two passes over the rows of B the active fragments own
+                (void)hipEventElapsedTime(&ms, g_pcm_timing.ev[sl.id & 1][2], g_pcm_timing.ev[sl.id & 1][3]);
+                double rows = 0.0;
+                for (int v : job.hnt) rows += v;
+                g_pcm_timing.iter_s[sl.id & 1] += ms * 1e-3 * block_len;
+                g_pcm_timing.iter_bytes[sl.id & 1] += 2.0 * 8.0 * rows * np * ((double)remaining / nf) * block_len;
+                g_pcm_timing.launches[sl.id & 1] += block_len;
+            }
             (void)hipEventElapsedTime(&ms, lane.step[0], lane.step[1]);
             st.scf_step_seconds += ms * 1e-3 * block_len;
             (void)hipEventElapsedTime(&ms, lane.fock[0], lane.fock[1]);
@@ -692,7 +760,7 @@ static void embedding_and_mulliken(const Topology& topo, const double* D, const 
 
 // what a chunk's results are made of, read back once after its SCF loop
 struct ChunkOut {
-    std::vector<double> scal, eps, epsb, dip, grad, pcgrad, mp2;
+    std::vector<double> scal, eps, epsb, dip, grad, pcgrad, mp2, pcm;
     std::vector<double> D, U, S;      // total density, embedding operator, overlap: only where a caller reads them
     std::vector<double> Da, Db;       // spin densities of an unrestricted chunk, where a caller asked for them
     std::vector<int> ist;
@@ -720,6 +788,7 @@ static int write_result(const BatchPlan& plan, Batch& b, const Job& job, const C
     r->e_electronic = o.scal[8 * f + 4];
     r->e_total = r->e_electronic + r->e_nuclear;
     r->e_xc = plan.xc.ncomp > 0 ? o.scal[8 * f + 5] : 0.0;
+    if (plan.pcm_stride > 0) r->e_xc = plan.xc.ncomp > 0 ? o.pcm[8 * f + 1] : 0.0;      // scal[5] holds E_xc + E_pcm there
     r->iterations = o.ist[4 * f + 1];
     const bool conv = o.ist[4 * f + 3] != 0 && o.ist[4 * f] == ST_DONE;
     r->scf_status = conv ? MQC_HIP_SCF_CONVERGED : MQC_HIP_SCF_NOT_CONVERGED;
@@ -758,9 +827,12 @@ static int write_result(const BatchPlan& plan, Batch& b, const Job& job, const C
     r->has_error = 0; r->message[0] = '\0';
     if (plan.two_e == TWO_E_DF && o.scal[8 * f + 7] == 1.0)
         fill_error(r, "density fitting: the auxiliary metric (P|Q) could not be factorised or diagonalised");
+    else if (plan.pcm_stride > 0 && o.pcm[8 * f + 7] != 0.0)
+        fill_error(r, "PCM: the cavity matrix S of this fragment could not be factorised (a pivot failed)");
     else if (!std::isfinite(r->e_total)) fill_error(r, "SCF produced a non-finite energy");
     else if (!conv && !b.opts.allow_crap_scf)
         fill_error(r, "SCF did not converge in " + std::to_string(r->iterations) + " iterations");
+    if (plan.pcm_stride > 0 && io.e_pcm && !r->has_error) *io.e_pcm = o.pcm[8 * f];
     if (b.mp2_frozen >= 0 && conv && !r->has_error) {
         // the correlation energy belongs to converged orbitals only; everything else keeps the entry's zeros
         *io.mp2_os = o.mp2[2 * f];
@@ -837,6 +909,10 @@ static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& j
     HIP_CHECK_RET(hipMemcpyAsync(o.dip.data(), bv.dip, sizeof(double) * o.dip.size(), hipMemcpyDeviceToHost, s));
     HIP_CHECK_RET(hipMemcpyAsync(&formed, bv.eri_count, sizeof(formed), hipMemcpyDeviceToHost, s));
     HIP_CHECK_RET(hipMemcpyAsync(o.scal.data(), bv.scal, sizeof(double) * o.scal.size(), hipMemcpyDeviceToHost, s));
+    if (plan.pcm_stride > 0) {
+        o.pcm.resize((size_t)nf * 8);
+        HIP_CHECK_RET(hipMemcpyAsync(o.pcm.data(), job.pcm.scal, sizeof(double) * o.pcm.size(), hipMemcpyDeviceToHost, s));
+    }
     HIP_CHECK_RET(hipMemcpyAsync(o.eps.data(), bv.eps, sizeof(double) * o.eps.size(), hipMemcpyDeviceToHost, s));
     HIP_CHECK_RET(hipMemcpyAsync(o.ist.data(), bv.istate, sizeof(int) * o.ist.size(), hipMemcpyDeviceToHost, s));
     // matrices the callers asked for (total density, embedding operator, overlap): the whole chunk in one copy each
@@ -882,6 +958,8 @@ struct Work {
     bool embedded_entry = false;         // the call came through mqc_hip_scf_gradient_embedded_batch
     bool any_d0 = false;                 // mqc_hip_scf_run_batch_restart: some fragment of the group brought a starting density
     int mp2_frozen = -1;                 // mqc_hip_rimp2_batch only: frozen orbitals of the topology (>= 0)
+    double pcm_f = -1.0;                 // mqc_hip_scf_pcm_batch only: (epsilon - 1) / epsilon, and the fragments' cavities
+    std::vector<pcm::Cavity> cavities;   // (reserved up front: the fragment records point into it)
     std::shared_ptr<AtomicGuess> guess;
     // deferred small groups (schedule_groups): the largest group's batch opens the gate, the others wait at it
     GroupGate* opens = nullptr;
@@ -900,7 +978,7 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
     const double t_begin = now_s();
     const int ntot = (int)w.frags.size();
     Batch b{topo, aux, opts, w.guess.get()};
-    b.embedded_entry = w.embedded_entry; b.any_d0 = w.any_d0; b.mp2_frozen = w.mp2_frozen;
+    b.embedded_entry = w.embedded_entry; b.any_d0 = w.any_d0; b.mp2_frozen = w.mp2_frozen; b.pcm_f = w.pcm_f;
     b.gate = w.opens;
     if (w.waits && lane == 1) b.chain_side = 1;      // deferred on lane 1: its third side stream stays idle (schedule_groups)
     // whichever way this batch ends (refusal, error return, no chunk that reaches scf_loop), the waiting groups go on
@@ -921,6 +999,13 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
     }
     std::string msg;
     int rc = plan_batch(opts, topo, ntot, plan, msg);
+    if (rc == MQC_HIP_OK && w.pcm_f >= 0.0) {
+        // C-PCM: one stride for every chunk of the batch, the largest tessera count rounded up to 64
+        int largest = 0;
+        for (const FragmentIO& f : b.frags) largest = std::max(largest, f.cavity->count);
+        plan.pcm_stride = pcm::chunk_stride(largest);
+        plan.pcm_f = w.pcm_f;
+    }
     if (rc == MQC_HIP_OK && embedded && opts.want_gradient) {
         if (!b.embedded_entry) {
             msg = "analytic gradients of a fragment embedded in point charges or an extra one-electron operator are not returned by this entry "
@@ -1006,6 +1091,19 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
     b.stats.t_total += now_s() - t_begin;
     std::lock_guard<std::mutex> lock(ctx->stats_mutex);
     ctx->stats += b.stats;
+    if (plan.pcm_stride > 0 && pcm_timing_on()) {
+        // the lanes this batch ran on: both (chunks alternate) or its own
+        PcmTiming& t = g_pcm_timing;
+        double setup_s = 0, iter_s = 0, bytes = 0;
+        long launches = 0;
+        for (int l = 0; l < 2; ++l) {
+            if (lane >= 0 && l != (lane & 1)) continue;
+            setup_s += t.setup_s[l]; iter_s += t.iter_s[l]; bytes += t.iter_bytes[l]; launches += t.launches[l];
+            t.setup_s[l] = t.iter_s[l] = t.iter_bytes[l] = 0.0; t.launches[l] = 0;
+        }
+        std::fprintf(stderr, "mqc_hip: pcm timing: %d fragments in %d chunks, stride %d, setup %.3f ms, iterations %.3f ms in %ld launches, %.3f GB read, %.1f GB/s\n",
+                     ntot, njobs, plan.pcm_stride, setup_s * 1e3, iter_s * 1e3, launches, bytes * 1e-9, iter_s > 0 ? bytes * 1e-9 / iter_s : 0.0);
+    }
     return MQC_HIP_OK;
 }
 
@@ -1312,6 +1410,9 @@ struct BatchExtras {            // what the plain batch entry does not have
     bool frozen_core = false;
     double *e_os = nullptr, *e_ss = nullptr;
     int32_t* mp2_done = nullptr;
+    const mqc_hip_pcm_options_t* pcm = nullptr;     // mqc_hip_scf_pcm_batch: the settings (checked) and the [n] outputs
+    double* e_pcm = nullptr;
+    int32_t* n_tesserae = nullptr;
 };
 
 // frozen-core orbitals of a topology: per real atom 0 for Z <= 2, 1 for Z = 3-10, 5 for Z = 11-18, 9 for Z = 19-36
@@ -1420,8 +1521,28 @@ static int admit_group(const BatchCall& c, const BatchExtras& extras, const std:
     int worst = MQC_HIP_OK;
     bool all_d0 = extras.initial_density != nullptr;
     const size_t nn = (size_t)w.topo->nao * w.topo->nao, cnt = uhf ? 2 * nn : nn;
+    if (extras.pcm) {
+        w.pcm_f = (extras.pcm->epsilon - 1.0) / extras.pcm->epsilon;
+        w.cavities.reserve(idx.size());
+    }
     for (auto i : idx) {
         FragmentIO io{&c.mols[i], &c.results[i]};
+        if (extras.pcm) {
+            // the cavity of this geometry; a fragment the continuum refuses fails alone
+            pcm::Cavity cav;
+            std::string why;
+            const int prc = pcm_build_cavity(c.mols[i], *extras.pcm, cav, why);
+            extras.n_tesserae[i] = cav.count;
+            if (prc != MQC_HIP_OK) {
+                fill_error(io.result, why);
+                set_error(why);
+                worst = prc;
+                continue;
+            }
+            w.cavities.push_back(std::move(cav));
+            io.cavity = &w.cavities.back();
+            io.e_pcm = extras.e_pcm + i;
+        }
         if (extras.embedded_entry && extras.site_gradients) io.pcgrad = extras.site_gradients[i];
         if (extras.initial_density) io.d0 = extras.initial_density[i];
         if (extras.spin_densities_out) io.spin_out = extras.spin_densities_out[i];
@@ -1604,6 +1725,40 @@ int mqc_hip_rimp2_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molec
     extras.mp2 = true;
     extras.frozen_core = frozen_core != 0;
     extras.e_os = e_os; extras.e_ss = e_ss; extras.mp2_done = mp2_done;
+    return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, opts, results, extras);
+}
+
+void mqc_hip_default_pcm_options(mqc_hip_pcm_options_t* p)
+{
+    if (!p) return;
+    p->epsilon = 78.39;          // water
+    p->angular_points = 110;
+    p->radius_scale = 1.2;
+    p->radii_by_z = nullptr;
+}
+
+int mqc_hip_scf_pcm_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols,
+                          const mqc_hip_basis_t* orbitals, const mqc_hip_basis_t* auxes,
+                          const mqc_hip_scf_options_t* opts, const mqc_hip_pcm_options_t* pcm,
+                          mqc_hip_scf_result_t* results, double* e_pcm, int32_t* n_tesserae)
+{
+    if (!opts || !pcm) return fail(MQC_HIP_ERR_VALIDATION, "null argument");
+    if (nfrag > 0 && (!e_pcm || !n_tesserae)) return fail(MQC_HIP_ERR_VALIDATION, "PCM: e_pcm and n_tesserae must not be NULL");
+    for (int64_t i = 0; i < nfrag; ++i) { e_pcm[i] = 0.0; n_tesserae[i] = 0; }
+    // what the whole call refuses: no fragment runs an SCF
+    std::string why;
+    int code = pcm_check_options(pcm, why);
+    if (code == MQC_HIP_OK && opts->want_gradient) {
+        why = "analytic gradients in the PCM are not built: the cavity surface is cut sharply and is not differentiable (energies only)";
+        code = MQC_HIP_ERR_UNSUPPORTED;
+    }
+    if (code != MQC_HIP_OK) {
+        if (results)
+            for (int64_t i = 0; i < nfrag; ++i) { init_result(&results[i]); fill_error(&results[i], why); }
+        return fail(code, why);
+    }
+    BatchExtras extras;
+    extras.pcm = pcm; extras.e_pcm = e_pcm; extras.n_tesserae = n_tesserae;
     return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, opts, results, extras);
 }
 

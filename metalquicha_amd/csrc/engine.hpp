@@ -200,6 +200,22 @@ struct BatchView {      // plain pointers handed to kernels
     double *Jlr = nullptr, *Klr = nullptr, *Klrb = nullptr;
 };
 
+// C-PCM solvation (kern_pcm.hip): the device arrays of one chunk, next to its BatchView (which stays as it is, so that
+// no other kernel's argument changes).  Every per-fragment array has the chunk's stride = the batch's largest tessera
+// count rounded up to 64; fragment f uses its first nt[f] entries and the rest is padding: the cavity matrix continues
+// as the identity, A, v_nuc and b as zeros, so that the factorisation and the products run at one size for the chunk.
+struct PcmView {
+    int stride = 0;               // 0: no PCM
+    double f = 0.0;               // (epsilon - 1) / epsilon
+    int* nt = nullptr;            // [nfrag] tesserae of each fragment
+    double* pts = nullptr;        // [nfrag][stride][4] x, y, z, area
+    double *S = nullptr, *Linv = nullptr, *work = nullptr;   // [nfrag][stride^2]: cavity matrix (its factor L after setup), L^-1, scratch
+    double *A = nullptr, *B = nullptr;                       // [nfrag][stride][npair]: (mu| 1/|r - s_t| |nu) packed, B = L^-1 A
+    double *vnuc = nullptr, *b = nullptr, *c = nullptr, *v = nullptr;   // [nfrag][stride]: nuclear potential, L^-1 v_nuc, c = L^-1 v, v (stage entry)
+    double* dp = nullptr;         // [nfrag][npair] packed total density, off-diagonal pairs doubled
+    double* scal = nullptr;       // [nfrag][8]: E_pcm, E_xc of the iteration, -, -, -, -, -, factorisation flag (0 = ok)
+};
+
 // Where an integral goes in the pair matrix of one fragment: both mirror elements of the square, or the one stored
 // element of the triangular block layout (diagonal elements halved, see BatchView::eri_tri).
 struct PairStore {
@@ -275,10 +291,12 @@ struct BatchPlan {
     int npts = 0, rad_pt = 0;          // quadrature points per fragment, points per tile of the radial cache
     size_t rad_doubles = 0, pt4_doubles = 0;   // per fragment: radial cache and point buffer of the quadrature (0: none)
     double stol = 0.0, direct_tol = 0.0;       // Schwarz thresholds of the in-core build and of the direct digest
+    int pcm_stride = 0;                // C-PCM: stride of the per-fragment tessera arrays (0: no PCM); then the accumulator
+    double pcm_f = 0.0;                // bv.Vxc exists for Hartree-Fock too (V_pcm reaches the Fock matrix through it)
 };
 
 // The device pools one chunk is carved from (a lane of the context holds one of each)
-enum : int { POOL_MAIN = 0, POOL_ERI, POOL_MISC, POOL_GRIDW, POOL_DF, NPOOL };
+enum : int { POOL_MAIN = 0, POOL_ERI, POOL_MISC, POOL_GRIDW, POOL_DF, POOL_PCM, NPOOL };
 struct ChunkBytes {
     size_t pool[NPOOL] = {};
     size_t total() const { size_t t = 0; for (size_t b : pool) t += b; return t; }
@@ -342,7 +360,9 @@ void plan_layout(BatchPlan& p, int ntot, int nshell, int lmax, bool rad_cache);
 // from the five pools at bases[POOL_*] into bv's pointers (with its shape: nfrag, n, npair, uhf, npc, naux, tensor
 // layout).  Returns the bytes each pool needs; bases == nullptr only sizes (the pointers are then offsets).  record
 // (optional) receives every array carved.  The block table of a triangular tensor is left for the caller to upload.
-ChunkBytes carve_chunk(const BatchPlan& p, int nfrag, char* const* bases, BatchView& bv, std::vector<CarvedArray>* record = nullptr);
+// A plan with PCM carves (and counts) the PCM arrays too; pcm (optional) receives them.
+ChunkBytes carve_chunk(const BatchPlan& p, int nfrag, char* const* bases, BatchView& bv, std::vector<CarvedArray>* record = nullptr,
+                       PcmView* pcm = nullptr);
 // bytes per fragment that bound every chunk: carve_chunk(p, nf) <= nf x this (+ the direct path's own J/K accumulators)
 size_t fragment_bytes(const BatchPlan& p);
 // fragments per chunk of a batched stage entry: what fits 70 % of free_bytes, at most nfrag and cap, at least one
@@ -425,6 +445,14 @@ struct DfJkRoute {
 };
 DfJkRoute launch_df_jk(const BatchView& bv, bool only_active, hipStream_t s);
 void launch_xc(const BatchView& bv, bool only_active, hipStream_t s);
+// C-PCM (kern_pcm.hip).  Setup, once per geometry: the cavity matrix, its Cholesky factor and inverse (the density
+// fitting's kernels on a view of the PCM arrays), A, B = L^-1 A, v_nuc and b = L^-1 v_nuc.  Iteration: c = b - B d,
+// E_pcm = -f/2 c.c and f sum_P c_P B^P / 2 into both mirror elements of the accumulator bv.Vxc (added when add != 0, as
+// after the quadrature; stored otherwise), E_pcm added to scal[5], for the fragments that are not done.  Stage: v and
+// q = -f L^-T c of the last iteration into pv.v and pv.b.
+void launch_pcm_setup(const BatchView& bv, const PcmView& pv, const Topology& topo, hipStream_t s);
+void launch_pcm_iteration(const BatchView& bv, const PcmView& pv, bool add, hipStream_t s);
+void launch_pcm_charges(const BatchView& bv, const PcmView& pv, hipStream_t s);
 bool build_atom_template(int z, int level, int n_radial, int n_angular, std::vector<double>& xyz, std::vector<double>& w, std::string& err);
 bool parse_functional(const char* name, XcSpec& spec, std::string& err);
 double bragg_radius_bohr(int z);

@@ -2,7 +2,7 @@
 // topology (shell, pair and quartet-class lists), the Boys table and cart->sph tables, and the
 // device layout of a batch chunk (carve_chunk: the one place every per-fragment array is sized).
 // Nothing here computes integrals or any part of an SCF; that is all on the device.
-#include "engine.hpp"
+#include "driver.hpp"
 #include "md_integrals.hpp"
 #include <algorithm>
 #include <array>
@@ -399,7 +399,7 @@ void plan_layout(BatchPlan& p, int ntot, int nshell, int lmax, bool rad_cache)
     p.pt4_doubles = (p.rad_doubles && p.n <= 96 && lmax <= 3 && p.rad_pt == 32) ? tiles * p.rad_pt * 4 : 0;
 }
 
-ChunkBytes carve_chunk(const BatchPlan& p, int nfrag, char* const* bases, BatchView& bv, std::vector<CarvedArray>* record)
+ChunkBytes carve_chunk(const BatchPlan& p, int nfrag, char* const* bases, BatchView& bv, std::vector<CarvedArray>* record, PcmView* pcm)
 {
     const size_t nf = (size_t)nfrag, n = (size_t)p.n, nn = n * n, np = (size_t)p.npair;
     ChunkBytes used;
@@ -459,7 +459,7 @@ ChunkBytes carve_chunk(const BatchPlan& p, int nfrag, char* const* bases, BatchV
     // Kohn-Sham: grid weights, the V_xc accumulator of each spin, radial cache, point buffer
     const bool ks = p.xc.ncomp > 0;
     bv.grid.weights = ks ? doubles(POOL_GRIDW, nf * p.npts) : nullptr;
-    bv.Vxc = ks ? doubles(POOL_GRIDW, nf * nn * (p.uhf ? 2 : 1)) : nullptr;
+    bv.Vxc = (ks || p.pcm_stride > 0) ? doubles(POOL_GRIDW, nf * nn * (p.uhf ? 2 : 1)) : nullptr;
     bv.grid.rad = ks && p.rad_doubles ? doubles(POOL_GRIDW, nf * p.rad_doubles) : nullptr;
     bv.grid.pt4 = ks && p.pt4_doubles ? doubles(POOL_GRIDW, nf * p.pt4_doubles) : nullptr;
     if (ks) bv.grid.rad_pt = p.rad_pt;
@@ -472,7 +472,50 @@ ChunkBytes carve_chunk(const BatchPlan& p, int nfrag, char* const* bases, BatchV
     bv.df_metric = df ? doubles(POOL_DF, mm) : nullptr;
     bv.df_linv = df ? doubles(POOL_DF, mm) : nullptr;
     bv.df_work = df ? doubles(POOL_DF, mm) : nullptr;
+
+    // C-PCM: tesserae, cavity matrix with its inverse factor and scratch, A and B = L^-1 A, the vectors, the packed density
+    if (p.pcm_stride > 0) {
+        PcmView pv;
+        const size_t ts = (size_t)p.pcm_stride;
+        pv.stride = p.pcm_stride; pv.f = p.pcm_f;
+        pv.nt = (int*)take(POOL_PCM, sizeof(int) * nf);
+        pv.pts = doubles(POOL_PCM, nf * ts * 4);
+        for (double** m : {&pv.S, &pv.Linv, &pv.work}) *m = doubles(POOL_PCM, nf * ts * ts);
+        pv.A = doubles(POOL_PCM, nf * ts * np);
+        pv.B = doubles(POOL_PCM, nf * ts * np);
+        for (double** m : {&pv.vnuc, &pv.b, &pv.c, &pv.v}) *m = doubles(POOL_PCM, nf * ts);
+        pv.dp = doubles(POOL_PCM, nf * np);
+        pv.scal = doubles(POOL_PCM, nf * 8);
+        if (pcm) *pcm = pv;
+    }
     return used;
+}
+
+// ---- C-PCM: the settings' and a molecule's refusals, then the cavity (pcm_cavity.hpp)
+int pcm_check_options(const mqc_hip_pcm_options_t* o, std::string& msg)
+{
+    if (!o) { msg = "PCM: null options"; return MQC_HIP_ERR_VALIDATION; }
+    if (!std::isfinite(o->epsilon) || o->epsilon < 1.0) { msg = "PCM: the dielectric constant epsilon must be finite and at least 1 (1 is the vacuum)"; return MQC_HIP_ERR_VALIDATION; }
+    if (pcm::rule_index(o->angular_points) < 0) {
+        msg = "PCM: angular_points = " + std::to_string(o->angular_points) + " is not a Lebedev rule of the engine up to 590 points "
+              "(38, 50, 74, 86, 110, 146, 170, 194, 230, 266, 302, 350, 434, 590)";
+        return MQC_HIP_ERR_VALIDATION;
+    }
+    if (!std::isfinite(o->radius_scale) || !(o->radius_scale > 0.0)) { msg = "PCM: radius_scale must be positive and finite"; return MQC_HIP_ERR_VALIDATION; }
+    return MQC_HIP_OK;
+}
+
+int pcm_build_cavity(const mqc_hip_molecule_t& mol, const mqc_hip_pcm_options_t& o, pcm::Cavity& cav, std::string& msg)
+{
+    if (mol.n_point_charges > 0) { msg = "PCM: a fragment that carries external point charges is not supported (the charges would have to polarise the continuum too)"; return MQC_HIP_ERR_UNSUPPORTED; }
+    if (mol.h_extra) { msg = "PCM: a fragment that carries an extra one-electron operator (h_extra) is not supported"; return MQC_HIP_ERR_UNSUPPORTED; }
+    std::vector<double> rho;
+    if (!pcm::sphere_radii(mol.n_atoms, mol.atomic_numbers, mol.ghost, o.radius_scale, o.radii_by_z, rho, msg)) return MQC_HIP_ERR_VALIDATION;
+    for (int k = 0; k < 3 * mol.n_atoms; ++k)
+        if (!std::isfinite(mol.xyz[k])) { msg = "PCM: a non-finite coordinate"; return MQC_HIP_ERR_VALIDATION; }
+    if (!pcm::build_cavity(mol.n_atoms, mol.xyz, rho.data(), o.angular_points, cav, msg)) return MQC_HIP_ERR_VALIDATION;
+    if (cav.count < 1) { msg = "PCM: the fragment has no real atom, so no cavity"; return MQC_HIP_ERR_VALIDATION; }
+    return MQC_HIP_OK;
 }
 
 size_t fragment_bytes(const BatchPlan& p)

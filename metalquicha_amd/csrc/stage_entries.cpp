@@ -124,6 +124,76 @@ int mqc_hip_eri_packed_attenuated(mqc_hip_context* ctx, const mqc_hip_molecule_t
     return stage_eri_packed(ctx, mol, bas, omega, schwarz_tol, M);
 }
 
+// The PCM stage of one fragment for a given density: the SCF entry's setup and iteration kernels (kern_pcm.hip) on the
+// arrays of a one-fragment chunk, everything in between copied out
+int mqc_hip_pcm_stage(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, const mqc_hip_pcm_options_t* pcm,
+                      const double* D, int32_t tessera_capacity, int64_t a_capacity, int32_t* n_tesserae, double* tesserae, double* areas,
+                      double* A, double* v, double* q, double* e_pcm, double* V_pcm)
+{
+    if (!ctx || !mol || !bas || !pcm || !D || !n_tesserae) return fail(MQC_HIP_ERR_VALIDATION, "null argument");
+    if (!mol->atomic_numbers || !mol->xyz || mol->n_atoms <= 0) return fail(MQC_HIP_ERR_VALIDATION, "fragment has no geometry");
+    *n_tesserae = 0;
+    std::string why;
+    int rc = pcm_check_options(pcm, why);
+    if (rc != MQC_HIP_OK) return fail(rc, why);
+    pcm::Cavity cav;
+    rc = pcm_build_cavity(*mol, *pcm, cav, why);
+    *n_tesserae = cav.count;
+    if (rc != MQC_HIP_OK) return fail(rc, why);
+    HIP_CHECK_RET(hipSetDevice(ctx->device));
+    StageBatch sb;
+    if ((rc = build_topology(*mol, *bas, sb.topo, why)) != MQC_HIP_OK) return fail(rc, why);
+    if (sb.topo.nao > 256) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large (n_ao <= 256)");
+    const int T = cav.count, n = sb.topo.nao;
+    const size_t np = (size_t)sb.topo.npair, nn = (size_t)n * n;
+    if ((tesserae || areas || v || q) && tessera_capacity < T)
+        return fail(MQC_HIP_ERR_VALIDATION, "PCM stage: tessera_capacity " + std::to_string(tessera_capacity) + " is below the " + std::to_string(T) + " tesserae of the cavity");
+    if (A && a_capacity < (int64_t)((size_t)T * np))
+        return fail(MQC_HIP_ERR_VALIDATION, "PCM stage: a_capacity is below n_tesserae x npair = " + std::to_string((size_t)T * np));
+    if ((rc = upload_topology(ctx, sb.topo, sb.td)) != MQC_HIP_OK) return rc;
+    BatchPlan plan = stage_plan(sb.topo, TWO_E_NONE, 1);
+    plan.pcm_stride = pcm::chunk_stride(T);
+    plan.pcm_f = (pcm->epsilon - 1.0) / pcm->epsilon;
+    PcmView pv;
+    if ((rc = carve_slot(ctx, make_slot(ctx, 0, nullptr), plan, sb.td, 1, sb.bv, &pv)) != MQC_HIP_OK) return rc;
+    hipStream_t s = ctx->lane[0].stream;
+    const size_t ts = (size_t)pv.stride;
+    std::vector<double> hp(ts * 4, 0.0);
+    std::memcpy(hp.data(), cav.xyza.data(), sizeof(double) * 4 * (size_t)T);
+    HIP_CHECK_RET(hipMemcpyAsync(sb.bv.xyz, mol->xyz, sizeof(double) * 3 * mol->n_atoms, hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemsetAsync(sb.bv.istate, 0, sizeof(int) * 4, s));
+    HIP_CHECK_RET(hipMemcpyAsync(sb.bv.D, D, sizeof(double) * nn, hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemcpyAsync(pv.pts, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemcpyAsync(pv.nt, &T, sizeof(int), hipMemcpyHostToDevice, s));
+    // poison what the kernels must fill: an element they leave out reads as NaN
+    HIP_CHECK_RET(hipMemsetAsync(pv.A, 0xFF, sizeof(double) * ts * np, s));
+    HIP_CHECK_RET(hipMemsetAsync(pv.B, 0xFF, sizeof(double) * ts * np, s));
+    HIP_CHECK_RET(hipMemsetAsync(pv.Linv, 0xFF, sizeof(double) * ts * ts, s));      // the factorisation leaves its upper triangle alone
+    HIP_CHECK_RET(hipMemsetAsync(sb.bv.Vxc, 0xFF, sizeof(double) * nn, s));
+    launch_pcm_setup(sb.bv, pv, sb.topo, s);
+    launch_pcm_iteration(sb.bv, pv, false, s);
+    launch_pcm_charges(sb.bv, pv, s);
+    if ((rc = sync_and_check(s)) != MQC_HIP_OK) return rc;
+    double sc[8];
+    HIP_CHECK_RET(hipMemcpy(sc, pv.scal, sizeof(sc), hipMemcpyDeviceToHost));
+    if (sc[7] != 0.0) return fail(MQC_HIP_ERR_GENERIC, "PCM: the cavity matrix S of this fragment could not be factorised (a pivot failed)");
+    for (int t = 0; t < T; ++t) {
+        if (tesserae) { tesserae[3 * t] = cav.xyza[4 * (size_t)t]; tesserae[3 * t + 1] = cav.xyza[4 * (size_t)t + 1]; tesserae[3 * t + 2] = cav.xyza[4 * (size_t)t + 2]; }
+        if (areas) areas[t] = cav.xyza[4 * (size_t)t + 3];
+    }
+    if (A) HIP_CHECK_RET(hipMemcpy(A, pv.A, sizeof(double) * (size_t)T * np, hipMemcpyDeviceToHost));
+    if (v) HIP_CHECK_RET(hipMemcpy(v, pv.v, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost));
+    if (q) HIP_CHECK_RET(hipMemcpy(q, pv.b, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost));
+    if (e_pcm) *e_pcm = sc[0];
+    if (V_pcm) {
+        std::vector<double> acc(nn);
+        HIP_CHECK_RET(hipMemcpy(acc.data(), sb.bv.Vxc, sizeof(double) * nn, hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n; ++j) V_pcm[(size_t)i * n + j] = acc[(size_t)i * n + j] + acc[(size_t)j * n + i];
+    }
+    return MQC_HIP_OK;
+}
+
 int mqc_hip_jk_incore(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, const double* D, double* J, double* K)
 {
     StageBatch sb;

@@ -14,6 +14,9 @@
   run_hip_esp         <- (no counterpart) the potential of converged densities at arbitrary points (mqc_hip_esp_batch)
   run_hip_rimp2_batch, run_hip_rimp2_groups <- (no counterpart: the reference's MP2 is conventional) density-fitted RHF
                          and the RI-MP2 correlation energy of every converged fragment (mqc_hip_rimp2_batch)
+  PcmSettings, run_hip_scf_pcm_batch, run_hip_scf_pcm_groups <- the SCF with cuestPCMPotentialCompute's term ("C-PCM
+                         charges + V_pcm", mqc_cuest_integrals.f90:974-1366), this engine's own discretisation
+                         (mqc_hip_scf_pcm_batch)
 
 Same names, argument meaning and error behaviour; the numerics all happen in libmqc_hip.so.
 """
@@ -106,6 +109,7 @@ class EnergyT:
     scf: float = 0.0
     mp2_os: float = 0.0        # opposite-spin and same-spin parts of the RI-MP2 correlation energy (run_hip_rimp2_batch)
     mp2_ss: float = 0.0
+    pcm: float = 0.0           # E_pcm = q.v / 2 of a run in the continuum (run_hip_scf_pcm_batch); already part of scf
 
     @property
     def mp2(self) -> float:
@@ -113,6 +117,39 @@ class EnergyT:
 
     def total(self) -> float:
         return self.scf + self.mp2
+
+
+@dataclass
+class PcmSettings:
+    """C-PCM implicit solvation (mqc_hip_pcm_options_t): the dielectric constant (1 = vacuum), the Lebedev rule on
+    every atomic sphere, the scale of the built-in Bondi radii, and optionally the caller's own radii by atomic number
+    (Bohr, unscaled; a dict {Z: radius} or an array indexed by Z, 0 = built-in)."""
+    epsilon: float = 78.39
+    angular_points: int = 110
+    radius_scale: float = 1.2
+    radii_by_z: Optional[object] = None
+
+    def radii_table(self) -> Optional[np.ndarray]:
+        if self.radii_by_z is None:
+            return None
+        table = np.zeros(capi.PCM_RADII_LEN)
+        if isinstance(self.radii_by_z, dict):
+            for z, r in self.radii_by_z.items():
+                table[int(z)] = float(r)
+        else:
+            given = np.asarray(self.radii_by_z, dtype=np.float64).reshape(-1)
+            table[:min(len(given), len(table))] = given[:len(table)]
+        return table
+
+    def options(self, keep: list) -> capi.PcmOptions:
+        """The C struct; `keep` receives the array it points into."""
+        o = capi.PcmOptions()
+        o.epsilon = float(self.epsilon); o.angular_points = int(self.angular_points); o.radius_scale = float(self.radius_scale)
+        table = self.radii_table()
+        if table is not None:
+            keep.append(table)
+            o.radii_by_z = capi.dptr(table)
+        return o
 
 
 @dataclass
@@ -365,7 +402,8 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
                        gradients_out: Optional[list] = None, extras: Sequence[str] = (),
                        extras_out: Optional[list] = None, site_gradients_out: Optional[list] = None,
                        status_out: Optional[list] = None, initial_densities: Optional[Sequence] = None,
-                       spin_densities_out: Optional[list] = None, rimp2: Optional[dict] = None) -> List[np.ndarray]:
+                       spin_densities_out: Optional[list] = None, rimp2: Optional[dict] = None,
+                       pcm: Optional[dict] = None) -> List[np.ndarray]:
     """All fragments of all groups in ONE mqc_hip_scf_run_batch call; returns, per group, a structured array
     viewing the engine's result records (fields of capi.ScfResult: e_total, iterations, has_error, message ...).
 
@@ -388,13 +426,16 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
     geometry.  `spin_densities_out` (a list) receives one (m, 2, n_ao, n_ao) array per group, written for the fragments
     that ran unrestricted (zeros elsewhere).
 
-    `rimp2` (a dict, see run_hip_rimp2_groups) sends the batch through mqc_hip_rimp2_batch."""
+    `rimp2` (a dict, see run_hip_rimp2_groups) sends the batch through mqc_hip_rimp2_batch; `pcm` (a dict, see
+    run_hip_scf_pcm_groups) through mqc_hip_scf_pcm_batch."""
     embedded = site_gradients_out is not None
     restart = initial_densities is not None or spin_densities_out is not None
     if restart and embedded:
         raise ValueError("starting densities and the embedded-gradient entry do not combine")
     if rimp2 is not None and (restart or embedded):
         raise ValueError("RI-MP2 combines with neither starting densities nor the embedded-gradient entry")
+    if pcm is not None and (restart or embedded or rimp2 is not None):
+        raise ValueError("PCM combines with neither starting densities, the embedded-gradient entry nor RI-MP2")
     if initial_densities is not None and len(initial_densities) != len(groups):
         raise ValueError("initial_densities must hold one entry per group")
     want_gradient = bool(want_gradient) or embedded
@@ -404,6 +445,8 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
         if rimp2 is not None:
             rimp2.update(e_os=[np.zeros(0) for _ in groups], e_ss=[np.zeros(0) for _ in groups],
                          mp2_done=[np.zeros(0, dtype=np.int32) for _ in groups])
+        if pcm is not None:
+            pcm.update(e_pcm=[np.zeros(0) for _ in groups], n_tesserae=[np.zeros(0, dtype=np.int32) for _ in groups])
         return [np.zeros(0, dtype=_RES_DTYPE) for _ in groups]
     lib = capi.load_library()
     ctx = capi.get_context(settings.device_rank)
@@ -554,6 +597,15 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
                                      done.ctypes.data_as(capi.c_int32_p))
         cuts = np.cumsum(sizes)[:-1]
         rimp2.update(e_os=np.split(e_os, cuts), e_ss=np.split(e_ss, cuts), mp2_done=np.split(done, cuts))
+    elif pcm is not None:
+        e_pcm, n_tess = np.zeros(n), np.zeros(n, dtype=np.int32)
+        popts = pcm["settings"].options(keep)
+        rc = lib.mqc_hip_scf_pcm_batch(ctx, n, mols.ctypes.data_as(C.POINTER(capi.Molecule)),
+                                       bass.ctypes.data_as(C.POINTER(capi.Basis)),
+                                       auxs.ctypes.data_as(C.POINTER(capi.Basis)) if df else None, C.byref(opts), C.byref(popts), res,
+                                       capi.dptr(e_pcm), n_tess.ctypes.data_as(capi.c_int32_p))
+        cuts = np.cumsum(sizes)[:-1]
+        pcm.update(e_pcm=np.split(e_pcm, cuts), n_tesserae=np.split(n_tess, cuts))
     else:
         rc = lib.mqc_hip_scf_run_batch(ctx, n, mols.ctypes.data_as(C.POINTER(capi.Molecule)),
                                        bass.ctypes.data_as(C.POINTER(capi.Basis)),
@@ -693,6 +745,35 @@ def run_hip_rimp2_batch(settings: ScfSettings, fragments: Sequence[PhysicalFragm
             if results[i].has_energy and dn[pos]:
                 results[i].energy.mp2_os = float(os_[pos]); results[i].energy.mp2_ss = float(ss_[pos])
                 results[i].has_mp2 = True
+    return results
+
+
+def run_hip_scf_pcm_groups(settings: ScfSettings, pcm: PcmSettings, groups: Sequence[FragmentGroup], want_gradient: bool = False,
+                           extras: Sequence[str] = (), extras_out: Optional[list] = None, status_out: Optional[list] = None):
+    """All fragments of all groups in ONE mqc_hip_scf_pcm_batch call: run_hip_scf_groups in the C-PCM continuum `pcm`
+    describes.  -> (records, e_pcm, n_tesserae): per group the result records (e_total and e_electronic contain E_pcm)
+    and two arrays (m,): E_pcm (0 where the fragment failed) and the tesserae of its cavity.  Refusals (a gradient,
+    point charges, h_extra, a bad epsilon or rule, an element without a radius) arrive in the records' messages, the
+    call's status in `status_out`."""
+    box = {"settings": pcm}
+    rec = run_hip_scf_groups(settings, groups, want_gradient=want_gradient, extras=extras, extras_out=extras_out,
+                             status_out=status_out, pcm=box)
+    return rec, box["e_pcm"], box["n_tesserae"]
+
+
+def run_hip_scf_pcm_batch(settings: ScfSettings, pcm: PcmSettings, fragments: Sequence[PhysicalFragment]) -> List[CalculationResult]:
+    """Many independent fragments through mqc_hip_scf_pcm_batch, results as CalculationResult objects: energy.scf is the
+    total energy in the continuum and energy.pcm the part of it that is E_pcm."""
+    results = [CalculationResult() for _ in range(len(fragments))]
+    if not fragments:
+        return results
+    groups, index = _groups_of(fragments)
+    recs, e_pcm, _ = run_hip_scf_pcm_groups(settings, pcm, groups)
+    for idx, rec, ep in zip(index, recs, e_pcm):
+        for pos, (i, r) in enumerate(zip(idx, rec)):
+            _fill_record(results[i], r)
+            if results[i].has_energy:
+                results[i].energy.pcm = float(ep[pos])
     return results
 
 
