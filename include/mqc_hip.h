@@ -437,6 +437,44 @@ int mqc_hip_pcm_stage(mqc_hip_context *ctx, const mqc_hip_molecule_t *mol, const
                       int32_t *n_tesserae, double *tesserae, double *areas, double *A, double *v, double *q,
                       double *e_pcm, double *V_pcm);
 
+/* The gradient stage of ONE fragment on the CALLER'S densities: the device terms of the analytic gradient, each returned
+ * on its own -- never summed with each other or with E_nuc' (kern_grad.hip: grad_weighted_density_kernel, grad1e_kernel,
+ * eri_grad_kernel, the screening kernels).  Nothing has to be converged; the matrices are row-major.
+ *   inputs    D [n*n] (total density; the alpha density when D_beta is given), D_beta [n*n] or NULL, C [n*n] (AO x MO),
+ *             eps [n], n_occ (n_alpha when unrestricted); C_beta, eps_beta, n_beta when unrestricted; exx
+ *   w         [n*n] the energy-weighted density occ sum_i eps_i C_i C_i^T
+ *   g1e       [natoms*3] sum D (T' + V') - W S' over all shell pairs; g1e_pair: the same for the one pair of shells
+ *             (pair_a, pair_b), or NULL
+ *   g2e       [natoms*3] the exact two-electron term over every class list; with Q [nshell*nshell] (Schwarz bounds) it is
+ *             the screened route with threshold q_thresh instead
+ *   rows      per-row mode, row_count > 0: the slice [row_start, row_start + row_count) of the list of class
+ *             (la lb|lc ld) = row_class, exactly as the topology holds it (mode 0), or of the lists of the density-fitted
+ *             term (mode 1: (A B|P -), orbital A >= B, auxiliary P, class (la lb|lp 0); mode 2: (P -|Q -), auxiliary
+ *             P >= Q, class (lp 0|lq 0)) with Gamma from gam ([naux][n*n] or [naux][naux]) and the auxiliary basis aux.
+ *             rows [row_count*4] receives the rows, class_length the length of the list, g_rows [row_count][natoms*3]
+ *             one launch's result per row; g_rows NULL: rows and class_length only, no device work for them.
+ * Outputs passed as NULL are not computed.  Refusals (MQC_HIP_ERR_VALIDATION, nothing written): null arguments, a shell
+ * or a class with l > 3, a class the topology does not have, a slice outside the list, a shell pair that does not exist,
+ * occupations outside 0..n_ao, non-finite input.  (Added without an ABI bump: no existing struct changed.) */
+typedef struct {
+    const double *D, *D_beta, *C, *eps, *C_beta, *eps_beta;
+    int32_t n_occ, n_beta;
+    double exx;
+    double *w, *g1e, *g1e_pair, *g2e;
+    int32_t pair_a, pair_b;
+    const double *Q;
+    double q_thresh;
+    int32_t mode;              /* 0 exact, 1 three-centre, 2 two-centre */
+    int32_t row_class[4];
+    int64_t row_start, row_count;
+    const double *gam;
+    int32_t *rows;
+    int64_t *class_length;
+    double *g_rows;
+} mqc_hip_gradient_stage_t;
+int mqc_hip_gradient_stage(mqc_hip_context *ctx, const mqc_hip_molecule_t *mol, const mqc_hip_basis_t *orbital,
+                           const mqc_hip_basis_t *aux /* NULL unless mode 1 or 2 */, const mqc_hip_gradient_stage_t *args);
+
 int mqc_hip_syev(mqc_hip_context *ctx, int32_t n, const double *A, double *w, double *V);
 /* DIIS coefficients from an age-ordered overlap matrix, the device routine's algorithm
  * (diis_coefficients/solve_diis, src/methods/mqc_diis.f90:164-273) */

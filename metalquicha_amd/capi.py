@@ -69,6 +69,15 @@ class PcmOptions(C.Structure):
                 ("radii_by_z", c_double_p)]
 
 
+class GradientStage(C.Structure):
+    _fields_ = [("D", c_double_p), ("D_beta", c_double_p), ("C", c_double_p), ("eps", c_double_p), ("C_beta", c_double_p),
+                ("eps_beta", c_double_p), ("n_occ", C.c_int32), ("n_beta", C.c_int32), ("exx", C.c_double),
+                ("w", c_double_p), ("g1e", c_double_p), ("g1e_pair", c_double_p), ("g2e", c_double_p),
+                ("pair_a", C.c_int32), ("pair_b", C.c_int32), ("Q", c_double_p), ("q_thresh", C.c_double),
+                ("mode", C.c_int32), ("row_class", C.c_int32 * 4), ("row_start", C.c_int64), ("row_count", C.c_int64),
+                ("gam", c_double_p), ("rows", c_int32_p), ("class_length", c_int64_p), ("g_rows", c_double_p)]
+
+
 PCM_RADII_LEN = 119          # MQC_HIP_PCM_RADII_LEN: a caller's radii_by_z is indexed by atomic number
 
 
@@ -93,6 +102,7 @@ DECLARED_SYMBOLS = [
     "mqc_hip_scf_run_batch_restart", "mqc_hip_rimp2_batch", "mqc_hip_df_jk_batch", "mqc_hip_df_fit_batch",
     "mqc_hip_jk_tensor_layout", "mqc_hip_jk_incore_batch",
     "mqc_hip_default_pcm_options", "mqc_hip_scf_pcm_batch", "mqc_hip_pcm_stage",
+    "mqc_hip_gradient_stage",
 ]
 
 _lib = None
@@ -136,6 +146,7 @@ def load_library():
     lib.mqc_hip_pcm_stage.argtypes = [C.c_void_p, C.POINTER(Molecule), C.POINTER(Basis), C.POINTER(PcmOptions), c_double_p, C.c_int32,
                                       C.c_int64, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                       c_double_p]
+    lib.mqc_hip_gradient_stage.argtypes = [C.c_void_p, C.POINTER(Molecule), C.POINTER(Basis), C.POINTER(Basis), C.POINTER(GradientStage)]
     lib.mqc_hip_int1e.argtypes = [C.c_void_p, C.POINTER(Molecule), C.POINTER(Basis), c_double_p, c_double_p, c_double_p]
     lib.mqc_hip_eri_packed.argtypes = [C.c_void_p, C.POINTER(Molecule), C.POINTER(Basis), C.c_double, c_double_p]
     lib.mqc_hip_eri_packed_attenuated.argtypes = [C.c_void_p, C.POINTER(Molecule), C.POINTER(Basis), C.c_double, C.c_double, c_double_p]

@@ -865,9 +865,70 @@ static Grad2eLayout grad2e_layout(int la, int lb, int lc, int ld)
     return g;
 }
 
-// Gradient of the whole batch into d_grad [nfrag][natoms][3] (zeroed here); Dtot = D (restricted) or D_a + D_b.
-// work: device scratch of at least 2 * nfrag * n * n doubles (energy-weighted density, total density of a UHF run).
 bool launch_xc_gradient(const BatchView& bv, double* d_grad, hipStream_t s, std::string& err);      // kern_xc.hip
+
+// ---------------------------------------------------------------------------------------
+// The steps of launch_gradient.  The gradient stage entry (mqc_hip_gradient_stage, stage_entries.cpp) runs the same
+// steps one at a time on a caller's densities, so they are functions of the namespace and not of this file alone.
+
+// both wave kernels take up to the whole LDS of a compute unit
+void grad_prepare_kernels()
+{
+    (void)hipFuncSetAttribute((const void*)grad1e_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)eri_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+
+// W into work [nfrag][n*n]; an unrestricted run's total density behind it.  Returns the total density.
+double* launch_grad_densities(const BatchView& bv, double* work, hipStream_t s)
+{
+    const int nf = bv.nfrag;
+    const size_t nn = (size_t)bv.n * bv.n;
+    hipLaunchKernelGGL(grad_weighted_density_kernel, dim3((unsigned)((nn + 255) / 256), nf), dim3(256), 0, s, bv, work);
+    if (!bv.uhf) return bv.D;
+    double* Dtot = work + (size_t)nf * nn;
+    const size_t tot = (size_t)nf * nn;
+    hipLaunchKernelGGL(grad_total_density_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, bv, Dtot);
+    return Dtot;
+}
+
+// grad1e_kernel over npairs shell pairs (la >= lb, device list) of every fragment of the view
+void launch_grad1e_pairs(const BatchView& bv, int la, int lb, const int* d_pairs, int npairs, const double* Dtot, const double* Wm,
+                         double* d_grad, hipStream_t s)
+{
+    const Grad1eLayout lay = grad1e_layout(la, lb);
+    const long total = (long)npairs * bv.nfrag;
+    hipLaunchKernelGGL(grad1e_kernel, dim3((unsigned)total), dim3(64), sizeof(double) * (size_t)lay.total, s, bv, la, lb, lay,
+                       d_pairs, npairs, Dtot, Wm, d_grad);
+}
+
+// eri_grad_kernel over nq rows (device list) of one class for every fragment of the view: layout, LDS check, launch
+bool launch_eri_grad_rows(const BatchView& bv, int la, int lb, int lc, int ld, const int* d_list, int nq, const double* Dtot,
+                          const double* Dbeta, double* d_grad, int mode, const double* gam, hipStream_t s, std::string& err)
+{
+    const Grad2eLayout lay = grad2e_layout(la, lb, lc, ld);
+    if (sizeof(double) * (size_t)lay.total > 160 * 1024) { err = "gradient: class too large for LDS"; return false; }
+    const long total = (long)nq * bv.nfrag;
+    hipLaunchKernelGGL(eri_grad_kernel, dim3((unsigned)total), dim3(64), sizeof(double) * (size_t)lay.total, s, bv, la, lb, lc, ld, lay,
+                       d_list, nq, Dtot, Dbeta, d_grad, mode, gam);
+    return true;
+}
+
+// task lists of the density-fitted term: (A >= B, P, -) by (la, lb, lp); (P, -, Q <= P, -) by (lp, lq)
+void df_gradient_lists(const Topology& topo, const Topology& aux, std::vector<int> (&t3)[4][4][4], std::vector<int> (&t2)[4][4])
+{
+    const int ns = (int)topo.shells.size(), nx = (int)aux.shells.size();
+    for (int A = 0; A < ns; ++A)
+        for (int B = 0; B <= A; ++B)
+            for (int P = 0; P < nx; ++P) {
+                auto& v = t3[topo.shells[A].l][topo.shells[B].l][aux.shells[P].l];
+                v.push_back(A); v.push_back(B); v.push_back(P); v.push_back(0);
+            }
+    for (int P = 0; P < nx; ++P)
+        for (int Q = 0; Q <= P; ++Q) {
+            auto& v = t2[aux.shells[P].l][aux.shells[Q].l];
+            v.push_back(P); v.push_back(0); v.push_back(Q); v.push_back(0);
+        }
+}
 
 static bool launch_df_gradient(const BatchView& bv, const Topology& topo, const Topology& aux, const double* Dtot, double* d_grad,
                                hipStream_t s, std::string& err)
@@ -899,20 +960,8 @@ static bool launch_df_gradient(const BatchView& bv, const Topology& topo, const 
     hipLaunchKernelGGL(dfg_gamma_kernel, ge, dim3(256), 0, s, bv, Dtot, (const double*)cvec, (const double*)Y, x, Z, Gam);
     hipLaunchKernelGGL(dfg_cfit_kernel, dim3((np + 255) / 256, na, nf), dim3(256), 0, s, bv, Cfit);
     hipLaunchKernelGGL(dfg_gamma2_kernel, dim3(na * na, nf), dim3(64), 0, s, bv, (const double*)cvec, (const double*)Cfit, (const double*)Z, x, gam2);
-    // ---- task lists: (A >= B, P) by (la, lb, lp); (P >= Q) by (lp, lq)
-    const int ns = (int)topo.shells.size(), nx = (int)aux.shells.size();
     std::vector<int> t3[4][4][4], t2[4][4];
-    for (int A = 0; A < ns; ++A)
-        for (int B = 0; B <= A; ++B)
-            for (int P = 0; P < nx; ++P) {
-                auto& v = t3[topo.shells[A].l][topo.shells[B].l][aux.shells[P].l];
-                v.push_back(A); v.push_back(B); v.push_back(P); v.push_back(0);
-            }
-    for (int P = 0; P < nx; ++P)
-        for (int Q = 0; Q <= P; ++Q) {
-            auto& v = t2[aux.shells[P].l][aux.shells[Q].l];
-            v.push_back(P); v.push_back(0); v.push_back(Q); v.push_back(0);
-        }
+    df_gradient_lists(topo, aux, t3, t2);
     size_t tot = 0;
     for (auto& a : t3) for (auto& b : a) for (auto& c : b) tot += c.size();
     for (auto& a : t2) for (auto& b : a) tot += b.size();
@@ -922,11 +971,7 @@ static bool launch_df_gradient(const BatchView& bv, const Topology& topo, const 
     auto run = [&](std::vector<int>& v, int la, int lb, int lc, int mode, const double* g) -> bool {
         if (v.empty()) return true;
         (void)hipMemcpyAsync(d + off, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, s);
-        const Grad2eLayout lay = grad2e_layout(la, lb, lc, 0);
-        if (sizeof(double) * (size_t)lay.total > 160 * 1024) { err = "gradient: class too large for LDS"; return false; }
-        const long total = (long)(v.size() / 4) * nf;
-        hipLaunchKernelGGL(eri_grad_kernel, dim3((unsigned)total), dim3(64), sizeof(double) * (size_t)lay.total, s, bv, la, lb, lc, 0, lay,
-                           d + off, (int)(v.size() / 4), (const double*)nullptr, (const double*)nullptr, d_grad, mode, g);
+        if (!launch_eri_grad_rows(bv, la, lb, lc, 0, d + off, (int)(v.size() / 4), nullptr, nullptr, d_grad, mode, g, s, err)) return false;
         off += v.size();
         return true;
     };
@@ -979,36 +1024,17 @@ static bool launch_eri_grad_screened(const BatchView& bv, const Topology& topo, 
         for (int k = 0; k < ncl; ++k) {
             if (hcount[k] == 0) continue;
             const auto& cl = topo.classes[k];
-            const Grad2eLayout lay = grad2e_layout(cl.la, cl.lb, cl.lc, cl.ld);
-            if (sizeof(double) * (size_t)lay.total > 160 * 1024) { err = "gradient: class too large for LDS"; return false; }
-            hipLaunchKernelGGL(eri_grad_kernel, dim3((unsigned)hcount[k]), dim3(64), sizeof(double) * (size_t)lay.total, s, vf, cl.la, cl.lb, cl.lc, cl.ld, lay,
-                               (const int*)(out + class_off[k] - class_off[0]), hcount[k], Dtot + f * nn, Dbf, d_grad + (size_t)f * topo.natoms * 3);
+            if (!launch_eri_grad_rows(vf, cl.la, cl.lb, cl.lc, cl.ld, (const int*)(out + class_off[k] - class_off[0]), hcount[k], Dtot + f * nn,
+                                      Dbf, d_grad + (size_t)f * topo.natoms * 3, GRAD_EXACT, nullptr, s, err)) return false;
         }
     }
     return true;
 }
 
-bool launch_gradient(const BatchView& bv, const Topology& topo, const Topology* aux, double* d_grad, double* work, int* d_lists,
-                     size_t list_capacity_ints, hipStream_t s, std::string& err, const double* schwarz, double screen_tol)
+// ---- one-electron: pairs bucketed by (la >= lb); the lists go to d_lists from `off` on, which moves past them
+void grad_one_electron(const BatchView& bv, const Topology& topo, const double* Dtot, const double* Wm, double* d_grad, int* d_lists,
+                       size_t& off, hipStream_t s)
 {
-    const int n = bv.n, nf = bv.nfrag;
-    const size_t nn = (size_t)n * n;
-    if (topo.lmax > 3) { err = "analytic gradients cover s, p, d and f shells"; return false; }
-    double* Wm = work;
-    double* Dtot = bv.D;
-    // MQC_HIP_GRAD_TIMING=1 (measurement): the span of this stage and of its XC part on stderr, per batch
-    static const bool timing = env_opt_in("MQC_HIP_GRAD_TIMING");
-    hipEvent_t ev[3] = {};
-    if (timing) for (auto& e : ev) { (void)hipEventCreate(&e); }
-    if (timing) (void)hipEventRecord(ev[0], s);
-    (void)hipMemsetAsync(d_grad, 0, sizeof(double) * (size_t)nf * topo.natoms * 3, s);
-    hipLaunchKernelGGL(grad_weighted_density_kernel, dim3((unsigned)((nn + 255) / 256), nf), dim3(256), 0, s, bv, Wm);
-    if (bv.uhf) {
-        Dtot = work + (size_t)nf * nn;
-        const size_t tot = (size_t)nf * nn;
-        hipLaunchKernelGGL(grad_total_density_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, bv, Dtot);
-    }
-    // ---- one-electron: pairs bucketed by (la >= lb)
     static std::vector<int> bucket[2][4][4];
     auto& bk = bucket[bv.slot & 1];
     for (auto& row : bk) for (auto& b : row) b.clear();
@@ -1018,28 +1044,25 @@ bool launch_gradient(const BatchView& bv, const Topology& topo, const Topology* 
         if (la < lb) { std::swap(A, B); std::swap(la, lb); }
         bk[la][lb].push_back(A); bk[la][lb].push_back(B);
     }
-    size_t need = topo.pairs.size();
-    if (bv.naux == 0) for (auto& cl : topo.classes) need += cl.quartets.size();
-    if (need + 64 > list_capacity_ints) { err = "gradient: list buffer too small"; return false; }
-    size_t off = 0;
-    (void)hipFuncSetAttribute((const void*)grad1e_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)eri_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     for (int la = 0; la <= 3; ++la)
         for (int lb = 0; lb <= la; ++lb) {
             auto& v = bk[la][lb];
             if (v.empty()) continue;
             (void)hipMemcpyAsync(d_lists + off, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, s);
-            const Grad1eLayout lay = grad1e_layout(la, lb);
-            const long total = (long)(v.size() / 2) * nf;
-            hipLaunchKernelGGL(grad1e_kernel, dim3((unsigned)total), dim3(64), sizeof(double) * (size_t)lay.total, s, bv, la, lb, lay,
-                               d_lists + off, (int)(v.size() / 2), Dtot, Wm, d_grad);
+            launch_grad1e_pairs(bv, la, lb, d_lists + off, (int)(v.size() / 2), Dtot, Wm, d_grad, s);
             off += v.size();
         }
-    // ---- two-electron: density-fitted, or every canonical class of the exact integrals
+}
+
+// ---- two-electron: density-fitted, or every canonical class of the exact integrals (screened when schwarz is given)
+bool grad_two_electron(const BatchView& bv, const Topology& topo, const Topology* aux, const double* Dtot, double* d_grad, int* d_lists,
+                       size_t& off, const double* schwarz, double screen_tol, hipStream_t s, std::string& err)
+{
     if (bv.naux > 0) {
         if (!aux) { err = "gradient: the auxiliary basis is missing"; return false; }
-        if (!launch_df_gradient(bv, topo, *aux, Dtot, d_grad, s, err)) return false;
-    } else if (schwarz) {
+        return launch_df_gradient(bv, topo, *aux, Dtot, d_grad, s, err);
+    }
+    if (schwarz) {
         std::vector<size_t> class_off;
         for (auto& cl : topo.classes) {
             class_off.push_back(off);
@@ -1047,18 +1070,46 @@ bool launch_gradient(const BatchView& bv, const Topology& topo, const Topology* 
                 (void)hipMemcpyAsync(d_lists + off, cl.quartets.data(), cl.quartets.size() * sizeof(int), hipMemcpyHostToDevice, s);
             off += cl.quartets.size();
         }
-        if (!launch_eri_grad_screened(bv, topo, Dtot, d_grad, d_lists, class_off, schwarz, screen_tol, s, err)) return false;
-    } else
+        return launch_eri_grad_screened(bv, topo, Dtot, d_grad, d_lists, class_off, schwarz, screen_tol, s, err);
+    }
     for (auto& cl : topo.classes) {
         if (cl.quartets.empty()) continue;
         (void)hipMemcpyAsync(d_lists + off, cl.quartets.data(), cl.quartets.size() * sizeof(int), hipMemcpyHostToDevice, s);
-        const Grad2eLayout lay = grad2e_layout(cl.la, cl.lb, cl.lc, cl.ld);
-        if (sizeof(double) * (size_t)lay.total > 160 * 1024) { err = "gradient: class too large for LDS"; return false; }
-        const long total = (long)(cl.quartets.size() / 4) * nf;
-        hipLaunchKernelGGL(eri_grad_kernel, dim3((unsigned)total), dim3(64), sizeof(double) * (size_t)lay.total, s, bv, cl.la, cl.lb, cl.lc, cl.ld, lay,
-                           d_lists + off, (int)(cl.quartets.size() / 4), Dtot, bv.uhf ? bv.Db : (const double*)nullptr, d_grad);
+        if (!launch_eri_grad_rows(bv, cl.la, cl.lb, cl.lc, cl.ld, d_lists + off, (int)(cl.quartets.size() / 4), Dtot,
+                                  bv.uhf ? bv.Db : (const double*)nullptr, d_grad, GRAD_EXACT, nullptr, s, err)) return false;
         off += cl.quartets.size();
     }
+    return true;
+}
+
+// ints of d_lists the two steps above use
+size_t grad_list_ints(const BatchView& bv, const Topology& topo)
+{
+    size_t need = topo.pairs.size();
+    if (bv.naux == 0) for (auto& cl : topo.classes) need += cl.quartets.size();
+    return need;
+}
+
+// Gradient of the whole batch into d_grad [nfrag][natoms][3] (zeroed here); Dtot = D (restricted) or D_a + D_b.
+// work: device scratch of at least 2 * nfrag * n * n doubles (energy-weighted density, total density of a UHF run).
+bool launch_gradient(const BatchView& bv, const Topology& topo, const Topology* aux, double* d_grad, double* work, int* d_lists,
+                     size_t list_capacity_ints, hipStream_t s, std::string& err, const double* schwarz, double screen_tol)
+{
+    const int n = bv.n, nf = bv.nfrag;
+    if (topo.lmax > 3) { err = "analytic gradients cover s, p, d and f shells"; return false; }
+    double* Wm = work;
+    // MQC_HIP_GRAD_TIMING=1 (measurement): the span of this stage and of its XC part on stderr, per batch
+    static const bool timing = env_opt_in("MQC_HIP_GRAD_TIMING");
+    hipEvent_t ev[3] = {};
+    if (timing) for (auto& e : ev) { (void)hipEventCreate(&e); }
+    if (timing) (void)hipEventRecord(ev[0], s);
+    (void)hipMemsetAsync(d_grad, 0, sizeof(double) * (size_t)nf * topo.natoms * 3, s);
+    const double* Dtot = launch_grad_densities(bv, work, s);
+    if (grad_list_ints(bv, topo) + 64 > list_capacity_ints) { err = "gradient: list buffer too small"; return false; }
+    size_t off = 0;
+    grad_prepare_kernels();
+    grad_one_electron(bv, topo, Dtot, Wm, d_grad, d_lists, off, s);
+    if (!grad_two_electron(bv, topo, aux, Dtot, d_grad, d_lists, off, schwarz, screen_tol, s, err)) return false;
     // ---- exchange-correlation (Kohn-Sham): moving functions, moving points, moving partition
     if (timing) (void)hipEventRecord(ev[1], s);
     if (bv.xc.ncomp > 0 && !launch_xc_gradient(bv, d_grad, s, err)) return false;

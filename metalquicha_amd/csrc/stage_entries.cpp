@@ -1,6 +1,6 @@
 // stage_entries.cpp -- the stage-level extern "C" entry points of libmqc_hip.so: one stage of the engine on the caller's
-// inputs (one-electron integrals, the ERI tensor, J/K, Coulomb and potential batches, the XC quadrature, the
-// eigen-solver, the DIIS coefficients).  They run on lane 0 with the driver's own pieces (driver.hpp).
+// inputs (one-electron integrals, the ERI tensor, J/K, Coulomb and potential batches, the XC quadrature, the terms of
+// the analytic gradient, the eigen-solver, the DIIS coefficients).  They run on lane 0 with the driver's own pieces (driver.hpp).
 #include "driver.hpp"
 #include <algorithm>
 #include <cmath>
@@ -14,6 +14,19 @@ bool launch_esp(const TopologyDev& td, const Topology& topo, const double* boys_
                 hipStream_t s, std::string& err);
 size_t esp_record_doubles(const Topology& topo);
 static DevicePool g_esp_pool;
+// kern_grad.hip: the steps of launch_gradient
+void grad_prepare_kernels();
+double* launch_grad_densities(const BatchView& bv, double* work, hipStream_t s);
+void launch_grad1e_pairs(const BatchView& bv, int la, int lb, const int* d_pairs, int npairs, const double* Dtot, const double* Wm,
+                         double* d_grad, hipStream_t s);
+bool launch_eri_grad_rows(const BatchView& bv, int la, int lb, int lc, int ld, const int* d_list, int nq, const double* Dtot,
+                          const double* Dbeta, double* d_grad, int mode, const double* gam, hipStream_t s, std::string& err);
+void df_gradient_lists(const Topology& topo, const Topology& aux, std::vector<int> (&t3)[4][4][4], std::vector<int> (&t2)[4][4]);
+void grad_one_electron(const BatchView& bv, const Topology& topo, const double* Dtot, const double* Wm, double* d_grad, int* d_lists,
+                       size_t& off, hipStream_t s);
+bool grad_two_electron(const BatchView& bv, const Topology& topo, const Topology* aux, const double* Dtot, double* d_grad, int* d_lists,
+                       size_t& off, const double* schwarz, double screen_tol, hipStream_t s, std::string& err);
+size_t grad_list_ints(const BatchView& bv, const Topology& topo);
 
 // every fragment has the elements (and ghosts) of the first, and its arrays: one topology per batched call
 static bool same_elements(const mqc_hip_molecule_t* mols, int64_t nfrag)
@@ -191,6 +204,209 @@ int mqc_hip_pcm_stage(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const
         for (int i = 0; i < n; ++i)
             for (int j = 0; j < n; ++j) V_pcm[(size_t)i * n + j] = acc[(size_t)i * n + j] + acc[(size_t)j * n + i];
     }
+    return MQC_HIP_OK;
+}
+
+// The gradient stage of one fragment on the caller's densities (include/mqc_hip.h): the steps of launch_gradient
+// (kern_grad.hip) one at a time, every term into a buffer of its own
+int mqc_hip_gradient_stage(mqc_hip_context* ctx, const mqc_hip_molecule_t* mol, const mqc_hip_basis_t* bas, const mqc_hip_basis_t* auxbas,
+                           const mqc_hip_gradient_stage_t* a)
+{
+    if (!mol || !bas || !a) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: null argument");
+    if (!mol->atomic_numbers || !mol->xyz || mol->n_atoms <= 0) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: fragment has no geometry");
+    const bool want_rows = a->row_count > 0;
+    const bool device_rows = want_rows && a->g_rows;
+    const bool whole = a->w || a->g1e || a->g1e_pair || a->g2e;
+    const bool uhf = a->D_beta != nullptr;
+    const int mode = a->mode;
+    // the rows alone are host work: only then may the context be missing
+    if (!ctx && (whole || device_rows)) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: null argument (context)");
+    if (mode < 0 || mode > 2) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: mode must be 0 (exact), 1 (three-centre) or 2 (two-centre)");
+    if (want_rows && (!a->rows || !a->class_length)) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: null argument (rows, class_length)");
+    if (want_rows && mode != 0 && !auxbas) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: null argument (the auxiliary basis of a density-fitted row)");
+    if (device_rows && mode != 0 && !a->gam) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: null argument (gam)");
+    const bool need_d = whole || (device_rows && mode == 0);
+    if (need_d && !a->D) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: null argument (D)");
+    const bool need_w = a->w || a->g1e || a->g1e_pair;
+    if (need_w && (!a->C || !a->eps || (uhf && (!a->C_beta || !a->eps_beta))))
+        return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: null argument (C, eps)");
+    if (want_rows)
+        for (int k = 0; k < 4; ++k)
+            if (a->row_class[k] < 0 || a->row_class[k] > KERNEL_LMAX)
+                return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: class with l = " + std::to_string(a->row_class[k]) + " (l > 3 is not covered: s, p, d and f shells)");
+    std::string why;
+    StageBatch sb;
+    Topology xtopo;
+    int rc = build_topology(*mol, *bas, sb.topo, why);
+    if (rc != MQC_HIP_OK) return fail(rc, "gradient stage: " + why);
+    const Topology& topo = sb.topo;
+    if (topo.lmax > KERNEL_LMAX) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: a shell with l > 3 (s, p, d and f shells are covered)");
+    if (topo.nao > 256) return fail(MQC_HIP_ERR_UNSUPPORTED, "fragment too large (n_ao <= 256)");
+    if (want_rows && mode != 0) {
+        if ((rc = build_topology(*mol, *auxbas, xtopo, why, AUX_LMAX, false)) != MQC_HIP_OK) return fail(rc, "gradient stage: auxiliary basis: " + why);
+    }
+    const int n = topo.nao, nat = topo.natoms, ns = (int)topo.shells.size(), na = xtopo.nao;
+    const size_t nn = (size_t)n * n, g3 = (size_t)nat * 3;
+    for (int k = 0; k < 3 * nat; ++k)
+        if (!std::isfinite(mol->xyz[k])) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: non-finite input (a coordinate)");
+    auto finite = [](const double* p, size_t count) {
+        for (size_t k = 0; k < count; ++k) if (!std::isfinite(p[k])) return false;
+        return true;
+    };
+    if (!std::isfinite(a->exx)) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: non-finite input (exx)");
+    if (need_d && (!finite(a->D, nn) || (uhf && !finite(a->D_beta, nn)))) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: non-finite input (the density)");
+    if (need_w) {
+        if (!finite(a->C, nn) || !finite(a->eps, n) || (uhf && (!finite(a->C_beta, nn) || !finite(a->eps_beta, n))))
+            return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: non-finite input (C, eps)");
+        if (a->n_occ < 0 || a->n_occ > n || (uhf && (a->n_beta < 0 || a->n_beta > n)))
+            return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: occupations outside 0..n_ao");
+    }
+    if (a->g2e && a->Q && (!finite(a->Q, (size_t)ns * ns) || !std::isfinite(a->q_thresh)))
+        return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: non-finite input (Q, q_thresh)");
+    int pA = a->pair_a, pB = a->pair_b;
+    if (a->g1e_pair) {
+        if (pA < 0 || pB < 0 || pA >= ns || pB >= ns) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: the shell pair (pair_a, pair_b) does not exist");
+        if (pA < pB) std::swap(pA, pB);                                           // the pair list's order, then la >= lb
+        if (topo.shells[pA].l < topo.shells[pB].l) std::swap(pA, pB);
+    }
+    // ---- the rows of the per-row mode: a slice of the topology's own list, or of the density-fitted term's lists
+    const std::vector<int>* list = nullptr;
+    std::vector<int> t3[4][4][4], t2[4][4];
+    const int* rcl = a->row_class;
+    if (want_rows) {
+        if (mode == 0) {
+            for (auto& cl : topo.classes)
+                if (cl.la == rcl[0] && cl.lb == rcl[1] && cl.lc == rcl[2] && cl.ld == rcl[3] && !cl.quartets.empty()) list = &cl.quartets;
+        } else {
+            if (rcl[3] != 0 || (mode == 2 && rcl[1] != 0)) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: the empty slots of a density-fitted class hold an s shell (l = 0)");
+            df_gradient_lists(topo, xtopo, t3, t2);
+            list = mode == 1 ? &t3[rcl[0]][rcl[1]][rcl[2]] : &t2[rcl[0]][rcl[2]];
+            if (list->empty()) list = nullptr;
+        }
+        if (!list) return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: the topology has no class (" + std::to_string(rcl[0]) + " " + std::to_string(rcl[1]) +
+                                                       "|" + std::to_string(rcl[2]) + " " + std::to_string(rcl[3]) + ")");
+        const int64_t len = (int64_t)(list->size() / 4);
+        if (a->row_start < 0 || a->row_count > 4096 || a->row_start + a->row_count > len)
+            return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: slice outside the list (rows " + std::to_string(a->row_start) + " .. " +
+                                                std::to_string(a->row_start + a->row_count) + " of " + std::to_string(len) + ", at most 4096 at a time)");
+        if (device_rows && mode != 0 && !finite(a->gam, mode == 1 ? (size_t)na * nn : (size_t)na * na))
+            return fail(MQC_HIP_ERR_VALIDATION, "gradient stage: non-finite input (gam)");
+    }
+    // ---- nothing refused from here on
+    const size_t nrow = want_rows ? (size_t)a->row_count : 0;
+    if (want_rows) {
+        *a->class_length = (int64_t)(list->size() / 4);
+        std::memcpy(a->rows, list->data() + 4 * (size_t)a->row_start, sizeof(int) * 4 * nrow);
+    }
+    if (!whole && !device_rows) return MQC_HIP_OK;
+    HIP_CHECK_RET(hipSetDevice(ctx->device));
+    if ((rc = upload_topology(ctx, topo, sb.td)) != MQC_HIP_OK) return rc;
+    TopologyDev tdx{};
+    if (device_rows && mode != 0 && (rc = upload_topology(ctx, xtopo, tdx, &ctx->lane[0].aux)) != MQC_HIP_OK) return rc;
+    BatchPlan plan;
+    plan.n = n; plan.npair = topo.npair; plan.natoms = nat; plan.two_e = TWO_E_NONE;
+    plan.uhf = uhf; plan.nocc = a->n_occ; plan.nalpha = a->n_occ; plan.nbeta = a->n_beta;
+    plan_layout(plan, 1, ns, topo.lmax, false);
+    BatchView& bv = sb.bv;
+    if ((rc = carve_slot(ctx, make_slot(ctx, 0, nullptr), plan, sb.td, 1, bv)) != MQC_HIP_OK) return rc;
+    bv.nocc = a->n_occ; bv.nalpha = a->n_occ; bv.nbeta = a->n_beta; bv.exx = a->exx;
+    hipStream_t s = ctx->lane[0].stream;
+    // [g1e | pair | g2e | rows ...] gradients, [W | Dtot], Q, gam, then the lists
+    const size_t gdoubles = ((3 + nrow) * g3 + 7) & ~size_t(7);
+    const size_t gam_doubles = (device_rows && mode != 0) ? (mode == 1 ? (size_t)na * nn : (size_t)na * na) : 0;
+    const size_t lint = grad_list_ints(bv, topo) + 64;
+    static DevicePool pool;
+    char* base = (char*)pool.ensure(sizeof(double) * (gdoubles + 2 * nn + (size_t)ns * ns + gam_doubles + 8) + sizeof(int) * (lint + 4 * nrow + 64));
+    if (!base) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (gradient stage)");
+    double* d_g1e = (double*)base; double* d_pair = d_g1e + g3; double* d_g2e = d_pair + g3; double* d_rows = d_g2e + g3;
+    double* work = d_g1e + gdoubles;
+    double* d_q = work + 2 * nn;
+    double* d_gam = d_q + (((size_t)ns * ns + 7) & ~size_t(7));
+    int* d_lists = (int*)(d_gam + gam_doubles);
+    int* d_rowlist = d_lists + lint;
+    HIP_CHECK_RET(hipMemcpyAsync(bv.xyz, mol->xyz, sizeof(double) * g3, hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemsetAsync(bv.istate, 0, sizeof(int) * 4, s));
+    HIP_CHECK_RET(hipMemsetAsync(d_g1e, 0, sizeof(double) * gdoubles, s));
+    if (need_d) HIP_CHECK_RET(hipMemcpyAsync(bv.D, a->D, sizeof(double) * nn, hipMemcpyHostToDevice, s));
+    if (need_d && uhf) HIP_CHECK_RET(hipMemcpyAsync(bv.Db, a->D_beta, sizeof(double) * nn, hipMemcpyHostToDevice, s));
+    if (need_w) {
+        HIP_CHECK_RET(hipMemcpyAsync(bv.C, a->C, sizeof(double) * nn, hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipMemcpyAsync(bv.eps, a->eps, sizeof(double) * n, hipMemcpyHostToDevice, s));
+        if (uhf) {
+            HIP_CHECK_RET(hipMemcpyAsync(bv.Cb, a->C_beta, sizeof(double) * nn, hipMemcpyHostToDevice, s));
+            HIP_CHECK_RET(hipMemcpyAsync(bv.epsb, a->eps_beta, sizeof(double) * n, hipMemcpyHostToDevice, s));
+        }
+    } else {
+        // the weighted-density kernel still runs (it is a step of the stage): on zeros
+        HIP_CHECK_RET(hipMemsetAsync(bv.C, 0, sizeof(double) * nn, s));
+        HIP_CHECK_RET(hipMemsetAsync(bv.eps, 0, sizeof(double) * n, s));
+        if (uhf) { HIP_CHECK_RET(hipMemsetAsync(bv.Cb, 0, sizeof(double) * nn, s)); HIP_CHECK_RET(hipMemsetAsync(bv.epsb, 0, sizeof(double) * n, s)); }
+        bv.nocc = bv.nalpha = bv.nbeta = 0;
+    }
+    if (!need_d) {
+        HIP_CHECK_RET(hipMemsetAsync(bv.D, 0, sizeof(double) * nn, s));
+        if (uhf) HIP_CHECK_RET(hipMemsetAsync(bv.Db, 0, sizeof(double) * nn, s));
+    }
+    grad_prepare_kernels();
+    const double* Dtot = launch_grad_densities(bv, work, s);
+    size_t off = 0;
+    if (a->g1e) grad_one_electron(bv, topo, Dtot, work, d_g1e, d_lists, off, s);
+    if (a->g1e_pair) {
+        const int pr[2] = {pA, pB};
+        HIP_CHECK_RET(hipMemcpyAsync(d_lists + off, pr, sizeof(pr), hipMemcpyHostToDevice, s));
+        HIP_CHECK_RET(hipStreamSynchronize(s));                                   // pr lives on this frame
+        launch_grad1e_pairs(bv, topo.shells[pA].l, topo.shells[pB].l, d_lists + off, 1, Dtot, work, d_pair, s);
+        off += 2;
+    }
+    if (a->g2e) {
+        if (a->Q) HIP_CHECK_RET(hipMemcpyAsync(d_q, a->Q, sizeof(double) * (size_t)ns * ns, hipMemcpyHostToDevice, s));
+        if (!grad_two_electron(bv, topo, nullptr, Dtot, d_g2e, d_lists, off, a->Q ? d_q : nullptr, a->q_thresh, s, why))
+            return fail(MQC_HIP_ERR_UNSUPPORTED, why);
+    }
+    if (device_rows) {
+        HIP_CHECK_RET(hipMemcpyAsync(d_rowlist, a->rows, sizeof(int) * 4 * nrow, hipMemcpyHostToDevice, s));
+        BatchView vx = bv;
+        if (mode != 0) {
+            vx.naux = na; vx.aux = tdx;
+            HIP_CHECK_RET(hipMemcpyAsync(d_gam, a->gam, sizeof(double) * gam_doubles, hipMemcpyHostToDevice, s));
+        }
+        // one single-wave launch per row: a long slice goes round four streams of its own, which start after the uploads
+        // above and which the lane's stream waits for
+        struct Side {
+            hipStream_t st[4] = {};
+            hipEvent_t ev[5] = {};
+            int n = 0;
+            ~Side()
+            {
+                for (int k = 0; k < n; ++k) (void)hipStreamDestroy(st[k]);
+                for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+            }
+        } side;
+        if (nrow >= 64) {
+            for (auto& e : side.ev) HIP_CHECK_RET(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            for (; side.n < 4; ++side.n) HIP_CHECK_RET(hipStreamCreateWithFlags(&side.st[side.n], hipStreamNonBlocking));
+            HIP_CHECK_RET(hipEventRecord(side.ev[4], s));
+            for (int k = 0; k < 4; ++k) HIP_CHECK_RET(hipStreamWaitEvent(side.st[k], side.ev[4], 0));
+        }
+        for (size_t r = 0; r < nrow; ++r)
+            if (!launch_eri_grad_rows(vx, rcl[0], rcl[1], rcl[2], rcl[3], d_rowlist + 4 * r, 1, mode == 0 ? Dtot : nullptr,
+                                      mode == 0 && uhf ? bv.Db : nullptr, d_rows + r * g3, mode, mode == 0 ? nullptr : d_gam,
+                                      side.n ? side.st[r & 3] : s, why)) {
+                (void)hipDeviceSynchronize();
+                return fail(MQC_HIP_ERR_UNSUPPORTED, why);
+            }
+        for (int k = 0; k < side.n; ++k) {
+            HIP_CHECK_RET(hipEventRecord(side.ev[k], side.st[k]));
+            HIP_CHECK_RET(hipStreamWaitEvent(s, side.ev[k], 0));
+        }
+        if ((rc = sync_and_check(s)) != MQC_HIP_OK) return rc;          // before the side streams go
+    }
+    if ((rc = sync_and_check(s)) != MQC_HIP_OK) return rc;
+    if (a->w) HIP_CHECK_RET(hipMemcpy(a->w, work, sizeof(double) * nn, hipMemcpyDeviceToHost));
+    if (a->g1e) HIP_CHECK_RET(hipMemcpy(a->g1e, d_g1e, sizeof(double) * g3, hipMemcpyDeviceToHost));
+    if (a->g1e_pair) HIP_CHECK_RET(hipMemcpy(a->g1e_pair, d_pair, sizeof(double) * g3, hipMemcpyDeviceToHost));
+    if (a->g2e) HIP_CHECK_RET(hipMemcpy(a->g2e, d_g2e, sizeof(double) * g3, hipMemcpyDeviceToHost));
+    if (device_rows) HIP_CHECK_RET(hipMemcpy(a->g_rows, d_rows, sizeof(double) * nrow * g3, hipMemcpyDeviceToHost));
     return MQC_HIP_OK;
 }
 

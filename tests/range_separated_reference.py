@@ -37,7 +37,12 @@ PW_FZ20 = 1.709921          # f''(0) as the original PW92 parameter set rounds i
 # ------------------------------------------------------------------ attenuated integrals
 def boys(nmax: int, T: np.ndarray) -> np.ndarray:
     """F_0..F_nmax(T) -> [nmax+1, ...]; the closed form through the regularised incomplete gamma function, a short
-    Taylor series near T = 0."""
+    Taylor series near T = 0.  A complex T = T0 + i eps (complex-step differentiation, eps ~ 1e-30) takes the first
+    order of its Taylor series, F_n(T0) - i eps F_{n+1}(T0), which is all such a step sees."""
+    if np.iscomplexobj(T):
+        T = np.asarray(T)
+        F = boys(nmax + 1, T.real)
+        return F[:-1] - 1j * T.imag * F[1:]
     T = np.asarray(T, dtype=np.float64)
     out = np.empty((nmax + 1,) + T.shape)
     small = T < 1e-3
@@ -116,11 +121,11 @@ class _Pair:
         P = (a[:, None] * ra + b[:, None] * rb) / p[:, None]
         mu = a * b / p
         self.p, self.P = p, P
-        self.k = np.repeat(ca, len(eb)) * np.tile(cb, len(ea)) * np.exp(-mu * float(np.sum((ra - rb) ** 2)))
+        self.k = np.repeat(ca, len(eb)) * np.tile(cb, len(ea)) * np.exp(-mu * np.sum((ra - rb) ** 2))
         self.la, self.lb = la, lb
         E = [_e1d(la, lb, P[:, d] - ra[d], P[:, d] - rb[d], 0.5 / p) for d in range(3)]
         H = _herm(la + lb)
-        self.E = np.zeros((len(_cart(la)), len(_cart(lb)), len(H), len(p)))
+        self.E = np.zeros((len(_cart(la)), len(_cart(lb)), len(H), len(p)), dtype=P.dtype)      # complex centres: complex tables
         for ia, (ax, ay, az) in enumerate(_cart(la)):
             for ib, (bx, by, bz) in enumerate(_cart(lb)):
                 for ih, (t, u, v) in enumerate(H):
@@ -149,7 +154,7 @@ def shell_quartet(mol, pab: _Pair, pcd: _Pair, omega2: float | None):
     L1, L2 = pab.la + pab.lb, pcd.la + pcd.lb
     R = hermite_r(L1 + L2, alpha, PQ[..., 0], PQ[..., 1], PQ[..., 2], scale * pref)
     H1, H2 = _herm(L1), _herm(L2)
-    Rt = np.empty((len(H1), len(H2)) + alpha.shape)
+    Rt = np.empty((len(H1), len(H2)) + alpha.shape, dtype=np.result_type(PQ, pref))
     for i, (t, u, v) in enumerate(H1):
         for j, (tt, uu, vv) in enumerate(H2):
             Rt[i, j] = (-1) ** (tt + uu + vv) * R[(t + tt, u + uu, v + vv)]

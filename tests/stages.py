@@ -1,5 +1,6 @@
 """Stage-level entry points of the C ABI (mqc_hip_int1e, _eri_packed, _eri_packed_attenuated, _jk_incore, _jk_direct,
-_coulomb_batch, _xc_batch, _df_jk_batch, _df_fit_batch, _jk_tensor_layout, _jk_incore_batch, _syev, _diis_coefficients) as numpy-in / numpy-out functions.  They run the same kernels the SCF
+_coulomb_batch, _xc_batch, _df_jk_batch, _df_fit_batch, _jk_tensor_layout, _jk_incore_batch, _gradient_stage, _syev,
+_diis_coefficients) as numpy-in / numpy-out functions.  They run the same kernels the SCF
 driver launches and exist so that each row of the hot-path table can be parity-tested alone.
 Test infrastructure: a ctypes helper for tests/, not part of the product package."""
 from __future__ import annotations
@@ -187,4 +188,80 @@ def unpack_pairs(P: np.ndarray) -> np.ndarray:
     out = np.zeros(P.shape[:-1] + (n, n), dtype=P.dtype)
     out[..., ii, jj] = P
     out[..., jj, ii] = P
+    return out
+
+
+GRAD_EXACT, GRAD_DF3C, GRAD_DF2C = 0, 1, 2
+
+
+def gradient_rows(basis_set: str, fragment: PhysicalFragment, cls, start: int = 0, count: int = 1, mode: int = GRAD_EXACT,
+                  aux_basis_set: str | None = None):
+    """The host-only half of mqc_hip_gradient_stage (no context, no device): rows [start, start + count) of the list of
+    class cls = (la, lb, lc, ld) as the engine holds it, and the length of that list.  count = None: the whole list."""
+    m = _marshal(basis_set, fragment)
+    x = _marshal(aux_basis_set, fragment) if aux_basis_set else None
+    lib = capi.load_library()
+
+    def call(first, cnt):
+        a = capi.GradientStage()
+        a.mode = mode
+        a.row_class[:] = [int(v) for v in cls]
+        a.row_start, a.row_count = first, cnt
+        rows = np.full((cnt, 4), -1, dtype=np.int32)
+        length = C.c_int64(-1)
+        a.rows = rows.ctypes.data_as(capi.c_int32_p)
+        a.class_length = C.pointer(length)
+        capi.check(lib.mqc_hip_gradient_stage(None, C.byref(m.mol), C.byref(m.bas), C.byref(x.bas) if x else None, C.byref(a)))
+        return rows, length.value
+    if count is not None:
+        return call(start, count)
+    out, length = call(0, 1)
+    parts = [call(k, min(4096, length - k))[0] for k in range(0, length, 4096)]
+    return np.concatenate(parts), length
+
+
+def gradient_stage(basis_set: str, fragment: PhysicalFragment, D=None, D_beta=None, C_mo=None, eps=None, C_beta=None, eps_beta=None,
+                   n_occ: int = 0, n_beta: int = 0, exx: float = 1.0, want=(), pair=None, Q=None, q_thresh: float = 0.0,
+                   cls=None, start: int = 0, count: int = 0, mode: int = GRAD_EXACT, aux_basis_set: str | None = None, gam=None,
+                   context=True, out=None):
+    """mqc_hip_gradient_stage for one fragment.  want: any of "w", "g1e", "g2e"; pair = (A, B) adds "g1e_pair"; cls with
+    count > 0 adds "rows" (count, 4), "class_length" and "g_rows" (count, natoms, 3).  Every output starts as NaN (rows as
+    -1) and comes back so wherever the engine did not write; a caller's `out` dict receives them even when the call raises."""
+    m = _marshal(basis_set, fragment)
+    x = _marshal(aux_basis_set, fragment) if aux_basis_set else None
+    n, nat = m.fb.nao, len(fragment.element_numbers)
+    keep = []
+
+    def dbl(v):
+        if v is None:
+            return None
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        keep.append(v)
+        return capi.dptr(v)
+    a = capi.GradientStage()
+    a.D, a.D_beta, a.C, a.eps, a.C_beta, a.eps_beta = dbl(D), dbl(D_beta), dbl(C_mo), dbl(eps), dbl(C_beta), dbl(eps_beta)
+    a.n_occ, a.n_beta, a.exx = int(n_occ), int(n_beta), float(exx)
+    a.Q, a.q_thresh, a.gam, a.mode = dbl(Q), float(q_thresh), dbl(gam), int(mode)
+    out = {} if out is None else out
+    for name, shape in (("w", (n, n)), ("g1e", (nat, 3)), ("g2e", (nat, 3))):
+        if name in want:
+            out[name] = np.full(shape, np.nan)
+            setattr(a, name, capi.dptr(out[name]))
+    a.pair_a = a.pair_b = -1
+    if pair is not None:
+        a.pair_a, a.pair_b = int(pair[0]), int(pair[1])
+        out["g1e_pair"] = np.full((nat, 3), np.nan)
+        a.g1e_pair = capi.dptr(out["g1e_pair"])
+    length = C.c_int64(-1)
+    if cls is not None:
+        a.row_class[:] = [int(v) for v in cls]
+        a.row_start, a.row_count = int(start), int(count)
+        out["rows"] = np.full((max(count, 0), 4), -1, dtype=np.int32)
+        out["g_rows"] = np.full((max(count, 0), nat, 3), np.nan)
+        a.rows = out["rows"].ctypes.data_as(capi.c_int32_p)
+        a.g_rows = capi.dptr(out["g_rows"])
+        a.class_length = C.pointer(length)
+    capi.check(capi.load_library().mqc_hip_gradient_stage(capi.get_context() if context else None, C.byref(m.mol), C.byref(m.bas),
+                                                          C.byref(x.bas) if x else None, C.byref(a)))
+    out["class_length"] = length.value
     return out
