@@ -387,6 +387,55 @@ int mqc_hip_rimp2_batch(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip
                         int32_t frozen_core,
                         double *e_os /* [n] */, double *e_ss /* [n] */, int32_t *mp2_done /* [n] */);
 
+/* ---- static dipole polarizabilities (CPHF) ---------------------------------------------- */
+/* Settings of the coupled-perturbed Hartree-Fock solve: a fragment is converged when the largest element, over the three
+ * directions, of the residual Delta o U + G(U) + b is at most tol; max_iter bounds its conjugate-gradient iterations. */
+typedef struct {
+    double tol;                      /* > 0 and finite; default 1e-8 */
+    int32_t max_iter;                /* >= 1; default 64 */
+} mqc_hip_cphf_options_t;
+void mqc_hip_default_cphf_options(mqc_hip_cphf_options_t *o);   /* 1e-8, 64 */
+
+/* Static dipole polarizabilities of closed-shell Hartree-Fock fragments.  The SCF part IS mqc_hip_scf_run_batch --
+ * grouping by topology, chunking under MQC_HIP_HBM_BUDGET_GB, deferred groups, per-fragment failures in results[i],
+ * results[i] unchanged in meaning -- on the in-core path with the SQUARE tensor at every batch size (the chunks are sized
+ * for it), and after the SCF loop of a chunk, while its tensor, orbitals C and energies e are still on the device, the
+ * stage of kern_cphf.hip solves, per direction d = x, y, z with H(F) = H + sum_d F_d r_d (r_d the electron position
+ * integrals about the coordinate origin), b = C_v^T r_d C_o and Delta_ai = e_a - e_i,
+ *     Delta o U + G(U) = -b,   G(U) = C_v^T [J(D1) - K(D1)/2] C_o,   D1 = 2 (C_v U C_o^T + C_o U^T C_v^T),
+ *     alpha_cd = -d2E / dF_c dF_d = -tr(D1_d r_c)                      (atomic units, the laboratory frame)
+ * by conjugate gradients preconditioned with 1/Delta; the three directions of all fragments of the chunk advance
+ * together, one three-density J/K launch per iteration (MQC_HIP_CPHF_MULTI=0: three single-density launches), finished
+ * fragments skipped.  For every fragment whose SCF converged and whose solve converged:
+ *     alpha_done[i] = 1, alpha[9 i + 3 c + d] written, cphf_iterations[i] = its iterations;
+ * every other fragment gets alpha_done[i] = 0 and zeros.  A solve that meets a direction with p.Ap <= 0 ends that
+ * fragment with "the RHF solution is unstable" in results[i]; one that reaches max_iter ends it with an error naming the
+ * CPHF; the other fragments are unaffected.  Point charges and h_extra are legal: the orbitals carry the field.
+ * MQC_HIP_ERR_UNSUPPORTED (the refused fragments run no SCF): density fitting, eri_mode = direct or n_ao > 116 (no
+ * tensor to stream), a functional (CPKS needs the second derivatives of the XC kernel), an unrestricted run
+ * (opts->unrestricted, multiplicity != 1, an odd electron count), want_gradient.  MQC_HIP_ERR_VALIDATION: a NULL cphf or
+ * output array, tol <= 0 or not finite, max_iter < 1.  The plain entry's own refusals keep their text.
+ * (Added without an ABI bump: no struct changed.) */
+int mqc_hip_polarizability_batch(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip_molecule_t *mols,
+                                 const mqc_hip_basis_t *orbitals, const mqc_hip_scf_options_t *opts,
+                                 const mqc_hip_cphf_options_t *cphf, mqc_hip_scf_result_t *results,
+                                 double *alpha /* [n][9], row-major */, int32_t *cphf_iterations /* [n] */,
+                                 int32_t *alpha_done /* [n] */);
+
+/* The multi-density J/K stage of a CPHF iteration alone, on given SQUARE tensors [n_fragments][npair*npair] (packed
+ * pairs mu >= nu, index mu (mu + 1) / 2 + nu) and n_densities = 1..3 symmetric densities per fragment
+ * D [n_fragments][n_densities][n_ao*n_ao]: J and K in the layout of D from ONE pass over the tensor (MQC_HIP_CPHF_MULTI=0:
+ * one launch of the single-density stream per density).  J and K are poisoned (NaN) before the launch; an element of a
+ * fragment marked finished (done[f] != 0; done may be NULL) comes back as the poison or as zero, never as anything
+ * else; the pool bytes next to J and K are compared before and after.  route receives the instance chosen:
+ * "multi<3,KCH,lds|global,lds|mem,NW,MAXU>" (K accumulated in LDS or global memory, packed densities in LDS or memory,
+ * waves per workgroup, register chunks of a row), or "single:" and the single-density instance.
+ * MQC_HIP_ERR_VALIDATION: null pointers, n_fragments < 1, n_ao outside 1..116, n_densities outside 1..3.
+ * (Added without an ABI bump: no struct changed.) */
+int mqc_hip_jk_multi_batch(mqc_hip_context *ctx, int64_t n_fragments, int32_t n_ao, int32_t n_densities,
+                           const double *tensor, const double *D, const int32_t *done, double *J, double *K,
+                           char *route, int32_t route_len);
+
 /* ---- C-PCM implicit solvation -------------------------------------------------------- */
 /* The SCF in a conductor-like polarisable continuum (the reference's cuestPCMPotentialCompute term: "C-PCM charges +
  * V_pcm", F = H + J - K + V_xc + V_pcm, mqc_cuest_integrals.f90:974-1366).  The discretisation is this engine's own

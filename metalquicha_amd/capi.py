@@ -69,6 +69,10 @@ class PcmOptions(C.Structure):
                 ("radii_by_z", c_double_p)]
 
 
+class CphfOptions(C.Structure):
+    _fields_ = [("tol", C.c_double), ("max_iter", C.c_int32)]
+
+
 class GradientStage(C.Structure):
     _fields_ = [("D", c_double_p), ("D_beta", c_double_p), ("C", c_double_p), ("eps", c_double_p), ("C_beta", c_double_p),
                 ("eps_beta", c_double_p), ("n_occ", C.c_int32), ("n_beta", C.c_int32), ("exx", C.c_double),
@@ -103,6 +107,7 @@ DECLARED_SYMBOLS = [
     "mqc_hip_jk_tensor_layout", "mqc_hip_jk_incore_batch",
     "mqc_hip_default_pcm_options", "mqc_hip_scf_pcm_batch", "mqc_hip_pcm_stage",
     "mqc_hip_gradient_stage",
+    "mqc_hip_default_cphf_options", "mqc_hip_polarizability_batch", "mqc_hip_jk_multi_batch",
 ]
 
 _lib = None
@@ -146,6 +151,12 @@ def load_library():
     lib.mqc_hip_pcm_stage.argtypes = [C.c_void_p, C.POINTER(Molecule), C.POINTER(Basis), C.POINTER(PcmOptions), c_double_p, C.c_int32,
                                       C.c_int64, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                       c_double_p]
+    lib.mqc_hip_default_cphf_options.argtypes = [C.POINTER(CphfOptions)]
+    lib.mqc_hip_default_cphf_options.restype = None
+    lib.mqc_hip_polarizability_batch.argtypes = [C.c_void_p, C.c_int64, C.POINTER(Molecule), C.POINTER(Basis), C.POINTER(ScfOptions),
+                                                 C.POINTER(CphfOptions), C.POINTER(ScfResult), c_double_p, c_int32_p, c_int32_p]
+    lib.mqc_hip_jk_multi_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, c_double_p, c_double_p, c_int32_p, c_double_p,
+                                           c_double_p, C.c_char_p, C.c_int32]
     lib.mqc_hip_gradient_stage.argtypes = [C.c_void_p, C.POINTER(Molecule), C.POINTER(Basis), C.POINTER(Basis), C.POINTER(GradientStage)]
     lib.mqc_hip_int1e.argtypes = [C.c_void_p, C.POINTER(Molecule), C.POINTER(Basis), c_double_p, c_double_p, c_double_p]
     lib.mqc_hip_eri_packed.argtypes = [C.c_void_p, C.POINTER(Molecule), C.POINTER(Basis), C.c_double, c_double_p]

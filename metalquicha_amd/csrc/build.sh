@@ -6,7 +6,7 @@ OUT=../libmqc_hip.so
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Wno-unused-result -Wno-pass-failed"
 mkdir -p _obj
 [ -f lebedev_tables.inc ] || python3 gen_lebedev.py
-HDRS="md_integrals.hpp engine.hpp driver.hpp eri_kernels.hpp hermite_records.hpp pcm_cavity.hpp ../../include/mqc_hip.h"
+HDRS="md_integrals.hpp engine.hpp driver.hpp jk_helpers.hpp eri_kernels.hpp hermite_records.hpp pcm_cavity.hpp ../../include/mqc_hip.h"
 stale() { # obj src
   [ ! -f "$1" ] && return 0
   [ "$2" -nt "$1" ] && return 0
@@ -23,7 +23,7 @@ for g in 15 27 18 6 26 12 4 24 13 5 25 14 10 2 22 11 3 23 9 19 1 21 8 0 20 7 16 
 done
 # kern_scf_wide.hip is kern_scf.hip compiled with 512 threads per fragment
 [ kern_scf.hip -nt kern_scf_wide.hip ] && touch kern_scf_wide.hip
-for f in kern_int1e.hip kern_eri.hip kern_eri_general.hip kern_grad.hip kern_grad_pc.hip kern_esp.hip kern_fock.hip kern_scf.hip kern_scf_wide.hip kern_xc.hip kern_df.hip kern_mp2.hip kern_pcm.hip host_setup.cpp grid_host.cpp engine.cpp stage_entries.cpp; do
+for f in kern_int1e.hip kern_eri.hip kern_eri_general.hip kern_grad.hip kern_grad_pc.hip kern_esp.hip kern_fock.hip kern_scf.hip kern_scf_wide.hip kern_xc.hip kern_df.hip kern_mp2.hip kern_pcm.hip kern_cphf.hip host_setup.cpp grid_host.cpp engine.cpp stage_entries.cpp; do
   o=_obj/${f%.*}.o
   if stale "$o" "$f" || { [ "$f" = kern_eri.hip ] && { [ eri_dispatch.hpp -nt "$o" ] || [ eri_plan.hpp -nt "$o" ]; }; }; then run hipcc $FLAGS -x hip -c "$f" -o "$o"; fi
 done

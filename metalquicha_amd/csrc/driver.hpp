@@ -60,6 +60,8 @@ struct FragmentIO {
     int32_t* mp2_done;                 // and the done flag go
     const pcm::Cavity* cavity;         // mqc_hip_scf_pcm_batch: the fragment's tesserae, and where E_pcm goes
     double* e_pcm;
+    double* alpha;                     // mqc_hip_polarizability_batch: where the tensor [9], the iterations of the solve
+    int32_t *cphf_iter, *alpha_done;   // and the done flag go
 };
 
 // What the stages of one batch call share besides the plan: the fragments, ordered by compactness, the device topology
@@ -74,6 +76,7 @@ struct Batch {
     bool any_d0 = false;                             // some fragment brought a starting density
     int mp2_frozen = -1;                             // mqc_hip_rimp2_batch only: the frozen orbitals of this topology (>= 0)
     double pcm_f = -1.0;                             // mqc_hip_scf_pcm_batch only: (epsilon - 1) / epsilon (>= 0)
+    const mqc_hip_cphf_options_t* cphf = nullptr;    // mqc_hip_polarizability_batch only: the settings of the solve
     TopologyDev td{}, tdx{};
     GridDev grid;
     Stats stats;

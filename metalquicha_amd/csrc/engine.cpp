@@ -39,6 +39,11 @@ size_t gradpc_record_doubles(const Topology& topo);
 // (the caller joins the stream); device bytes per fragment of the stage
 bool launch_rimp2(const BatchView& bv, int n_frozen, double* h_out, hipStream_t s, std::string& err);
 size_t rimp2_fragment_bytes(int n, int nocc, int naux, int n_frozen);
+// kern_cphf.hip: the CPHF solve of a converged in-core chunk with the square tensor -- alpha [nfrag][9], iterations and
+// CPHF_* status per fragment, complete on return (h_counter: the slot's pinned word); device bytes per fragment
+bool launch_cphf(const BatchView& bv, const Topology& topo, double tol, int max_iter, double* h_alpha, int* h_iter, int* h_status,
+                 int* h_counter, hipStream_t s, std::string& err);
+size_t cphf_fragment_bytes(int n, int nocc, int nmo);
 
 int stage_check(const char* stage)
 {
@@ -760,7 +765,8 @@ static void embedding_and_mulliken(const Topology& topo, const double* D, const 
 
 // what a chunk's results are made of, read back once after its SCF loop
 struct ChunkOut {
-    std::vector<double> scal, eps, epsb, dip, grad, pcgrad, mp2, pcm;
+    std::vector<double> scal, eps, epsb, dip, grad, pcgrad, mp2, pcm, alpha;
+    std::vector<int> cphf_iter, cphf_status;
     std::vector<double> D, U, S;      // total density, embedding operator, overlap: only where a caller reads them
     std::vector<double> Da, Db;       // spin densities of an unrestricted chunk, where a caller asked for them
     std::vector<int> ist;
@@ -839,6 +845,18 @@ static int write_result(const BatchPlan& plan, Batch& b, const Job& job, const C
         *io.mp2_ss = o.mp2[2 * f + 1];
         *io.mp2_done = 1;
     }
+    if (b.cphf && conv && !r->has_error) {
+        // alpha belongs to a converged solve on converged orbitals; everything else keeps the entry's zeros
+        const int status = o.cphf_status[f];
+        *io.cphf_iter = o.cphf_iter[f];
+        if (status == CPHF_CONVERGED) {
+            std::memcpy(io.alpha, &o.alpha[(size_t)9 * f], sizeof(double) * 9);
+            *io.alpha_done = 1;
+        } else if (status == CPHF_UNSTABLE)
+            fill_error(r, "CPHF: the RHF solution is unstable (a search direction with p.Ap <= 0)");
+        else
+            fill_error(r, "CPHF did not converge in " + std::to_string(o.cphf_iter[f]) + " iterations");
+    }
     b.stats.scf_iterations_total += r->iterations;
     return MQC_HIP_OK;
 }
@@ -897,6 +915,15 @@ static int fetch_results(const BatchPlan& plan, Batch& b, const Slot& sl, Job& j
         if (!launch_rimp2(bv, b.mp2_frozen, o.mp2.data(), s, merr)) return fail(MQC_HIP_ERR_DEVICE, merr);
         int mrc = stage_check("RI-MP2");
         if (mrc != MQC_HIP_OK) return mrc;
+    }
+    // ---- CPHF (mqc_hip_polarizability_batch): the square tensor, the orbitals and their energies are still in place
+    if (b.cphf) {
+        o.alpha.assign((size_t)nf * 9, 0.0); o.cphf_iter.assign(nf, 0); o.cphf_status.assign(nf, CPHF_NOT_SOLVED);
+        std::string cerr;
+        if (!launch_cphf(bv, topo, b.cphf->tol, b.cphf->max_iter, o.alpha.data(), o.cphf_iter.data(), o.cphf_status.data(), sl.h_counter, s, cerr))
+            return fail(MQC_HIP_ERR_DEVICE, cerr);
+        int crc = stage_check("CPHF");
+        if (crc != MQC_HIP_OK) return crc;
     }
     launch_dipole(bv, topo, s);
     if (plan.uhf) {
@@ -959,6 +986,7 @@ struct Work {
     bool any_d0 = false;                 // mqc_hip_scf_run_batch_restart: some fragment of the group brought a starting density
     int mp2_frozen = -1;                 // mqc_hip_rimp2_batch only: frozen orbitals of the topology (>= 0)
     double pcm_f = -1.0;                 // mqc_hip_scf_pcm_batch only: (epsilon - 1) / epsilon, and the fragments' cavities
+    const mqc_hip_cphf_options_t* cphf = nullptr;   // mqc_hip_polarizability_batch only: the settings of the solve
     std::vector<pcm::Cavity> cavities;   // (reserved up front: the fragment records point into it)
     std::shared_ptr<AtomicGuess> guess;
     // deferred small groups (schedule_groups): the largest group's batch opens the gate, the others wait at it
@@ -979,11 +1007,13 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
     const int ntot = (int)w.frags.size();
     Batch b{topo, aux, opts, w.guess.get()};
     b.embedded_entry = w.embedded_entry; b.any_d0 = w.any_d0; b.mp2_frozen = w.mp2_frozen; b.pcm_f = w.pcm_f;
+    b.cphf = w.cphf;
     b.gate = w.opens;
     if (w.waits && lane == 1) b.chain_side = 1;      // deferred on lane 1: its third side stream stays idle (schedule_groups)
     // whichever way this batch ends (refusal, error return, no chunk that reaches scf_loop), the waiting groups go on
     struct GateOpener { GroupGate* g; ~GateOpener() { if (g) g->open(); } } const opener{w.opens};
     BatchPlan plan;
+    plan.square_only = w.cphf != nullptr;      // the multi-density stream reads the square tensor: the chunks are sized for it
     // external point charges (FMO / EE-MBE embedding) and h_extra: the same in every fragment of the group (its key says so)
     plan.npc = ntot > 0 ? w.frags[0].mol->n_point_charges : 0;
     plan.hx = ntot > 0 && w.frags[0].mol->h_extra != nullptr;
@@ -1038,6 +1068,8 @@ static int run_batch(mqc_hip_context* ctx, const Work& w, const mqc_hip_scf_opti
     if (opts.want_gradient && plan.npc > 0) per_frag += sizeof(double) * (gradpc_record_doubles(topo) + 3 * (size_t)plan.npc);
     // RI-MP2: the transformed tensor and the pair partials, from the stage's own pool
     if (w.mp2_frozen >= 0) per_frag += rimp2_fragment_bytes(plan.n, plan.nocc, plan.naux, w.mp2_frozen);
+    // CPHF: first-order densities with their J and K, dipole matrices and the solver's vectors, from the stage's own pool
+    if (w.cphf) per_frag += cphf_fragment_bytes(plan.n, plan.nocc, plan.n);
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
     // what the lanes' pools hold is free to this batch (the counters' few hundred bytes are not counted)
@@ -1413,6 +1445,9 @@ struct BatchExtras {            // what the plain batch entry does not have
     const mqc_hip_pcm_options_t* pcm = nullptr;     // mqc_hip_scf_pcm_batch: the settings (checked) and the [n] outputs
     double* e_pcm = nullptr;
     int32_t* n_tesserae = nullptr;
+    const mqc_hip_cphf_options_t* cphf = nullptr;   // mqc_hip_polarizability_batch: the settings (checked) and the [n] outputs
+    double* alpha = nullptr;
+    int32_t *cphf_iter = nullptr, *alpha_done = nullptr;
 };
 
 // frozen-core orbitals of a topology: per real atom 0 for Z <= 2, 1 for Z = 3-10, 5 for Z = 11-18, 9 for Z = 19-36
@@ -1515,6 +1550,14 @@ static int admit_group(const BatchCall& c, const BatchExtras& extras, const std:
         if (w.mp2_frozen >= nocc)
             return refuse_group(MQC_HIP_ERR_VALIDATION, "RI-MP2: the frozen core (" + std::to_string(w.mp2_frozen) + " orbitals) leaves no active occupied orbital of " + std::to_string(nocc));
     }
+    if (extras.cphf) {
+        // closed shells on the in-core path only: a refused group runs no SCF
+        if (uhf)
+            return refuse_group(MQC_HIP_ERR_UNSUPPORTED, "polarizabilities are built for closed-shell restricted references: the unrestricted CPHF (open shells, multiplicity != 1, odd electron counts) is not built");
+        if (!incore_supported(w.topo->nao) || w.topo->nao > 116)
+            return refuse_group(MQC_HIP_ERR_UNSUPPORTED, "polarizabilities stream the in-core ERI tensor (n_ao <= 116): a fragment of " + std::to_string(w.topo->nao) + " functions has no tensor to stream");
+        w.cphf = extras.cphf;
+    }
     w.embedded_entry = extras.embedded_entry;
     // supplied densities: their size follows from the run's spin treatment; one with a non-finite entry fails its own
     // fragment and nothing else
@@ -1547,6 +1590,7 @@ static int admit_group(const BatchCall& c, const BatchExtras& extras, const std:
         if (extras.initial_density) io.d0 = extras.initial_density[i];
         if (extras.spin_densities_out) io.spin_out = extras.spin_densities_out[i];
         if (extras.mp2) { io.mp2_os = extras.e_os + i; io.mp2_ss = extras.e_ss + i; io.mp2_done = extras.mp2_done + i; }
+        if (extras.cphf) { io.alpha = extras.alpha + 9 * i; io.cphf_iter = extras.cphf_iter + i; io.alpha_done = extras.alpha_done + i; }
         bool finite = true;
         if (io.d0) for (size_t k = 0; k < cnt && finite; ++k) finite = std::isfinite(io.d0[k]);
         if (!finite) {
@@ -1726,6 +1770,43 @@ int mqc_hip_rimp2_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molec
     extras.frozen_core = frozen_core != 0;
     extras.e_os = e_os; extras.e_ss = e_ss; extras.mp2_done = mp2_done;
     return scf_run_batch_impl(ctx, nfrag, mols, orbitals, auxes, opts, results, extras);
+}
+
+void mqc_hip_default_cphf_options(mqc_hip_cphf_options_t* o)
+{
+    if (!o) return;
+    o->tol = 1.0e-8;
+    o->max_iter = 64;
+}
+
+int mqc_hip_polarizability_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols, const mqc_hip_basis_t* orbitals,
+                                 const mqc_hip_scf_options_t* opts, const mqc_hip_cphf_options_t* cphf, mqc_hip_scf_result_t* results,
+                                 double* alpha, int32_t* cphf_iterations, int32_t* alpha_done)
+{
+    if (!opts || !cphf) return fail(MQC_HIP_ERR_VALIDATION, "null argument");
+    if (nfrag > 0 && (!alpha || !cphf_iterations || !alpha_done))
+        return fail(MQC_HIP_ERR_VALIDATION, "polarizability: alpha, cphf_iterations and alpha_done must not be NULL");
+    for (int64_t i = 0; i < nfrag; ++i) { cphf_iterations[i] = 0; alpha_done[i] = 0; for (int k = 0; k < 9; ++k) alpha[9 * i + k] = 0.0; }
+    // what the whole call refuses: no fragment runs an SCF
+    std::string why;
+    int code = MQC_HIP_ERR_UNSUPPORTED;
+    if (!std::isfinite(cphf->tol) || !(cphf->tol > 0.0)) { why = "CPHF: tol must be positive and finite"; code = MQC_HIP_ERR_VALIDATION; }
+    else if (cphf->max_iter < 1) { why = "CPHF: max_iter must be at least 1"; code = MQC_HIP_ERR_VALIDATION; }
+    else if (opts->density_fitting) why = "polarizabilities stream the exact in-core ERI tensor: the density-fitted CPHF is not built";
+    else if (opts->eri_mode == MQC_HIP_ERI_DIRECT) why = "polarizabilities stream the in-core ERI tensor: the direct path (eri_mode = direct) keeps no tensor to stream";
+    else if (opts->functional[0] != '\0') why = "polarizabilities of a Kohn-Sham reference (CPKS) need the second derivatives of the XC kernel, which are not built";
+    else if (opts->unrestricted) why = "polarizabilities are built for closed-shell restricted references: the unrestricted CPHF is not built";
+    else if (opts->want_gradient) why = "polarizability derivatives are not built: the entry takes no want_gradient";
+    if (!why.empty()) {
+        if (results)
+            for (int64_t i = 0; i < nfrag; ++i) { init_result(&results[i]); fill_error(&results[i], why); }
+        return fail(code, why);
+    }
+    mqc_hip_scf_options_t o = *opts;
+    o.eri_mode = MQC_HIP_ERI_INCORE;
+    BatchExtras extras;
+    extras.cphf = cphf; extras.alpha = alpha; extras.cphf_iter = cphf_iterations; extras.alpha_done = alpha_done;
+    return scf_run_batch_impl(ctx, nfrag, mols, orbitals, nullptr, &o, results, extras);
 }
 
 void mqc_hip_default_pcm_options(mqc_hip_pcm_options_t* p)

@@ -286,6 +286,8 @@ struct BatchPlan {
                                        // TWO_E_NONE: stage-level calls without two-electron work
     int naux = 0;
     bool eri_tri = false;              // in-core tensor in the triangular block layout, for every chunk of the batch
+    bool square_only = false;          // the batch's consumers read the square tensor (the multi-density J/K stream of the
+                                       // polarizability entry): plan_layout then never picks the triangle
     int npc = 0;                       // external point charges per fragment
     bool hx = false;                   // the caller's h_extra matrices
     int npts = 0, rad_pt = 0;          // quadrature points per fragment, points per tile of the radial cache
@@ -415,6 +417,20 @@ struct JkRoute {
     int grid_x;
 };
 JkRoute launch_jk_incore(const BatchView& bv, bool only_active, hipStream_t s);
+// The three-density stream over the square tensor (kern_cphf.hip, jk_multi_kernel): J and K of nd <= 3 symmetric
+// densities, direction-major [3][nfrag][n * n] (the densities beyond nd are zeroed), in one pass over the tensor.  The
+// instance it chose: multi<3,KCH,lds|global,lds|mem,NW,MAXU> (K accumulated in LDS or in global memory, packed densities
+// in LDS or read from memory).  false with err: no tensor in the square layout, or no memory for the packed densities
+struct JkMultiRoute {
+    int kch, nw, maxu, grid_x;
+    bool klds, dplds;
+};
+bool launch_jk_multi(const BatchView& bv, int nd, double* D, double* J, double* K, bool only_active, hipStream_t s, JkMultiRoute* route,
+                     std::string& err);
+std::string jk_multi_route_name(const JkMultiRoute& r);
+// how the solve of a fragment ended (kern_cphf.hip, launch_cphf)
+enum : int { CPHF_NOT_SOLVED = 0, CPHF_CONVERGED = 1, CPHF_NOT_CONVERGED = 2, CPHF_UNSTABLE = 3 };
+bool cphf_multi_on();                  // MQC_HIP_CPHF_MULTI=0: three launches of the single-density stream instead
 // K <- exx K + exx_lr K_lr for every fragment not yet done (range-separated hybrids, before the SCF step)
 void launch_exchange_fold(const BatchView& bv, double* K, const double* Klr, double exx, double exx_lr, hipStream_t s);
 void launch_direct_setup(const BatchView& bv, const Topology& topo, hipStream_t s);

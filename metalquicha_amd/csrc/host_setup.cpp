@@ -390,7 +390,7 @@ bool jk_tri_layout(int n, int np, int nfrag, bool uhf)
 
 void plan_layout(BatchPlan& p, int ntot, int nshell, int lmax, bool rad_cache)
 {
-    p.eri_tri = p.two_e == TWO_E_INCORE && jk_tri_layout(p.n, p.npair, ntot, p.uhf);
+    p.eri_tri = p.two_e == TWO_E_INCORE && !p.square_only && jk_tri_layout(p.n, p.npair, ntot, p.uhf);
     // radial cache of the quadrature: 2 doubles per shell and (padded) grid point; point buffer of the split quadrature
     // (n <= 96, s-f shells, 32-point tiles): 4 doubles per padded grid point
     p.rad_pt = xc_tile_points(p.n);

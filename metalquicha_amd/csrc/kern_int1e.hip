@@ -258,7 +258,9 @@ static void launch_class(const BatchView& bv, const std::vector<int>& list, int*
 // (system_compute_dipole, mqc_cuest_integrals.f90:1443-1521: mu = sum_A Z_A (R_A - O) - sum_uv D_uv <u|r - O|v>;
 // the shift to the centre of nuclear charge O is applied on the host with tr(D S) = N_electrons).
 // First moments from the same Hermite tables: <a|x|b> = (E_1^{ij} + P_x E_0^{ij}) sqrt(pi/p).
-template <int LA, int LB>
+// STORE: no density and no trace -- the matrices themselves, <mu|x|nu>, <mu|y|nu>, <mu|z|nu>, both mirror elements, into
+// [nfrag][3][n * n] at bv.dip (launch_dipole_matrices points the view's dip there)
+template <int LA, int LB, bool STORE = false>
 __global__ void __launch_bounds__(64) dipole_kernel(BatchView bv, const int* __restrict__ pairs, int npairs)
 {
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -334,25 +336,35 @@ __global__ void __launch_bounds__(64) dipole_kernel(BatchView bv, const int* __r
                     vx += w * mx[ia * NCB + ib]; vy += w * my[ia * NCB + ib]; vz += w * mz[ia * NCB + ib];
                 }
             }
-            const double d = D[(size_t)(oa + i) * n + ob + j];
-            tx += d * vx; ty += d * vy; tz += d * vz;
+            if constexpr (STORE) {
+                double* R = bv.dip + (size_t)f * 3 * n * n;
+                const size_t ab = (size_t)(oa + i) * n + ob + j, ba = (size_t)(ob + j) * n + oa + i, nn = (size_t)n * n;
+                R[ab] = vx; R[ba] = vx; R[nn + ab] = vy; R[nn + ba] = vy; R[2 * nn + ab] = vz; R[2 * nn + ba] = vz;
+            } else {
+                const double d = D[(size_t)(oa + i) * n + ob + j];
+                tx += d * vx; ty += d * vy; tz += d * vz;
+            }
         }
-    const double w = (A == B) ? 1.0 : 2.0;      // the pair list holds A >= B once
-    double* dip = bv.dip + (size_t)f * 4;
-    atomicAdd(&dip[0], w * tx); atomicAdd(&dip[1], w * ty); atomicAdd(&dip[2], w * tz);
+    if constexpr (!STORE) {
+        const double w = (A == B) ? 1.0 : 2.0;      // the pair list holds A >= B once
+        double* dip = bv.dip + (size_t)f * 4;
+        atomicAdd(&dip[0], w * tx); atomicAdd(&dip[1], w * ty); atomicAdd(&dip[2], w * tz);
+    }
 }
 
 template <int LA, int LB>
-static void launch_dipole_class(const BatchView& bv, const std::vector<int>& list, int* d, hipStream_t s)
+static void launch_dipole_class(const BatchView& bv, const std::vector<int>& list, int* d, hipStream_t s, bool store)
 {
     if (list.empty()) return;
     const int npairs = (int)list.size() / 2;
     (void)hipMemcpyAsync(d, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, s);
     const long total = (long)npairs * bv.nfrag;
-    hipLaunchKernelGGL((dipole_kernel<LA, LB>), dim3((int)((total + 63) / 64)), dim3(64), 0, s, bv, d, npairs);
+    if (store) hipLaunchKernelGGL((dipole_kernel<LA, LB, true>), dim3((int)((total + 63) / 64)), dim3(64), 0, s, bv, d, npairs);
+    else hipLaunchKernelGGL((dipole_kernel<LA, LB>), dim3((int)((total + 63) / 64)), dim3(64), 0, s, bv, d, npairs);
 }
 
-void launch_dipole(const BatchView& bv, const Topology& topo, hipStream_t s, bool accumulate)
+// the class launches of the dipole kernel: the traces with the view's density into bv.dip, or (store) the matrices there
+static void dipole_launches(const BatchView& bv, const Topology& topo, hipStream_t s, bool accumulate, bool store)
 {
     static DevicePool scratch_slot[2];
     static std::vector<int> bucket_slot[2][LMAX_AO + 1][LMAX_AO + 1];      // kept alive for the async uploads
@@ -366,12 +378,25 @@ void launch_dipole(const BatchView& bv, const Topology& topo, hipStream_t s, boo
         bucket[la][lb].push_back(B);
     }
     int* d = (int*)scratch_slot[bv.slot & 1].ensure((topo.pairs.size() + 16) * sizeof(int));
-    if (!accumulate) (void)hipMemsetAsync(bv.dip, 0, sizeof(double) * 4 * (size_t)bv.nfrag, s);
+    if (!accumulate && !store) (void)hipMemsetAsync(bv.dip, 0, sizeof(double) * 4 * (size_t)bv.nfrag, s);
     size_t off = 0;
-#define DIP_CASE(a, b) launch_dipole_class<a, b>(bv, bucket[a][b], d + off, s); off += bucket[a][b].size();
+#define DIP_CASE(a, b) launch_dipole_class<a, b>(bv, bucket[a][b], d + off, s, store); off += bucket[a][b].size();
     DIP_CASE(0, 0) DIP_CASE(1, 0) DIP_CASE(1, 1) DIP_CASE(2, 0) DIP_CASE(2, 1) DIP_CASE(2, 2)
     DIP_CASE(3, 0) DIP_CASE(3, 1) DIP_CASE(3, 2) DIP_CASE(3, 3)
 #undef DIP_CASE
+}
+
+void launch_dipole(const BatchView& bv, const Topology& topo, hipStream_t s, bool accumulate)
+{
+    dipole_launches(bv, topo, s, accumulate, false);
+}
+
+// <mu| x, y, z |nu> about the origin of every fragment of the view into out [nfrag][3][n * n] (every element is written)
+void launch_dipole_matrices(const BatchView& bv, const Topology& topo, double* out, hipStream_t s)
+{
+    BatchView v = bv;
+    v.dip = out;
+    dipole_launches(v, topo, s, false, true);
 }
 
 // Small batches: the class launches of the one-electron stage are latency-bound (0.05-0.26 ms each for one fragment,

@@ -937,6 +937,91 @@ int mqc_hip_jk_incore_batch(mqc_hip_context* ctx, int64_t nfrag, int32_t n_ao, i
     return MQC_HIP_OK;
 }
 
+// The multi-density J/K stage of a CPHF iteration on given square tensors (include/mqc_hip.h).  The tensor and the state
+// words are the ones carve_slot gives an in-core batch planned with the square layout, as the polarizability entry plans
+// its batches; D, J and K sit direction-major [3][nfrag][n * n] in a pool of this entry, J and K between two guard
+// bands, and launch_jk_multi (or, MQC_HIP_CPHF_MULTI=0, launch_jk_incore once per density) runs once over all fragments.
+// Both launchers zero K with one memset over the whole batch, so an element of a finished fragment comes back as the
+// poison (J) or as zero (K).
+int mqc_hip_jk_multi_batch(mqc_hip_context* ctx, int64_t nfrag, int32_t n_ao, int32_t n_densities, const double* tensor, const double* D,
+                           const int32_t* done, double* J, double* K, char* route, int32_t route_len)
+{
+    static DevicePool pool;
+    if (!ctx || !tensor || !D || !J || !K || !route || route_len < 1) return fail(MQC_HIP_ERR_VALIDATION, "jk multi batch: null argument");
+    if (nfrag < 1 || nfrag > (1 << 20)) return fail(MQC_HIP_ERR_VALIDATION, "jk multi batch: n_fragments must be within 1..2^20");
+    if (n_ao < 1 || n_ao > 116 || !incore_supported(n_ao)) return fail(MQC_HIP_ERR_VALIDATION, "jk multi batch: n_ao must be within 1..116 (the in-core limit)");
+    if (n_densities < 1 || n_densities > 3) return fail(MQC_HIP_ERR_VALIDATION, "jk multi batch: n_densities must be within 1..3");
+    const int nf = (int)nfrag, n = n_ao, nd = n_densities;
+    BatchPlan plan;
+    plan.n = n; plan.npair = n * (n + 1) / 2; plan.natoms = 1;
+    plan.nalpha = plan.nbeta = plan.nocc = 1;
+    plan.two_e = TWO_E_INCORE;
+    plan.square_only = true;
+    plan_layout(plan, nf, 1, 0, false);
+    HIP_CHECK_RET(hipSetDevice(ctx->device));
+    route[0] = 0;
+    const size_t nn = (size_t)n * n, np = (size_t)plan.npair;
+    constexpr size_t GUARD = 1024;
+    hipStream_t s = ctx->lane[0].stream;
+    int rc;
+    BatchView bv{};
+    bv.nalpha = bv.nbeta = bv.nocc = 1; bv.exx = 1.0;
+    TopologyDev td{};
+    if ((rc = carve_slot(ctx, make_slot(ctx, 0, nullptr), plan, td, nf, bv)) != MQC_HIP_OK) return rc;
+    const size_t mat = sizeof(double) * 3 * (size_t)nf * nn;         // three slots, whatever n_densities is
+    unsigned char* base = (unsigned char*)pool.ensure(3 * mat + 2 * GUARD);
+    if (!base) return fail(MQC_HIP_ERR_DEVICE, "out of device memory (jk multi batch)");
+    unsigned char* lo = base;
+    double* dJ = (double*)(base + GUARD);
+    double* dK = (double*)(base + GUARD + mat);
+    unsigned char* hi = base + GUARD + 2 * mat;
+    double* dD = (double*)(hi + GUARD);
+    // poison the outputs and their neighbours, then the inputs: fragment f's density d from [f][d] to [d][f]
+    HIP_CHECK_RET(hipMemsetAsync(lo, 0xFF, 2 * GUARD + 2 * mat, s));
+    std::vector<int> ist((size_t)nf * 4, 0);
+    for (int f = 0; f < nf && done; ++f)
+        if (done[f]) ist[4 * (size_t)f] = ST_DONE;
+    HIP_CHECK_RET(hipMemcpyAsync(bv.istate, ist.data(), sizeof(int) * ist.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemcpyAsync(bv.eri, tensor, sizeof(double) * (size_t)nf * np * np, hipMemcpyHostToDevice, s));
+    const size_t row = sizeof(double) * nn;
+    for (int d = 0; d < nd; ++d)
+        HIP_CHECK_RET(hipMemcpy2DAsync(dD + (size_t)d * nf * nn, row, D + (size_t)d * nn, row * nd, row, (size_t)nf, hipMemcpyHostToDevice, s));
+    std::vector<unsigned char> before(2 * GUARD), after(2 * GUARD);
+    HIP_CHECK_RET(hipMemcpyAsync(before.data(), lo, GUARD, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipMemcpyAsync(before.data() + GUARD, hi, GUARD, hipMemcpyDeviceToHost, s));
+    std::string name;
+    if (cphf_multi_on()) {
+        JkMultiRoute r{};
+        std::string err;
+        if (!launch_jk_multi(bv, nd, dD, dJ, dK, done != nullptr, s, &r, err)) return fail(MQC_HIP_ERR_DEVICE, "jk multi batch: " + err);
+        name = jk_multi_route_name(r);
+    } else {
+        JkRoute r{};
+        for (int d = 0; d < nd; ++d) {
+            BatchView v1 = bv;
+            v1.D = dD + (size_t)d * nf * nn; v1.J = dJ + (size_t)d * nf * nn; v1.K = dK + (size_t)d * nf * nn;
+            v1.jk_loaded = nullptr;
+            r = launch_jk_incore(v1, done != nullptr, s);
+        }
+        char buf[64];
+        std::snprintf(buf, sizeof(buf), "single:wave<%d,%s,%d,%d,%s%s>", r.kch, r.klds ? "lds" : "global", r.nw, r.maxu, r.dreg ? "reg" : "mem",
+                      r.full8 ? ",full8" : "");
+        name = r.family == JK_ROWCOOP ? "single:rowcoop" : buf;
+    }
+    HIP_CHECK_RET(hipMemcpyAsync(after.data(), lo, GUARD, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipMemcpyAsync(after.data() + GUARD, hi, GUARD, hipMemcpyDeviceToHost, s));
+    for (int d = 0; d < nd; ++d) {
+        HIP_CHECK_RET(hipMemcpy2DAsync(J + (size_t)d * nn, row * nd, dJ + (size_t)d * nf * nn, row, row, (size_t)nf, hipMemcpyDeviceToHost, s));
+        HIP_CHECK_RET(hipMemcpy2DAsync(K + (size_t)d * nn, row * nd, dK + (size_t)d * nf * nn, row, row, (size_t)nf, hipMemcpyDeviceToHost, s));
+    }
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    if ((rc = stage_check("multi-density J/K")) != MQC_HIP_OK) return rc;
+    if (std::memcmp(before.data(), after.data(), 2 * GUARD) != 0)
+        return fail(MQC_HIP_ERR_DEVICE, "jk multi batch: the stage wrote outside J and K");
+    std::snprintf(route, (size_t)route_len, "%s", name.c_str());
+    return MQC_HIP_OK;
+}
+
 // The build of the fitted tensor alone (include/mqc_hip.h): the plan and the arrays of a density-fitted SCF batch of
 // nfrag fragments, launch_df_integrals, the metric copied out, launch_df_fit -- the two halves of launch_df_build.
 int mqc_hip_df_fit_batch(mqc_hip_context* ctx, int64_t nfrag, const mqc_hip_molecule_t* mols, const mqc_hip_basis_t* orbital,

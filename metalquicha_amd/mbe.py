@@ -14,6 +14,7 @@ kept so that bench.py and the tests exercise the engine exactly the way metalqui
   run_mbe                  do_fragment_work over the owned terms (one engine batch), energies
                            returned in a zero-padded vector ready for ONE all-reduce
   run_mbe_rimp2            the same with RI-MP2 fragment energies (SCF + correlation per term, plain or SCS)
+  run_mbe_polarizability   the same with the static dipole polarizability of every term, assembled like the energy
 
 Nothing here touches the GPU; the SCFs are run by methods.run_hip_scf_batch.
 """
@@ -306,6 +307,11 @@ class MbeRun:
     # (scaled by `scs` where given), zero for terms this rank does not own
     correlation_os: Optional[np.ndarray] = None
     correlation_ss: Optional[np.ndarray] = None
+    # run_mbe_polarizability only: (n_terms, 3, 3) per term in the laboratory frame (zero for terms not owned or failed),
+    # the iterations of each solve, and the assembled tensor of the owned terms (all-reduce it next to the energy)
+    polarizabilities: Optional[np.ndarray] = None
+    cphf_iterations: Optional[np.ndarray] = None
+    polarizability: Optional[np.ndarray] = None
 
 
 def _group_layout(system: FragmentedSystem, term_list: Sequence[Tuple[int, ...]]):
@@ -445,6 +451,46 @@ def run_mbe_rimp2(system: FragmentedSystem, settings: ScfSettings, level: int = 
                 "no RI-MP2 energy: the SCF did not converge"
             errors.append("term %s: %s" % (terms[tix[k]], msg))
     return MbeRun(terms, energies, iters, owned, errors, None, None, e_os, e_ss)
+
+
+def run_mbe_polarizability(system: FragmentedSystem, settings: ScfSettings, level: int = 2, cphf=None,
+                           cutoffs: Optional[Dict[int, float]] = None, rank: int = 0, world: int = 1,
+                           terms: Optional[List[Tuple[int, ...]]] = None, costs: Optional[Sequence[float]] = None,
+                           solver: Optional[Callable] = None) -> MbeRun:
+    """run_mbe with the static dipole polarizability of every term: the owned terms in one
+    mqc_hip_polarizability_batch call (closed-shell Hartree-Fock on the in-core path, then the CPHF solve of every
+    converged fragment).  The polarizability is additive over the expansion exactly as the energy is: every fragment's
+    tensor is in the common laboratory frame, so `polarizability` = sum_t c_t alpha_t with compute_mbe_coefficients'
+    c_t over the owned terms (a rank's share; sum the ranks' shares).  `energies` are the SCF energies, ready for
+    compute_mbe; `polarizabilities` and `cphf_iterations` hold the terms' own.  A term whose SCF or solve failed goes to
+    `errors`, keeps zeros and leaves the assembled tensor incomplete.
+    `solver(groups) -> (records, alpha, cphf_iterations, alpha_done)` replaces methods.run_hip_polarizability_groups
+    (host tests)."""
+    from .methods import run_hip_polarizability_groups
+    solver = solver or (lambda groups: run_hip_polarizability_groups(settings, groups, cphf))
+    terms = terms if terms is not None else generate_mbe_term_list(system, level, cutoffs)
+    owned = partition_terms(len(terms), rank, world) if costs is None else partition_terms_lpt(costs, rank, world)
+    groups, positions = build_fragment_groups(system, [terms[i] for i in owned])
+    owned_arr = np.asarray(owned)
+    energies = np.zeros(len(terms)); iters = np.zeros(len(terms), dtype=np.int64)
+    alphas = np.zeros((len(terms), 3, 3)); cits = np.zeros(len(terms), dtype=np.int64)
+    errors: List[str] = []
+    recs, al_g, it_g, done_g = solver(groups)
+    for pos, rec, al, it, dn in zip(positions, recs, al_g, it_g, done_g):
+        tix = owned_arr[pos]
+        scf_ok = rec["has_error"] == 0
+        ok = scf_ok & (np.asarray(dn) != 0)
+        energies[tix[scf_ok]] = rec["e_total"][scf_ok]
+        iters[tix[scf_ok]] = rec["iterations"][scf_ok]
+        alphas[tix[ok]] = np.asarray(al)[ok]
+        cits[tix[ok]] = np.asarray(it)[ok]
+        for k in np.nonzero(~ok)[0]:
+            msg = bytes(rec["message"][k]).split(b"\0", 1)[0].decode(errors="replace") if not scf_ok[k] else \
+                "no polarizability: the SCF did not converge"
+            errors.append("term %s: %s" % (terms[tix[k]], msg))
+    coef = compute_mbe_coefficients(terms)
+    total = np.einsum("t,tcd->cd", coef[owned_arr], alphas[owned_arr]) if len(owned_arr) else np.zeros((3, 3))
+    return MbeRun(terms, energies, iters, owned, errors, polarizabilities=alphas, cphf_iterations=cits, polarizability=total)
 
 
 def _run_mbe_restart(system: FragmentedSystem, settings: ScfSettings, terms: List[Tuple[int, ...]], owned: np.ndarray,

@@ -14,6 +14,9 @@
   run_hip_esp         <- (no counterpart) the potential of converged densities at arbitrary points (mqc_hip_esp_batch)
   run_hip_rimp2_batch, run_hip_rimp2_groups <- (no counterpart: the reference's MP2 is conventional) density-fitted RHF
                          and the RI-MP2 correlation energy of every converged fragment (mqc_hip_rimp2_batch)
+  CphfSettings, run_hip_polarizability_batch, run_hip_polarizability_groups <- (no counterpart) closed-shell RHF on the
+                         in-core path and the static dipole polarizability of every converged fragment by a batched
+                         CPHF solve (mqc_hip_polarizability_batch)
   PcmSettings, run_hip_scf_pcm_batch, run_hip_scf_pcm_groups <- the SCF with cuestPCMPotentialCompute's term ("C-PCM
                          charges + V_pcm", mqc_cuest_integrals.f90:974-1366), this engine's own discretisation
                          (mqc_hip_scf_pcm_batch)
@@ -153,6 +156,19 @@ class PcmSettings:
 
 
 @dataclass
+class CphfSettings:
+    """The coupled-perturbed Hartree-Fock solve (mqc_hip_cphf_options_t): a fragment is converged when the largest
+    element of its residual, over the three field directions, is at most `tol`; `max_iter` bounds the iterations."""
+    tol: float = 1.0e-8
+    max_iter: int = 64
+
+    def options(self) -> capi.CphfOptions:
+        o = capi.CphfOptions()
+        o.tol = float(self.tol); o.max_iter = int(self.max_iter)
+        return o
+
+
+@dataclass
 class CalculationResult:
     energy: EnergyT = field(default_factory=EnergyT)
     has_energy: bool = False
@@ -184,6 +200,10 @@ class CalculationResult:
     # filled by the restart path (run_hip_scf_batch / run_hip_scf with starting densities): what the next start needs
     density: Optional[np.ndarray] = None               # (n_ao, n_ao) total density
     spin_densities: Optional[np.ndarray] = None        # (2, n_ao, n_ao) alpha, beta: unrestricted runs only
+    # filled by run_hip_polarizability_batch
+    polarizability: Optional[np.ndarray] = None        # (3, 3) static dipole polarizability, atomic units, laboratory frame
+    has_polarizability: bool = False
+    cphf_iterations: int = 0
 
 
 DEFAULT_DISPLACEMENT = 0.005         # Bohr, src/core/mqc_calculation_defaults.f90:13
@@ -403,7 +423,7 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
                        extras_out: Optional[list] = None, site_gradients_out: Optional[list] = None,
                        status_out: Optional[list] = None, initial_densities: Optional[Sequence] = None,
                        spin_densities_out: Optional[list] = None, rimp2: Optional[dict] = None,
-                       pcm: Optional[dict] = None) -> List[np.ndarray]:
+                       pcm: Optional[dict] = None, cphf: Optional[dict] = None) -> List[np.ndarray]:
     """All fragments of all groups in ONE mqc_hip_scf_run_batch call; returns, per group, a structured array
     viewing the engine's result records (fields of capi.ScfResult: e_total, iterations, has_error, message ...).
 
@@ -427,7 +447,8 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
     that ran unrestricted (zeros elsewhere).
 
     `rimp2` (a dict, see run_hip_rimp2_groups) sends the batch through mqc_hip_rimp2_batch; `pcm` (a dict, see
-    run_hip_scf_pcm_groups) through mqc_hip_scf_pcm_batch."""
+    run_hip_scf_pcm_groups) through mqc_hip_scf_pcm_batch; `cphf` (a dict, see run_hip_polarizability_groups) through
+    mqc_hip_polarizability_batch."""
     embedded = site_gradients_out is not None
     restart = initial_densities is not None or spin_densities_out is not None
     if restart and embedded:
@@ -436,6 +457,8 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
         raise ValueError("RI-MP2 combines with neither starting densities nor the embedded-gradient entry")
     if pcm is not None and (restart or embedded or rimp2 is not None):
         raise ValueError("PCM combines with neither starting densities, the embedded-gradient entry nor RI-MP2")
+    if cphf is not None and (restart or embedded or rimp2 is not None or pcm is not None):
+        raise ValueError("polarizabilities combine with neither starting densities, the embedded-gradient entry, RI-MP2 nor PCM")
     if initial_densities is not None and len(initial_densities) != len(groups):
         raise ValueError("initial_densities must hold one entry per group")
     want_gradient = bool(want_gradient) or embedded
@@ -447,6 +470,9 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
                          mp2_done=[np.zeros(0, dtype=np.int32) for _ in groups])
         if pcm is not None:
             pcm.update(e_pcm=[np.zeros(0) for _ in groups], n_tesserae=[np.zeros(0, dtype=np.int32) for _ in groups])
+        if cphf is not None:
+            cphf.update(alpha=[np.zeros((0, 3, 3)) for _ in groups], cphf_iterations=[np.zeros(0, dtype=np.int32) for _ in groups],
+                        alpha_done=[np.zeros(0, dtype=np.int32) for _ in groups])
         return [np.zeros(0, dtype=_RES_DTYPE) for _ in groups]
     lib = capi.load_library()
     ctx = capi.get_context(settings.device_rank)
@@ -606,6 +632,14 @@ def run_hip_scf_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], w
                                        capi.dptr(e_pcm), n_tess.ctypes.data_as(capi.c_int32_p))
         cuts = np.cumsum(sizes)[:-1]
         pcm.update(e_pcm=np.split(e_pcm, cuts), n_tesserae=np.split(n_tess, cuts))
+    elif cphf is not None:
+        alpha, its, done = np.zeros((n, 3, 3)), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        copts = cphf["settings"].options()
+        rc = lib.mqc_hip_polarizability_batch(ctx, n, mols.ctypes.data_as(C.POINTER(capi.Molecule)),
+                                              bass.ctypes.data_as(C.POINTER(capi.Basis)), C.byref(opts), C.byref(copts), res,
+                                              capi.dptr(alpha), its.ctypes.data_as(capi.c_int32_p), done.ctypes.data_as(capi.c_int32_p))
+        cuts = np.cumsum(sizes)[:-1]
+        cphf.update(alpha=np.split(alpha, cuts), cphf_iterations=np.split(its, cuts), alpha_done=np.split(done, cuts))
     else:
         rc = lib.mqc_hip_scf_run_batch(ctx, n, mols.ctypes.data_as(C.POINTER(capi.Molecule)),
                                        bass.ctypes.data_as(C.POINTER(capi.Basis)),
@@ -745,6 +779,39 @@ def run_hip_rimp2_batch(settings: ScfSettings, fragments: Sequence[PhysicalFragm
             if results[i].has_energy and dn[pos]:
                 results[i].energy.mp2_os = float(os_[pos]); results[i].energy.mp2_ss = float(ss_[pos])
                 results[i].has_mp2 = True
+    return results
+
+
+def run_hip_polarizability_groups(settings: ScfSettings, groups: Sequence[FragmentGroup], cphf: Optional[CphfSettings] = None,
+                                  extras: Sequence[str] = (), extras_out: Optional[list] = None, status_out: Optional[list] = None):
+    """All fragments of all groups in ONE mqc_hip_polarizability_batch call: the closed-shell Hartree-Fock SCF of
+    run_hip_scf_groups on the in-core path followed, per converged fragment, by the CPHF solve for its static dipole
+    polarizability.  -> (records, alpha, cphf_iterations, alpha_done): per group the result records and three arrays:
+    alpha (m, 3, 3) in atomic units in the laboratory frame, the iterations of each solve (m,) and 1 where alpha was
+    formed -- 0, with zeros, where the SCF or the solve failed (the record then says why).  Refusals (density fitting, a
+    functional, open shells, a gradient, the direct path, n_ao > 116) arrive in the records' messages, the call's status
+    in `status_out`."""
+    box = {"settings": cphf or CphfSettings()}
+    rec = run_hip_scf_groups(settings, groups, extras=extras, extras_out=extras_out, status_out=status_out, cphf=box)
+    return rec, box["alpha"], box["cphf_iterations"], box["alpha_done"]
+
+
+def run_hip_polarizability_batch(settings: ScfSettings, fragments: Sequence[PhysicalFragment],
+                                 cphf: Optional[CphfSettings] = None) -> List[CalculationResult]:
+    """Many independent fragments through mqc_hip_polarizability_batch, results as CalculationResult objects: energy.scf,
+    and where has_polarizability is set `polarizability` (3, 3) and `cphf_iterations`."""
+    results = [CalculationResult() for _ in range(len(fragments))]
+    if not fragments:
+        return results
+    groups, index = _groups_of(fragments)
+    recs, alpha, its, done = run_hip_polarizability_groups(settings, groups, cphf)
+    for idx, rec, al, it, dn in zip(index, recs, alpha, its, done):
+        for pos, (i, r) in enumerate(zip(idx, rec)):
+            _fill_record(results[i], r)
+            results[i].cphf_iterations = int(it[pos])
+            if results[i].has_energy and dn[pos]:
+                results[i].polarizability = np.array(al[pos], dtype=float)
+                results[i].has_polarizability = True
     return results
 
 
