@@ -387,6 +387,41 @@ int mqc_hip_rimp2_batch(mqc_hip_context *ctx, int64_t n_fragments, const mqc_hip
                         int32_t frozen_core,
                         double *e_os /* [n] */, double *e_ss /* [n] */, int32_t *mp2_done /* [n] */);
 
+/* The RI-MP2 stage on GIVEN tensors, for n_fragments of one shape: what mqc_hip_rimp2_batch runs after the SCF loop of a
+ * chunk (the three kernels of kern_mp2.hip, once), alone.  No molecule: the kernels read the sizes, the fitted tensor,
+ * the orbitals, their energies and the fragment states only.
+ *     B [n][n_aux][npair]     the fitted tensor, packed pairs (mu >= nu, index mu (mu + 1) / 2 + nu) fastest
+ *     C [n][n_ao*n_ao]        row-major, columns are orbitals: n_frozen frozen, then the active occupied ones up to n_occ,
+ *                             then the virtuals up to nmo; columns beyond nmo are not orbitals and are never read into a result
+ *     eps [n][n_ao]           orbital energies
+ *     nmo [n], runs [n]       kept orbitals of each fragment; runs = 0 marks a fragment whose SCF is not finished.  The entry
+ *                             writes the state {done or iterating, 0, nmo, converged} from them; a fragment with runs = 0 or
+ *                             nmo < n_occ gets zeros, as in the batch entry
+ *     e [n][2]                e_os, e_ss
+ *     part [n][npairs][2]     the partial of every pair i >= j (pair index i (i + 1) / 2 + j over the n_occ - n_frozen active
+ *                             orbitals) before the reduction, weight 1 or 2 included
+ *     Bia (or NULL)           [n][n_occ - n_frozen][napad][nvpad] the transformed tensor WITH its padding: napad = n_aux
+ *                             rounded up to 4, nvpad = n_ao - n_occ rounded up to 16 (route[6], route[7])
+ *     route [16]              0: C in LDS (1) or from L2 (0); 1: pairs of a row prefetched per lane (NPF, 0: none); 2: waves per
+ *                             workgroup of the transform; 3: occupied orbitals per pass; 4: workgroups per fragment; 5: dynamic
+ *                             LDS bytes; 6: napad; 7: nvpad; 8: npairs; 9: passes over the occupied orbitals; 10: auxiliary
+ *                             rows the busiest wave walks (padding rows included); 11: times the launcher narrowed the pass to
+ *                             make the transform fit the LDS; 12-15: zero
+ * workgroups_per_fragment = 0 leaves the transform's grid to the launcher (as the batch entry does); a positive value may
+ * only LOWER the workgroups per fragment: it reproduces with a few fragments the rows per wave of a batch of thousands.
+ * e, part and Bia are filled with NaN first, and the stage's device arrays and the roundings between and behind them are
+ * poisoned before the launch: an element the kernels read without having written it shows as NaN.  The roundings are
+ * compared across the launch (MQC_HIP_ERR_DEVICE when the stage wrote outside its arrays).
+ * ctx = NULL runs no device code and reads none of the arrays (all may be NULL): route alone is written, the launcher's
+ * decision for this shape and n_fragments.  n_occ = n_ao (no virtual orbital): zeros, route[7] = 0.
+ * MQC_HIP_ERR_VALIDATION: null pointers, n_fragments < 1, n_ao outside 1..140, n_occ outside 1..n_ao, n_frozen outside
+ * 0..n_occ-1, n_aux < 1, workgroups_per_fragment < 0, nmo[i] outside 0..n_ao.  (Added without an ABI bump: no struct changed.) */
+#define MQC_HIP_RIMP2_ROUTE_LEN 16
+int mqc_hip_rimp2_stage(mqc_hip_context *ctx, int64_t n_fragments, int32_t n_ao, int32_t n_occ, int32_t n_aux,
+                        int32_t n_frozen, int32_t workgroups_per_fragment, const double *B, const double *C,
+                        const double *eps, const int32_t *nmo, const int32_t *runs, double *e, double *part,
+                        double *Bia /* or NULL */, int32_t *route /* [MQC_HIP_RIMP2_ROUTE_LEN] */);
+
 /* ---- static dipole polarizabilities (CPHF) ---------------------------------------------- */
 /* Settings of the coupled-perturbed Hartree-Fock solve: a fragment is converged when the largest element, over the three
  * directions, of the residual Delta o U + G(U) + b is at most tol; max_iter bounds its conjugate-gradient iterations. */

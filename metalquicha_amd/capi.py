@@ -108,6 +108,7 @@ DECLARED_SYMBOLS = [
     "mqc_hip_default_pcm_options", "mqc_hip_scf_pcm_batch", "mqc_hip_pcm_stage",
     "mqc_hip_gradient_stage",
     "mqc_hip_default_cphf_options", "mqc_hip_polarizability_batch", "mqc_hip_jk_multi_batch",
+    "mqc_hip_rimp2_stage",
 ]
 
 _lib = None
@@ -144,6 +145,8 @@ def load_library():
                                                   C.POINTER(ScfOptions), C.POINTER(ScfResult), C.POINTER(c_double_p), C.POINTER(c_double_p)]
     lib.mqc_hip_rimp2_batch.argtypes = [C.c_void_p, C.c_int64, C.POINTER(Molecule), C.POINTER(Basis), C.POINTER(Basis),
                                         C.POINTER(ScfOptions), C.POINTER(ScfResult), C.c_int32, c_double_p, c_double_p, c_int32_p]
+    lib.mqc_hip_rimp2_stage.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p,
+                                        c_double_p, c_double_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p]
     lib.mqc_hip_default_pcm_options.argtypes = [C.POINTER(PcmOptions)]
     lib.mqc_hip_default_pcm_options.restype = None
     lib.mqc_hip_scf_pcm_batch.argtypes = [C.c_void_p, C.c_int64, C.POINTER(Molecule), C.POINTER(Basis), C.POINTER(Basis),

@@ -35,10 +35,7 @@ static DevicePool g_grad_pool[2];
 bool launch_pc_gradient(const BatchView& bv, const Topology& topo, const double* Dtot, double* d_grad, double* d_pcgrad, double* d_rec,
                         hipStream_t s, std::string& err);
 size_t gradpc_record_doubles(const Topology& topo);
-// kern_mp2.hip: RI-MP2 pair energies of a converged density-fitted chunk, [nfrag][2] = e_os, e_ss copied to h_out on s
-// (the caller joins the stream); device bytes per fragment of the stage
-bool launch_rimp2(const BatchView& bv, int n_frozen, double* h_out, hipStream_t s, std::string& err);
-size_t rimp2_fragment_bytes(int n, int nocc, int naux, int n_frozen);
+// kern_mp2.hip (launch_rimp2, rimp2_fragment_bytes: engine.hpp, shared with the stage entry)
 // kern_cphf.hip: the CPHF solve of a converged in-core chunk with the square tensor -- alpha [nfrag][9], iterations and
 // CPHF_* status per fragment, complete on return (h_counter: the slot's pinned word); device bytes per fragment
 bool launch_cphf(const BatchView& bv, const Topology& topo, double tol, int max_iter, double* h_alpha, int* h_iter, int* h_status,

@@ -460,6 +460,31 @@ struct DfJkRoute {
     bool flag;
 };
 DfJkRoute launch_df_jk(const BatchView& bv, bool only_active, hipStream_t s);
+// RI-MP2 (kern_mp2.hip).  launch_rimp2 = rimp2_route (host arithmetic: the transform's instance, its LDS and grid) +
+// rimp2_carve (Bia, the pair partials and the results from the slot's pool, each rounded up to 256 bytes) +
+// rimp2_enqueue (the three kernels and the copy of the results).  The batch driver calls launch_rimp2;
+// mqc_hip_rimp2_stage takes the steps one at a time, poisons the pool between them and reports the route.
+struct Mp2Route {
+    bool clds;                    // C in LDS (else streamed from L2)
+    int npf;                      // pairs of a row a lane prefetches into registers (0: none)
+    int nw, oc, gx;               // waves per workgroup, occupied orbitals per pass, workgroups per fragment
+    size_t lds;                   // dynamic LDS bytes of the transform
+    int napad, nvpad, npairs;     // naux rounded up to 4, n - nocc rounded up to 16, pairs i >= j
+    int passes, rows;             // passes over the occupied orbitals; rows the busiest wave walks (padding included)
+    int narrowed;                 // times the occupied pass was narrowed by 16 to fit the LDS
+};
+struct Mp2Pool {
+    char* base;                   // [Bia | part | out], each rounded up to 256 bytes
+    size_t b_bia, b_part, b_out;  // the rounded sizes
+    size_t u_bia, u_part, u_out;  // the bytes the kernels own
+};
+// gx_cap > 0 may only lower the workgroups per fragment (the stage entry: several rows per wave with few fragments)
+bool rimp2_route(int nfrag, int n, int nocc, int naux, int n_frozen, int gx_cap, Mp2Route& r, std::string& err);
+bool rimp2_carve(const BatchView& bv, int n_frozen, Mp2Pool& p, std::string& err);
+bool rimp2_enqueue(const BatchView& bv, int n_frozen, const Mp2Route& r, const Mp2Pool& p, double* h_out, hipStream_t s, std::string& err);
+// e_os, e_ss of every fragment of the chunk copied to h_out [nfrag][2] on s (the caller joins the stream)
+bool launch_rimp2(const BatchView& bv, int n_frozen, double* h_out, hipStream_t s, std::string& err);
+size_t rimp2_fragment_bytes(int n, int nocc, int naux, int n_frozen);
 void launch_xc(const BatchView& bv, bool only_active, hipStream_t s);
 // C-PCM (kern_pcm.hip).  Setup, once per geometry: the cavity matrix, its Cholesky factor and inverse (the density
 // fitting's kernels on a view of the PCM arrays), A, B = L^-1 A, v_nuc and b = L^-1 v_nuc.  Iteration: c = b - B d,

@@ -239,65 +239,84 @@ size_t rimp2_fragment_bytes(int n, int nocc, int naux, int n_frozen)
     return sizeof(double) * ((size_t)mv.no * mv.napad * mv.nvpad + 2 * (size_t)mv.npairs + 2);
 }
 
-// e_os, e_ss of every fragment of the chunk copied to h_out [nfrag][2] (zeros for fragments whose SCF did not converge),
-// everything enqueued on s: the caller joins the stream before it reads h_out
-bool launch_rimp2(const BatchView& bv, int n_frozen, double* h_out, hipStream_t s, std::string& err)
+
+// The transform's route for a chunk of nf fragments: host arithmetic only (mqc_hip_rimp2_stage reports it without a device).
+// Per wave the LDS holds the packed row and T [16 nt][oc + 1]; fewer waves, then a narrower occupied pass, until it fits.
+// For n <= 140 neither the narrowing nor the refusal is reached: one wave with a 64-orbital pass needs 153 840 bytes at
+// n = 140 (tests/test_rimp2_stage_cases.py walks every (n, nocc)).
+bool rimp2_route(int nf, int n, int nocc, int naux, int n_frozen, int gx_cap, Mp2Route& r, std::string& err)
 {
-    static DevicePool pool[2];
-    const int nf = bv.nfrag, n = bv.n;
-    Mp2View mv = mp2_shape(n, bv.nocc, bv.naux, n_frozen);
-    if (bv.naux <= 0 || !bv.df_b) { err = "RI-MP2 uses the fitted tensor of a density-fitted SCF"; return false; }
+    const Mp2View mv = mp2_shape(n, nocc, naux, n_frozen);
+    r = Mp2Route{};
+    r.napad = mv.napad; r.nvpad = mv.nvpad; r.npairs = mv.npairs;
     if (mv.no < 1) { err = "RI-MP2: no active occupied orbital"; return false; }
-    if (mv.nvpad == 0) {                                // no virtual orbital: nothing to correlate
-        for (int k = 0; k < 2 * nf; ++k) h_out[k] = 0.0;
-        return true;
-    }
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t b_bia = up(sizeof(double) * (size_t)nf * mv.no * mv.napad * mv.nvpad);
-    const size_t b_part = up(sizeof(double) * (size_t)nf * mv.npairs * 2), b_out = up(sizeof(double) * (size_t)nf * 2);
-    char* base = (char*)pool[bv.slot & 1].ensure(b_bia + b_part + b_out);
-    if (!base) { err = "out of device memory (RI-MP2 transformed tensor)"; return false; }
-    mv.Bia = (double*)base; mv.part = (double*)(base + b_bia); mv.out = (double*)(base + b_bia + b_part);
-    // the transform's LDS: per wave the packed row and T [16 nt][oc + 1]; fewer waves, then a narrower occupied pass,
-    // until it fits (n = 140 with 16 orbitals per pass and one wave: 99 KB)
+    if (mv.nvpad == 0) return true;                     // no virtual orbital: nothing to correlate, nothing launched
+    const int npair = n * (n + 1) / 2;
     const int nt = (n + 15) / 16, nop = (mv.no + 15) & ~15;
     const size_t lds_max = 160 * 1024 - 512;
-    auto lds_of = [&](int w, int oc) { return sizeof(double) * (size_t)w * ((size_t)bv.npair + (size_t)16 * nt * (oc + 1)); };
+    auto lds_of = [&](int w, int oc) { return sizeof(double) * (size_t)w * ((size_t)npair + (size_t)16 * nt * (oc + 1)); };
     // C in LDS where it leaves room for at least two waves' buffers (one workgroup per CU, up to eight waves) ...
     const size_t c_lds = sizeof(double) * (size_t)(4 * ((n + 3) / 4)) * (nop + mv.nvpad);
     // (MQC_HIP_MP2_C_LDS=0: never, the A/B switch of the two variants)
     static const bool clds_on = env_on("MQC_HIP_MP2_C_LDS");
-    const bool clds = clds_on && nop <= 64 && c_lds + lds_of(2, nop) <= lds_max;
-    int nw = MP2_TW;
-    size_t lds = 0;
-    if (clds) {
-        mv.oc = nop;
-        while (c_lds + lds_of(nw, mv.oc) > lds_max) nw >>= 1;
-        lds = c_lds + lds_of(nw, mv.oc);
+    r.clds = clds_on && nop <= 64 && c_lds + lds_of(2, nop) <= lds_max;
+    r.nw = MP2_TW;
+    if (r.clds) {
+        r.oc = nop;
+        while (c_lds + lds_of(r.nw, r.oc) > lds_max) r.nw >>= 1;
+        r.lds = c_lds + lds_of(r.nw, r.oc);
+        r.npf = npair <= 64 * MP2_PF ? MP2_PF : 0;
     } else {
         // ... else C from L2, two workgroups per CU while that leaves a workgroup more than one wave
-        nw = 4;
-        mv.oc = std::min(nop, 64);
-        while (lds_of(nw, mv.oc) > (nw > 1 ? lds_max / 2 : lds_max)) {
-            if (nw > 1) nw >>= 1;
-            else if (mv.oc > 16) mv.oc -= 16;
+        r.nw = 4;
+        r.oc = std::min(nop, 64);
+        while (lds_of(r.nw, r.oc) > (r.nw > 1 ? lds_max / 2 : lds_max)) {
+            if (r.nw > 1) r.nw >>= 1;
+            else if (r.oc > 16) { r.oc -= 16; ++r.narrowed; }
             else { err = "RI-MP2: a packed row of the fitted tensor does not fit the LDS"; return false; }
         }
-        lds = lds_of(nw, mv.oc);
+        r.lds = lds_of(r.nw, r.oc);
     }
-    mv.ts = mv.oc + 1;
+    r.gx = (2048 + nf - 1) / nf;                        // workgroups per fragment: every wave should see several rows
+    const int maxg = (mv.napad + r.nw - 1) / r.nw;
+    if (r.gx > maxg) r.gx = maxg;
+    if (gx_cap > 0 && r.gx > gx_cap) r.gx = gx_cap;
+    if (r.gx < 1) r.gx = 1;
+    r.passes = (mv.no + r.oc - 1) / r.oc;
+    r.rows = (mv.napad + r.gx * r.nw - 1) / (r.gx * r.nw);
+    return true;
+}
+
+// Bia, the pair partials and the results of the chunk from the slot's pool (static, grow-only, reused across calls)
+bool rimp2_carve(const BatchView& bv, int n_frozen, Mp2Pool& p, std::string& err)
+{
+    static DevicePool pool[2];
+    const Mp2View mv = mp2_shape(bv.n, bv.nocc, bv.naux, n_frozen);
+    const size_t nf = (size_t)bv.nfrag;
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    p.u_bia = sizeof(double) * nf * mv.no * mv.napad * mv.nvpad;
+    p.u_part = sizeof(double) * nf * mv.npairs * 2;
+    p.u_out = sizeof(double) * nf * 2;
+    p.b_bia = up(p.u_bia); p.b_part = up(p.u_part); p.b_out = up(p.u_out);
+    p.base = (char*)pool[bv.slot & 1].ensure(p.b_bia + p.b_part + p.b_out);
+    if (!p.base) { err = "out of device memory (RI-MP2 transformed tensor)"; return false; }
+    return true;
+}
+
+bool rimp2_enqueue(const BatchView& bv, int n_frozen, const Mp2Route& r, const Mp2Pool& p, double* h_out, hipStream_t s, std::string& err)
+{
+    const int nf = bv.nfrag, n = bv.n;
+    Mp2View mv = mp2_shape(n, bv.nocc, bv.naux, n_frozen);
+    mv.Bia = (double*)p.base; mv.part = (double*)(p.base + p.b_bia); mv.out = (double*)(p.base + p.b_bia + p.b_part);
+    mv.oc = r.oc; mv.ts = r.oc + 1;
     // MQC_HIP_MP2_TIMING=1 (measurement): the span of this stage on stderr, per chunk
     static const bool timing = env_opt_in("MQC_HIP_MP2_TIMING");
     hipEvent_t ev[3] = {};
     if (timing) for (auto& e : ev) { (void)hipEventCreate(&e); }
     if (timing) (void)hipEventRecord(ev[0], s);
-    auto kern = !clds ? mp2_transform_kernel<false, 0> : bv.npair <= 64 * MP2_PF ? mp2_transform_kernel<true, MP2_PF> : mp2_transform_kernel<true, 0>;
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    int gx = (2048 + nf - 1) / nf;                      // workgroups per fragment: every wave should see several rows
-    const int maxg = (mv.napad + nw - 1) / nw;
-    if (gx > maxg) gx = maxg;
-    if (gx < 1) gx = 1;
-    hipLaunchKernelGGL(kern, dim3(gx, nf), dim3(64 * nw), lds, s, bv, mv);
+    auto kern = !r.clds ? mp2_transform_kernel<false, 0> : r.npf > 0 ? mp2_transform_kernel<true, MP2_PF> : mp2_transform_kernel<true, 0>;
+    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
+    hipLaunchKernelGGL(kern, dim3(r.gx, nf), dim3(64 * r.nw), r.lds, s, bv, mv);
     if (timing) (void)hipEventRecord(ev[1], s);
     hipLaunchKernelGGL(mp2_pair_kernel, dim3((mv.npairs + MP2_NW - 1) / MP2_NW, nf), dim3(64 * MP2_NW), 0, s, bv, mv);
     hipLaunchKernelGGL(mp2_reduce_kernel, dim3((nf + 255) / 256), dim3(256), 0, s, bv, mv);
@@ -316,6 +335,21 @@ bool launch_rimp2(const BatchView& bv, int n_frozen, double* h_out, hipStream_t 
         for (auto& e : ev) (void)hipEventDestroy(e);
     }
     return true;
+}
+
+// e_os, e_ss of every fragment of the chunk copied to h_out [nfrag][2] (zeros for fragments whose SCF did not converge),
+// everything enqueued on s: the caller joins the stream before it reads h_out
+bool launch_rimp2(const BatchView& bv, int n_frozen, double* h_out, hipStream_t s, std::string& err)
+{
+    if (bv.naux <= 0 || !bv.df_b) { err = "RI-MP2 uses the fitted tensor of a density-fitted SCF"; return false; }
+    Mp2Route r;
+    if (!rimp2_route(bv.nfrag, bv.n, bv.nocc, bv.naux, n_frozen, 0, r, err)) return false;
+    if (r.nvpad == 0) {                                 // no virtual orbital: nothing to correlate
+        for (int k = 0; k < 2 * bv.nfrag; ++k) h_out[k] = 0.0;
+        return true;
+    }
+    Mp2Pool p;
+    return rimp2_carve(bv, n_frozen, p, err) && rimp2_enqueue(bv, n_frozen, r, p, h_out, s, err);
 }
 
 }  // namespace mqc

@@ -802,6 +802,96 @@ int mqc_hip_df_jk_batch(mqc_hip_context* ctx, int64_t nfrag, int32_t n_ao, int32
     return MQC_HIP_OK;
 }
 
+// The RI-MP2 stage on given tensors (include/mqc_hip.h).  No molecule: the kernels read n, npair, naux, nocc, df_b, C, eps
+// and istate only.  The arrays are the ones carve_slot gives a density-fitted batch of this shape; the launcher's three
+// steps (kern_mp2.hip: route, carve, enqueue) run once over all fragments, as launch_rimp2 runs them, with the stage's
+// pool region poisoned in between.  ctx == nullptr: the route alone, no device call.
+int mqc_hip_rimp2_stage(mqc_hip_context* ctx, int64_t nfrag, int32_t n_ao, int32_t n_occ, int32_t n_aux, int32_t n_frozen, int32_t gx_cap,
+                        const double* B, const double* C, const double* eps, const int32_t* nmo, const int32_t* runs, double* e, double* part,
+                        double* Bia, int32_t* route)
+{
+    if (!route) return fail(MQC_HIP_ERR_VALIDATION, "rimp2 stage: null argument (route)");
+    if (ctx && (!B || !C || !eps || !nmo || !runs || !e || !part)) return fail(MQC_HIP_ERR_VALIDATION, "rimp2 stage: null argument");
+    if (nfrag < 1 || nfrag > (1 << 20)) return fail(MQC_HIP_ERR_VALIDATION, "rimp2 stage: n_fragments must be within 1..2^20");
+    if (n_ao < 1 || n_ao > 140) return fail(MQC_HIP_ERR_VALIDATION, "rimp2 stage: n_ao must be within 1..140");
+    if (n_occ < 1 || n_occ > n_ao) return fail(MQC_HIP_ERR_VALIDATION, "rimp2 stage: n_occ must be within 1..n_ao");
+    if (n_frozen < 0 || n_frozen >= n_occ) return fail(MQC_HIP_ERR_VALIDATION, "rimp2 stage: n_frozen must be within 0..n_occ-1");
+    if (n_aux < 1) return fail(MQC_HIP_ERR_VALIDATION, "rimp2 stage: n_aux must be at least 1");
+    if (gx_cap < 0) return fail(MQC_HIP_ERR_VALIDATION, "rimp2 stage: workgroups_per_fragment must not be negative");
+    if (ctx)
+        for (int64_t f = 0; f < nfrag; ++f)
+            if (nmo[f] < 0 || nmo[f] > n_ao) return fail(MQC_HIP_ERR_VALIDATION, "rimp2 stage: nmo[" + std::to_string(f) + "] is outside 0..n_ao");
+    const int nf = (int)nfrag;
+    std::string why;
+    Mp2Route r;
+    if (!rimp2_route(nf, n_ao, n_occ, n_aux, n_frozen, gx_cap, r, why)) return fail(MQC_HIP_ERR_UNSUPPORTED, why);
+    const int32_t rec[MQC_HIP_RIMP2_ROUTE_LEN] = {r.clds ? 1 : 0, r.npf, r.nw, r.oc, r.gx, (int32_t)r.lds, r.napad, r.nvpad,
+                                                  r.npairs, r.passes, r.rows, r.narrowed, 0, 0, 0, 0};
+    std::memcpy(route, rec, sizeof(rec));
+    if (!ctx) return MQC_HIP_OK;
+    const int no = n_occ - n_frozen;
+    const size_t nn = (size_t)n_ao * n_ao, c_part = (size_t)nf * r.npairs * 2, c_bia = (size_t)nf * no * r.napad * r.nvpad;
+    const double nan = std::nan("");
+    std::fill(e, e + 2 * (size_t)nf, nan);
+    std::fill(part, part + c_part, nan);
+    if (Bia) std::fill(Bia, Bia + c_bia, nan);
+    if (r.nvpad == 0) {                                 // no virtual orbital: the launcher launches nothing
+        std::fill(e, e + 2 * (size_t)nf, 0.0);
+        std::fill(part, part + c_part, 0.0);
+        return MQC_HIP_OK;
+    }
+    HIP_CHECK_RET(hipSetDevice(ctx->device));
+    BatchPlan plan;
+    plan.n = n_ao; plan.npair = n_ao * (n_ao + 1) / 2; plan.natoms = 1;
+    plan.nalpha = plan.nbeta = plan.nocc = n_occ;
+    plan.two_e = TWO_E_DF; plan.naux = n_aux;
+    plan_layout(plan, nf, 1, 0, false);
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    free_b += ctx->lane[0].pool[POOL_MAIN].capacity() + ctx->lane[0].pool[POOL_DF].capacity();
+    // one launch over all fragments (the route depends on their number): no chunks
+    if (stage_chunk_fragments(free_b, fragment_bytes(plan) + rimp2_fragment_bytes(n_ao, n_occ, n_aux, n_frozen), nfrag, nfrag) < nfrag)
+        return fail(MQC_HIP_ERR_UNSUPPORTED, "rimp2 stage: the batch does not fit the free device memory in one chunk");
+    const TopologyDev td{};
+    hipStream_t s = ctx->lane[0].stream;
+    BatchView bv{};
+    bv.nalpha = bv.nbeta = bv.nocc = n_occ; bv.exx = 1.0;
+    int rc;
+    if ((rc = carve_slot(ctx, make_slot(ctx, 0, nullptr), plan, td, nf, bv)) != MQC_HIP_OK) return rc;
+    std::vector<int> st(4 * (size_t)nf);
+    for (int f = 0; f < nf; ++f) {
+        st[4 * f] = runs[f] ? ST_DONE : ST_ITER; st[4 * f + 1] = 0; st[4 * f + 2] = nmo[f]; st[4 * f + 3] = runs[f] ? 1 : 0;
+    }
+    HIP_CHECK_RET(hipMemcpyAsync(bv.istate, st.data(), sizeof(int) * st.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemcpyAsync(bv.df_b, B, sizeof(double) * (size_t)nf * n_aux * plan.npair, hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemcpyAsync(bv.C, C, sizeof(double) * nf * nn, hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipMemcpyAsync(bv.eps, eps, sizeof(double) * (size_t)nf * n_ao, hipMemcpyHostToDevice, s));
+    Mp2Pool p;
+    if (!rimp2_carve(bv, n_frozen, p, why)) return fail(MQC_HIP_ERR_DEVICE, why);
+    if (p.u_bia != sizeof(double) * c_bia || p.u_part != sizeof(double) * c_part)
+        return fail(MQC_HIP_ERR_DEVICE, "rimp2 stage: the stage's arrays are not the size the entry expects");
+    // Poison: the pool is static and reused across calls, so without it an element the pair kernel reads from the padding
+    // of Bia, or the reduction from a pair nobody wrote, would be whatever the last call left.  What the poison cannot
+    // show is a write OUTSIDE the three arrays: the roundings behind each are compared across the launch.
+    const size_t total = p.b_bia + p.b_part + p.b_out;
+    HIP_CHECK_RET(hipMemsetAsync(p.base, 0xFF, total, s));
+    const size_t g0 = p.b_bia - p.u_bia, g1 = p.b_part - p.u_part, g2 = p.b_out - p.u_out;
+    std::vector<double> h_out(2 * (size_t)nf, nan);
+    if (!rimp2_enqueue(bv, n_frozen, r, p, h_out.data(), s, why)) return fail(MQC_HIP_ERR_DEVICE, why);
+    std::vector<unsigned char> gaps(g0 + g1 + g2 + 1, 0);
+    if (g0) HIP_CHECK_RET(hipMemcpyAsync(gaps.data(), p.base + p.u_bia, g0, hipMemcpyDeviceToHost, s));
+    if (g1) HIP_CHECK_RET(hipMemcpyAsync(gaps.data() + g0, p.base + p.b_bia + p.u_part, g1, hipMemcpyDeviceToHost, s));
+    if (g2) HIP_CHECK_RET(hipMemcpyAsync(gaps.data() + g0 + g1, p.base + p.b_bia + p.b_part + p.u_out, g2, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipMemcpyAsync(part, p.base + p.b_bia, p.u_part, hipMemcpyDeviceToHost, s));
+    if (Bia) HIP_CHECK_RET(hipMemcpyAsync(Bia, p.base, p.u_bia, hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    if ((rc = stage_check("RI-MP2")) != MQC_HIP_OK) return rc;
+    for (size_t k = 0; k < g0 + g1 + g2; ++k)
+        if (gaps[k] != 0xFF) return fail(MQC_HIP_ERR_DEVICE, "rimp2 stage: the stage wrote outside Bia, the pair partials and the results");
+    std::memcpy(e, h_out.data(), sizeof(double) * h_out.size());
+    return MQC_HIP_OK;
+}
+
 // the plan of an in-core SCF batch of ntot fragments of n functions: plan_layout picks the square or the triangle
 static BatchPlan jk_incore_plan(int n, int ntot, bool uhf)
 {

@@ -1,5 +1,5 @@
 """Stage-level entry points of the C ABI (mqc_hip_int1e, _eri_packed, _eri_packed_attenuated, _jk_incore, _jk_direct,
-_coulomb_batch, _xc_batch, _df_jk_batch, _df_fit_batch, _jk_tensor_layout, _jk_incore_batch, _gradient_stage, _syev,
+_coulomb_batch, _xc_batch, _df_jk_batch, _df_fit_batch, _jk_tensor_layout, _jk_incore_batch, _gradient_stage, _rimp2_stage, _syev,
 _diis_coefficients) as numpy-in / numpy-out functions.  They run the same kernels the SCF
 driver launches and exist so that each row of the hot-path table can be parity-tested alone.
 Test infrastructure: a ctypes helper for tests/, not part of the product package."""
@@ -178,6 +178,45 @@ def jk_incore_batch(tensor: np.ndarray, D: np.ndarray, unrestricted: bool = Fals
         0 if sl is None else len(sl), None if sl is None else ip(sl), None if q is None else capi.dptr(q), C.c_double(q_thresh),
         capi.dptr(J), capi.dptr(K), ip(loaded), route, len(route), C.byref(gx)))
     return J, K, loaded, route.value.decode(), gx.value
+
+
+RIMP2_ROUTE_FIELDS = ("clds", "npf", "waves", "oc", "gx", "lds", "napad", "nvpad", "npairs", "passes", "rows", "narrowed")
+
+
+def rimp2_route(n: int, n_occ: int, n_aux: int, n_frozen: int = 0, m: int = 1, workgroups_per_fragment: int = 0) -> dict:
+    """The host-only half of mqc_hip_rimp2_stage (no context, no device): the route the launcher of kern_mp2.hip takes for
+    m fragments of this shape, as a dict over RIMP2_ROUTE_FIELDS."""
+    route = np.full(16, -1, dtype=np.int32)
+    capi.check(capi.load_library().mqc_hip_rimp2_stage(None, int(m), int(n), int(n_occ), int(n_aux), int(n_frozen),
+                                                       int(workgroups_per_fragment), None, None, None, None, None, None, None, None,
+                                                       route.ctypes.data_as(capi.c_int32_p)))
+    return dict(zip(RIMP2_ROUTE_FIELDS, (int(v) for v in route)))
+
+
+def rimp2_stage(B: np.ndarray, C_mo: np.ndarray, eps: np.ndarray, n_occ: int, n_frozen: int = 0, nmo=None, runs=None,
+                workgroups_per_fragment: int = 0, want_bia: bool = True):
+    """mqc_hip_rimp2_stage: B (m, n_aux, npair) packed pairs fastest, C (m, n, n), eps (m, n) -> e (m, 2), the pair
+    partials (m, npairs, 2), Bia (m, no, napad, nvpad) with its padding (None unless want_bia) and the route as a dict.
+    nmo, runs (m,): kept orbitals and the run flag of each fragment (default: n, 1).  Every output starts as NaN."""
+    B = np.ascontiguousarray(B, dtype=np.float64)
+    C_mo = np.ascontiguousarray(C_mo, dtype=np.float64)
+    eps = np.ascontiguousarray(eps, dtype=np.float64)
+    m, n = C_mo.shape[0], C_mo.shape[-1]
+    assert B.shape[0] == m and B.shape[2] == n * (n + 1) // 2 and C_mo.shape == (m, n, n) and eps.shape == (m, n)
+    nmo = np.full(m, n, dtype=np.int32) if nmo is None else np.ascontiguousarray(nmo, dtype=np.int32)
+    runs = np.ones(m, dtype=np.int32) if runs is None else np.ascontiguousarray(runs, dtype=np.int32)
+    no, napad, nvpad = n_occ - n_frozen, (B.shape[1] + 3) // 4 * 4, (n - n_occ + 15) // 16 * 16
+    e, part = np.full((m, 2), np.nan), np.full((m, no * (no + 1) // 2, 2), np.nan)
+    bia = np.full((m, no, napad, nvpad), np.nan) if want_bia else None
+    route = np.full(16, -1, dtype=np.int32)
+    ip = lambda a: a.ctypes.data_as(capi.c_int32_p)
+    capi.check(capi.load_library().mqc_hip_rimp2_stage(capi.get_context(), m, n, int(n_occ), B.shape[1], int(n_frozen),
+                                                       int(workgroups_per_fragment), capi.dptr(B), capi.dptr(C_mo), capi.dptr(eps), ip(nmo),
+                                                       ip(runs), capi.dptr(e), capi.dptr(part), None if bia is None else capi.dptr(bia),
+                                                       ip(route)))
+    rt = dict(zip(RIMP2_ROUTE_FIELDS, (int(v) for v in route)))
+    assert (rt["napad"], rt["nvpad"], rt["npairs"]) == (napad, nvpad, part.shape[1])
+    return e, part, bia, rt
 
 
 def unpack_pairs(P: np.ndarray) -> np.ndarray:
